@@ -70,9 +70,39 @@ def make_step(model, wave):
     return step
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, result, seed=0):
+    """--dump-outputs: what one call of the timed step returned -- the decoded waveform (B, 1, samples) and the prosody / content /
+    residual code indices (B, n_q, frames) -- as <out_dir>/<name>.npy: the waveform in float32, the codes in float64 (exact).  When
+    the arrays exceed 64 MB together, every one keeps the same seeded sample of clips (dim 0); clip_index.npy names the clips kept."""
+    import numpy as np
+    y, (codes_p, codes_c, codes_r) = result
+    arrays = {"wave_out": y.float(), "codes_p": codes_p.double(), "codes_c": codes_c.double(), "codes_r": codes_r.double()}
+    batch = y.shape[0]
+    per_clip = sum(a[0].numel() * a.element_size() for a in arrays.values()) + 8
+    keep = max(1, min(batch, (DUMP_LIMIT_BYTES - 4096) // per_clip))        # 4 KB for the .npy headers
+    idx = torch.arange(batch)
+    if keep < batch:
+        idx = torch.randperm(batch, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+    arrays["clip_index"] = idx.double()
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        if name != "clip_index":
+            a = a[idx]
+        arr = a.numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2 ** 20:.1f} MB, {keep} of {batch} clips -> {out_dir}",
+          file=sys.stderr, flush=True)
+
+
 def check_codes(model, device):
     """Correctness gate of the metric ("...; code-index match"), part 1: the six code streams of the two golden clips must EQUAL
-    the REAL reference's (tests/golden/codec_e2e.npz was produced by importing /root/reference); any difference aborts the run
+    the REAL reference's (tests/golden/codec_e2e.npz was produced by running the reference implementation); any difference aborts the run
     (the near-tie triage of facodec_amd/diagnostics.py only words the message)."""
     import numpy as np
     from facodec_amd.diagnostics import LatentCapture, classify_faquantizer_codes
@@ -576,7 +606,11 @@ def main():
     ap.add_argument("--no-streaming", action="store_true", help="skip the configs[4] streaming-latency leg")
     ap.add_argument("--stream-hops", type=int, default=90000, help="configs[4]: 90 000 hops of 480 samples = 30 min of audio (~110 s)")
     ap.add_argument("--stream-check-minutes", type=float, default=5.0, help="prefix of the stream compared with the offline model")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, <= 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:          # child of cpu_baseline_isolated(): the CPU oracle only, no GPU
         r = (cpu_baseline(sweep_only=True, with_train=False) if args.cpu_worker == "sweep"
@@ -612,6 +646,12 @@ def main():
     codes_match = bool(codes_e2e and (codes_b32 is None or codes_b32["ok"]) and (codes_x4 is None or all(b["ok"] for b in codes_x4)))
     step = make_step(model, wave)
     sync = torch.cuda.synchronize
+    last = [None]
+    if args.dump_outputs:
+        def timed_step():                  # the same step; keeps what its last call returned
+            last[0] = step()
+    else:
+        timed_step = step
 
     prof = None
     if not args.no_roofline:
@@ -621,10 +661,13 @@ def main():
         sync()
         prof = ops.ConvLaunchProfile()
         ops.set_conv_profile(prof)
-        elapsed = benchutil.timed_steps(step, args.steps, 0, sync, device)
+        elapsed = benchutil.timed_steps(timed_step, args.steps, 0, sync, device)
         ops.set_conv_profile(None)
     else:
-        elapsed = benchutil.timed_steps(step, args.steps, args.warmup, sync, device)
+        elapsed = benchutil.timed_steps(timed_step, args.steps, args.warmup, sync, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    last[0] = None
 
     units = benchutil.aggregate_units(args.batch * CLIP_SECONDS * args.steps, device)
     value = units / elapsed

@@ -302,31 +302,32 @@ def test_focal_recon_meldataset_against_reference(golden_dir):
 def test_train_iteration_oracle_against_reference(golden_dir):
     """The whole iteration of train.py:265-374 replayed through the oracle + torch autograd against the real reference's
     .train() run (tests/golden/train_step.npz): 17 loss scalars, 5 gradient norms, gradient probes of ~60 tensors,
-    the set of parameters that receive no gradient, and the discriminator's weights after its AdamW step."""
-    from facodec_amd.commons import build_model, default_model_params
-    import train_replay as TR
-    fx = TR.load_fixture(golden_dir)
-    model = build_model(default_model_params())            # parameter / buffer holders on the CPU (no forward here)
-    for k in TR.KEYS:
-        synth.load_synthetic(model[k], seed=0, prefix=k + ".")
-    sds, names = TR.product_state(model)
-    sc, grads, norms, d_after = TR.oracle_iteration(O, sds, names, fx)
-    for k in TR.SCALARS:
-        assert abs(sc[k] - float(fx[k])) / abs(float(fx[k])) < 2e-5, (k, sc[k], float(fx[k]))
-    for k in TR.KEYS:
+    the set of parameters that receive no gradient, and the discriminator's weights after its AdamW step.
+    The replay runs in a fresh process on MKL's COMPATIBLE code path and 8 threads (the fixture's thread count): its worst
+    gradient probes sit at the conditioning floor of the next test (a rounding-level change moves them by ~1e-4), so the
+    1e-4 bar holds only where the summation order does not follow the host -- MKL's per-CPU kernels and the thread split
+    did (a 128-thread host with another vendor's CPU: 1.02e-4; 4.7e-4 on one discriminator probe at any thread count)."""
+    import subprocess
+    import sys
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE")        # read when MKL initialises: hence the fresh process
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_replay.py"), golden_dir, "8"],
+                       env=env, capture_output=True, text=True, timeout=1800)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rep = json.loads(r.stdout.splitlines()[-1])
+    assert len(rep["scalars"]) == 17 and len(rep["norms"]) == len(rep["worst_probe"]) == 5 and rep["no_grad"] and rep["param_after_err"]
+    for k, (got, ref) in rep["scalars"].items():
+        assert abs(got - ref) / abs(ref) < 2e-5, (k, got, ref)
+    for k, (norm, ref64, ref32) in rep["norms"].items():
         # fp64 norm over the key; the reference's own clip_grad_norm_ value (fp32 accumulation over ~1e8 elements) is kept
         # in the fixture too and sits up to 4.5e-4 away from it
-        assert abs(norms[k] - float(fx[f"grad_norm64_{k}"])) / float(fx[f"grad_norm64_{k}"]) < 1e-5, k
-        assert abs(norms[k] - float(fx[f"grad_norm_{k}"])) / float(fx[f"grad_norm_{k}"]) < 1e-3, k
-        worst = TR.compare_grads(fx, k, grads[k], 1e-4, 1e-4)
+        assert abs(norm - ref64) / ref64 < 1e-5, k
+        assert abs(norm - ref32) / ref32 < 1e-3, k
+        worst = rep["worst_probe"][k]
         assert worst[1] < 1e-4 and worst[2] < 1e-4, worst
-    for k, missing in fx["no_grad"].items():
-        assert sorted(n for n in names[k] if n not in grads[k]) == sorted(missing), k
-    for key in fx:
-        if key.startswith("param_after.discriminator."):
-            n = key[len("param_after.discriminator."):-len(".probe")]
-            flat = d_after[n].reshape(-1)
-            assert np.abs(flat[TR.probe_index(flat.numel())].numpy() - fx[key]).max() < 1e-6, n
+    for k, (got, missing) in rep["no_grad"].items():
+        assert got == missing, k
+    for n, err in rep["param_after_err"].items():
+        assert err < 1e-6, n
 
 
 def test_gradient_probe_conditioning_justifies_the_gpu_bars(golden_dir):

@@ -64,3 +64,36 @@ def oracle_iteration(O, sds, param_names, fx):
     """train.py:265-374 through the oracle + torch autograd (oracle/train_iteration.py)."""
     from oracle.train_iteration import oracle_iteration as it
     return it(sds, param_names, fx["t"])
+
+
+def replay_report(golden_dir):
+    """oracle_iteration on the formula weights (seed 0), reduced to what tests/test_oracle_golden.py::
+    test_train_iteration_oracle_against_reference checks, as JSON-able values next to the fixture's."""
+    from facodec_amd import synth
+    from facodec_amd.commons import build_model, default_model_params
+    from oracle import facodec_oracle as O
+    fx = load_fixture(golden_dir)
+    model = build_model(default_model_params())            # parameter / buffer holders on the CPU (no forward here)
+    for k in KEYS:
+        synth.load_synthetic(model[k], seed=0, prefix=k + ".")
+    sds, names = product_state(model)
+    sc, grads, norms, d_after = oracle_iteration(O, sds, names, fx)
+    after = {}
+    for key in fx:
+        if key.startswith("param_after.discriminator."):
+            n = key[len("param_after.discriminator."):-len(".probe")]
+            flat = d_after[n].reshape(-1)
+            after[n] = float(np.abs(flat[probe_index(flat.numel())].numpy() - fx[key]).max())
+    return {"scalars": {k: [float(sc[k]), float(fx[k])] for k in SCALARS},
+            "norms": {k: [float(norms[k]), float(fx[f"grad_norm64_{k}"]), float(fx[f"grad_norm_{k}"])] for k in KEYS},
+            "worst_probe": {k: list(compare_grads(fx, k, grads[k], 1e-4, 1e-4)) for k in KEYS},
+            "no_grad": {k: [sorted(n for n in names[k] if n not in grads[k]), sorted(missing)] for k, missing in fx["no_grad"].items()},
+            "param_after_err": after}
+
+
+if __name__ == "__main__":
+    # python tests/train_replay.py GOLDEN_DIR THREADS: replay_report as one JSON line, on THREADS intra-op threads
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    torch.set_num_threads(int(sys.argv[2]))
+    print(json.dumps(replay_report(sys.argv[1])), flush=True)

@@ -6,7 +6,7 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from facodec_amd import autograd as A  # noqa: E402
 from facodec_amd import ops, synth  # noqa: E402
 from facodec_amd.layers import SConv1d  # noqa: E402

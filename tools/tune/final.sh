@@ -2,8 +2,8 @@
 # the training step (rocprofv3 kernel trace), FETCH_SIZE / WRITE_SIZE passes for the traffic table, matrix-pipe counters.
 # usage: bash tools/tune/final.sh <round tag, e.g. r04> <git sha of the tree>
 TAG=${1:-rXX}; SHA=${2:-unknown}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -3 $O/pytest.log
 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 300 $O/bench_line.json; echo

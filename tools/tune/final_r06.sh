@@ -2,8 +2,8 @@
 # step, FETCH / WRITE passes for roofline.traffic, matrix-pipe / LDS counters of the forward, the train step's counter table, GPU
 # idle analysis, the HBM-kernel table, the host profile.   usage: bash tools/tune/final_r06.sh <tag> <git sha>
 TAG=${1:-r06}; SHA=${2:-unknown}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -3 $O/pytest.log
 python bench.py --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err; tail -c 400 $O/bench_line.json; echo
@@ -19,8 +19,8 @@ python $R/tools/pmc_mfma.py $(find $O/pmc_m -name "*counter_collection.csv" | he
 rm -rf $O/pmc_f $O/pmc_w $O/pmc_m $O/kb
 cd $R
 bash tools/tune/pmc_train.sh ${TAG}_pmc > $O/pmc_train.log 2>&1; tail -20 $O/pmc_train.log | cut -c1-180
-cp $R/gpurun_out/${TAG}_pmc/pmc_train.json $O/pmc_train.json; cp $R/gpurun_out/${TAG}_pmc/train_kernel_stats.csv $O/train_kernel_stats_one_stream.csv
-bash tools/tune/r6_idle.sh ${TAG}_idle > $O/idle.log 2>&1; cp $R/gpurun_out/${TAG}_idle/gpu_idle_train.json $O/gpu_idle_train.json
+cp $OUT/${TAG}_pmc/pmc_train.json $O/pmc_train.json; cp $OUT/${TAG}_pmc/train_kernel_stats.csv $O/train_kernel_stats_one_stream.csv
+bash tools/tune/r6_idle.sh ${TAG}_idle > $O/idle.log 2>&1; cp $OUT/${TAG}_idle/gpu_idle_train.json $O/gpu_idle_train.json
 python tools/elementwise_bench.py --pmc $O/pmc_train.json --out $O/hbm_kernels.json > $O/elementwise.log 2>&1
 python tools/tune/host_profile.py 30 > $O/host_profile.log 2>&1
 python tools/fwd_layers.py > $O/fwd_layers.log 2>&1

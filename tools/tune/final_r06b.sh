@@ -1,8 +1,8 @@
 # Final-tree measurement set of round 6 (one box, one call): seeded train record, the default bench line (its own check of that record
 # included), kernel stats of the train step with every chain serial, GPU idle analysis.   usage: bash tools/tune/final_r06b.sh <tag>
 TAG=${1:-r06fin3}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 python bench.py --no-cpu-baseline --no-streaming --record-train-loss > $O/record_line.json 2> $O/record.err
 cp tests/golden/bench_train_seeded.json $O/bench_train_seeded.json

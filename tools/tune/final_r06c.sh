@@ -2,8 +2,8 @@
 # stats of the forward bench and of the train step (every chain serial), LDS bank-conflict counters of the train step.
 # usage: bash tools/tune/final_r06c.sh <tag>
 TAG=${1:-r06fin4}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 python bench.py --no-cpu-baseline --no-streaming --record-train-loss > $O/record_line.json 2> $O/record.err
 cp tests/golden/bench_train_seeded.json $O/bench_train_seeded.json

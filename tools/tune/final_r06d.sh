@@ -1,8 +1,8 @@
 # Final-tree measurement set of round 6, third session (one box, one call): the default bench line, rocprof kernel stats of the forward
 # bench and of the train step (every chain serial).   usage: bash tools/tune/final_r06d.sh <tag>
 TAG=${1:-r06fin5}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 t0=$(date +%s)
 python bench.py --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
@@ -19,4 +19,4 @@ tail -3 $O/bench.err
 cp $(find $O/kf -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv; rm -rf $O/kf
 head -14 $O/bench_kernel_stats.csv | cut -c1-150
 bash tools/tune/train_stats.sh ${TAG}_ts > $O/train_stats.log 2>&1; tail -36 $O/train_stats.log | cut -c1-150
-cp $R/gpurun_out/${TAG}_ts/train_kernel_stats_one_stream.csv $O/ 2>/dev/null
+cp $OUT/${TAG}_ts/train_kernel_stats_one_stream.csv $O/ 2>/dev/null

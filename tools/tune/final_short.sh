@@ -1,8 +1,8 @@
 # Bench line + forward kernel stats + FETCH / WRITE traffic passes of the current tree (the subset of final.sh that changes when
 # only forward launches changed).  usage: bash tools/tune/final_short.sh <tag> <git sha>
 TAG=${1:-rXX}; SHA=${2:-unknown}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd $R
 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 300 $O/bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp

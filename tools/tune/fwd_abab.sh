@@ -1,6 +1,6 @@
 # forward (configs[1]) A/B on one box, B first then alternating three times: $2 = environment of the B leg
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-fwd_abab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-fwd_abab}; mkdir -p $O
 cd $R
 for i in 1 2 3; do
   env $2 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-streaming 2>>$O/err.log | tail -1 | python -c "

@@ -1,6 +1,6 @@
 import ctypes, os, sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from facodec_amd import ops, _lib
 lib = _lib.load()
 dev = torch.device("cuda:0")

@@ -1,10 +1,10 @@
 # Counters for the kernels of the configs[2] training step AT THE STEP'S OWN SHAPES (B = 16 x 2 s, predictor heads, every chain
 # serial so that kernel times add up): one un-profiled kernel trace for the durations, then separate --pmc passes (SQ issue /
 # wait / matrix-pipe counters, LDS counters, FETCH_SIZE, WRITE_SIZE -- never combined with other trace domains).
-# usage: bash tools/tune/pmc_train.sh <tag> [extra env assignments ...]      -> gpurun_out/<tag>/pmc_train.json
+# usage: bash tools/tune/pmc_train.sh <tag> [extra env assignments ...]      -> $OUT/<tag>/pmc_train.json
 TAG=${1:-pmc_train}; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export FAC_DISC_STREAMS=1 FAC_PRED_STREAMS=1 FAC_QUANT_STREAMS=1 FAC_MEL_STREAMS=1 "$@"
 CMD="$R/tools/train_bench.py --batch 16 --steps 2 --warmup 1 --predictors"

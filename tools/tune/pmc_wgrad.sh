@@ -1,7 +1,7 @@
 # FETCH_SIZE of the weight-gradient GEMM kernel with the plain 3-D grid and with the XCD-aware order (tools/wgrad_bench.py shapes).
-# usage: bash tools/tune/pmc_wgrad.sh <out dir under gpurun_out>
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-pmc_wgrad}; mkdir -p $O
+# usage: bash tools/tune/pmc_wgrad.sh <out dir under $OUT>
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-pmc_wgrad}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for v in 0 1; do
   FAC_WGRAD_XCD=$v FAC_WGRAD_KSPLIT=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/f$v -o f -- python $R/tools/wgrad_bench.py > $O/run_$v.log 2>&1

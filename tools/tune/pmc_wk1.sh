@@ -1,7 +1,7 @@
 # Counters of conv1d_wgrad_k1.hip at the train step's three shapes: HBM bytes per launch (FETCH_SIZE / WRITE_SIZE, separate passes, the
 # guide's gfx950 corrections) against the algorithmic 8 bytes per element pair, matrix-pipe busy.   usage: bash tools/tune/pmc_wk1.sh <tag>
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-pmc_wk1}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-pmc_wk1}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   n=$(echo $c | cut -d' ' -f1)

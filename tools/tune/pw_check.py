@@ -1,5 +1,5 @@
 import os, sys, json, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from facodec_amd import synth
 from facodec_amd.commons import build_model, default_model_params
 from facodec_amd.train import TrainStep

@@ -1,8 +1,8 @@
 # HBM traffic (counters) of the streaming bf16-plane kernels at the forward's shapes against their algorithmic bytes.
 # Separate --pmc passes for FETCH_SIZE and WRITE_SIZE (MI355X_MICROARCH.md, HBM section).   usage: bash tools/tune/pws_traffic.sh <tag>
 TAG=${1:-pws_traffic}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/$TAG; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/$c -o p -- python $R/tools/tune/pws_ab.py > $O/$c.log 2>$O/$c.err

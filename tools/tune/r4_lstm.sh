@@ -1,5 +1,5 @@
 # split resident LSTM: tests, layer timings, forward bench with / without it, cpu thread sweep, bench watchdog
-R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r4_lstm; mkdir -p $O; cd $R
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT; O=$OUT/r4_lstm; mkdir -p $O; cd $R
 timeout 900 python -m pytest tests/test_lstm_persist.py -x -q > $O/pytest_lstm.log 2>&1; tail -5 $O/pytest_lstm.log
 FAC_LSTM_PERSIST_MAX_BATCH=32 timeout 300 python tools/lstm_bench.py > $O/lstm_bench.log 2>&1; cat $O/lstm_bench.log | cut -c1-600
 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train --no-streaming > $O/bench_split.json 2> $O/bench_split.err; tail -c 400 $O/bench_split.err; python -c "

@@ -1,5 +1,5 @@
 # P8 pre-pass policy: parity, forward bench with / without
-R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r4_p8; mkdir -p $O; cd $R
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT; O=$OUT/r4_p8; mkdir -p $O; cd $R
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_rccl_one_rank.py -x -q -k "p8 or flattened or slstm or conv_transpose or end_to_end or rccl or one_rank" > $O/pytest.log 2>&1; tail -4 $O/pytest.log
 for i in 1 2; do
 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train --no-streaming > $O/bench_on_$i.json 2>/dev/null; python -c "

@@ -1,5 +1,5 @@
 # k = 7 kernel walking several tiles per workgroup: parity, layer timings against the one-tile build, forward bench
-R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r4_persist; mkdir -p $O; cd $R
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT; O=$OUT/r4_persist; mkdir -p $O; cd $R
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "split or conv1d_against or residual_unit or p8 or end_to_end or encoder_decoder" > $O/pytest_conv.log 2>&1; tail -4 $O/pytest_conv.log
 for i in 1 2; do
 python tools/tune/abl_bsplit.py 2>/dev/null | tail -1

@@ -1,5 +1,5 @@
 # the linearity test (B = 16 vs two B = 8 halves) N times per variant: round-5 tree (worktree _old) against this tree under switches
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 run() {  # dir, env..., -> pass/fail counts
   d=$1; shift
   p=0; f=0; vals=""

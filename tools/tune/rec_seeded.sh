@@ -1,5 +1,5 @@
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/rec3; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/rec3; mkdir -p $O
 cd $R
 python bench.py --no-cpu-baseline --no-streaming --record-train-loss > $O/record_line.json 2> $O/record.err
 cp tests/golden/bench_train_seeded.json $O/bench_train_seeded.json

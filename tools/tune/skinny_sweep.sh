@@ -1,6 +1,6 @@
 # split-reduction conv geometry sweep on the streaming hop (serial chain = clean signal; then the two-chain hop for the best few)
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-skinny_sweep}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-skinny_sweep}; mkdir -p $O
 cd $R
 run() {  # $1 = label, rest = env
   env "${@:2}" python tools/stream_bench.py --minutes 0.3 2>>$O/err.log | python -c "

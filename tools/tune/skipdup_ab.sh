@@ -1,6 +1,6 @@
 # weight-gradient row tiles with clamped duplicate rows: duplicates not staged (FAC_WGRAD_SKIP_DUP) -- tests, per-shape listing of the step, train A/B
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-skipdup}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-skipdup}; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_wgrad_split.py -x -q -m gpu 2>&1 | tail -3 | tee $O/test.log
 for v in 0 1; do

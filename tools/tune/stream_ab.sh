@@ -1,6 +1,6 @@
 # streaming hop A/B on one box: FAC_STREAM_FOLD=0 (separate elementwise launches) vs 1, alternating; $2 = extra env (e.g. FAC_STREAM_TWO_STREAMS=0)
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-stream_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-stream_ab}; mkdir -p $O
 cd $R
 for i in 1 2; do
   for f in 0 1; do

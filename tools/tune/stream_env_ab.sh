@@ -1,6 +1,6 @@
 # streaming hop A/B on one box, alternating: $2 = environment of the B leg; $3 = minutes per run
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-stream_env_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-stream_env_ab}; mkdir -p $O
 cd $R
 for i in 1 2 3; do
   for leg in "X=1" "$2"; do

@@ -1,7 +1,7 @@
 # configs[4], 30 minutes of audio, twice: alone, and next to a loop that polls the device through rocm-smi every 5 s -- do the rare
-# ~20 ms device-side hops follow a monitoring agent's polling?   -> gpurun_out/<tag>/streaming_poller_ab.json
-R=${GRAFT_REPO_ROOT:-/root/repo}
-export O=$R/gpurun_out/${1:-poller}; mkdir -p $O
+# ~20 ms device-side hops follow a monitoring agent's polling?   -> $OUT/<tag>/streaming_poller_ab.json
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+export O=$OUT/${1:-poller}; mkdir -p $O
 cd $R
 python tools/stream_bench.py --minutes 30 > $O/alone.json 2>$O/alone.err
 ( while true; do rocm-smi --showuse --showmemuse --showtemp --showpower > /dev/null 2>&1; sleep 5; done ) &

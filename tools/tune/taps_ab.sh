@@ -1,7 +1,7 @@
 # first-layer weight gradients on the virtual-row form of conv1d_wgrad_k1.hip: tests, per-shape listing, train A/B (FAC_WGRAD_K1_STREAM=0 turns
 # both this and the k = 1 tails off)
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-taps}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-taps}; mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests/test_wgrad_split.py tests/test_train_golden.py -x -q -m gpu 2>&1 | tail -4 | tee $O/test.log
 python tools/train_wgrads.py 2>/dev/null > $O/wgrads.log; head -1 $O/wgrads.log; grep "^ *[0-9]* *[12]    \(32\|64\) " $O/wgrads.log | head -20

@@ -1,6 +1,6 @@
 # train-step A/B on one box, alternating: $2 = the environment setting of the B leg (e.g. FAC_NARROW_TWO_LEVEL=0)
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-train_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-train_ab}; mkdir -p $O
 cd $R
 for i in 1 2; do
   python tools/train_bench.py --batch 16 --steps 6 --warmup 2 --predictors 2>>$O/err.log | tail -1 | python -c "

@@ -1,6 +1,6 @@
 # kernel stats of the train step, every chain serial (kernel times add up)   usage: bash tools/tune/train_stats.sh <tag>
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-tstats}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-tstats}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 FAC_DISC_STREAMS=1 FAC_PRED_STREAMS=1 FAC_QUANT_STREAMS=1 FAC_MEL_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o t -- python $R/tools/train_bench.py --batch 16 --steps 3 --warmup 1 --predictors > $O/line.json 2>$O/kt.err
 cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/train_kernel_stats_one_stream.csv

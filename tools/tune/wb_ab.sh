@@ -1,6 +1,6 @@
 # batched weight preparation (FAC_WEIGHT_BATCH) A/B on one box: new tests, forward alternating, train step alternating
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-wb_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-wb_ab}; mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests/test_weight_batch.py -x -q -m gpu 2>&1 | tail -15 | tee $O/test.log
 for i in 1 2; do

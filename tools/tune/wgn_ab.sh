@@ -1,6 +1,6 @@
 # column-split wave layouts of the weight gradient (FAC_WGRAD_NARROW) + the rest of the weight-batch tests: tests, per-shape bench, train A/B
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-wgn_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-wgn_ab}; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests/test_weight_batch.py tests/test_wgrad_split.py -x -q -m gpu 2>&1 | tail -15 | tee $O/test.log
 for nv in 0 1; do

@@ -1,6 +1,6 @@
 # k = 1 small-channel weight gradients on the fp32 streaming kernel (FAC_WGRAD_K1_STREAM): tests, per-shape bench, train A/B
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out/${1:-wk1_ab}; mkdir -p $O
+R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
+O=$OUT/${1:-wk1_ab}; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_wgrad_split.py tests/test_weight_batch.py -x -q -m gpu 2>&1 | tail -15 | tee $O/test.log
 for v in 0 1; do
