@@ -44,6 +44,18 @@ class VqDesc(C.Structure):
     ]
 
 
+
+VQ_DECODE_MAX_Q = 16
+
+
+class VqDecodeDesc(C.Structure):
+    _fields_ = [
+        ("codes", _p * 3), ("codes_bs", _i64 * 3), ("codes_qs", _i64 * 3), ("n_q", C.c_int32 * 3),
+        ("codebook", _p * VQ_DECODE_MAX_Q), ("w_out", _p * VQ_DECODE_MAX_Q), ("w_out_scale", _p * VQ_DECODE_MAX_Q),
+        ("b_out", _p * VQ_DECODE_MAX_Q), ("style", _p), ("outs", _p), ("z", _p * 3),
+        ("B", C.c_int32), ("D", C.c_int32), ("T", C.c_int32), ("Kc", C.c_int32),
+    ]
+
 # name -> (restype, argtypes); must list every symbol include/facodec_hip.h declares
 SIGNATURES = {
     "fac_version": (_i, []),
@@ -148,6 +160,7 @@ SIGNATURES = {
     "fac_stream_push": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _p]),
     "fac_vq_fwd": (_i, [C.POINTER(VqDesc), _p]),
     "fac_vq_loss_tiles": (_i, [_i]),
+    "fac_vq_decode": (_i, [C.POINTER(VqDecodeDesc), _p]),
     "fac_rccl_available": (_i, []),
     "fac_rccl_unique_id": (_i, [_p]),
     "fac_rccl_comm_init": (_i, [C.POINTER(_p), _p, _i, _i]),

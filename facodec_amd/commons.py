@@ -94,6 +94,20 @@ def default_redecoder_params():
         DAC=dict(encoder_dim=64, encoder_rates=[2, 5, 5, 6], decoder_dim=1536, decoder_rates=[6, 5, 5, 2], sr=24000)))
 
 
+@torch.no_grad()
+def decode_codes(model, codes, timbre):
+    """Codes + timbre -> waveform, the counterpart of reconstruct.py's encode -> quantize -> decode:
+
+        z = model.encoder(wave)
+        _, _, _, _, timbre, codes = model.quantizer(z, wave, n_c=2, return_codes=True)
+        wave_hat = decode_codes(model, codes, timbre)                  # (B, 1, 300 T)
+        converted = decode_codes(model, codes, other_timbre)           # timbre swap (zero-shot voice conversion)
+
+    codes = [codes_p, codes_c, codes_r] (B, n, T) int64; timbre (B, 1024).  FAquantizer.decode_input (one fac_vq_decode launch)
+    then the decoder."""
+    return model.decoder(model.quantizer.decode_input(codes, timbre))
+
+
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):
     """modules/commons.py:446-471: {'net': {key: state_dict}, ...}; strips DDP's 'module.' prefix."""
     state = torch.load(path, map_location="cpu")

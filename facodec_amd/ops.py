@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from .wprep import prepared
-from ._lib import ConvDesc, VqDesc, PAD_REFLECT, PAD_ZERO, ACT_NONE, ACT_TANH, ACT_MISH, ACT_LOG_MEL, ACT_GATE, ACT_WN_RES_SKIP  # noqa: F401
+from ._lib import ConvDesc, VqDesc, VqDecodeDesc, PAD_REFLECT, PAD_ZERO, ACT_NONE, ACT_TANH, ACT_MISH, ACT_LOG_MEL, ACT_GATE, ACT_WN_RES_SKIP  # noqa: F401
 
 
 def pad32(n):
@@ -1004,6 +1004,53 @@ def vq_step(z_in, w_in_packed, b_in, codebook, w_out, w_out_scale, b_out, codes_
     d.codes_bs = codes_out.stride(0)
     d.B, d.D, d.T, d.Kc = B, D, T, codebook.shape[0]
     _lib.check(_lib.load().fac_vq_fwd(C.byref(d), _stream()), "fac_vq_fwd")
+
+
+def vq_decode(codes, weights, style, Kc, out=None, z_out=(None, None, None)):
+    """Codes of the prosody / content / residual RVQs -> decoder input (fac_vq_decode: from_codes of each RVQ, their sum, the
+    timbre-conditioned LayerNorm).  codes: three int64 (B, n_r, T) tensors (any batch / row stride, unit frame stride) or None
+    for an RVQ without quantizers; weights: per RVQ a list of n_r tuples (codebook (Kc, 8), out_proj weight_v (D, 8, 1),
+    weight-norm scale (D) or None, bias (D)); style (B, 2D) = [gamma | beta].  z_out: optional (B, D, T) buffers for the
+    per-RVQ sums.  Codes are not range checked here (the kernel clamps them for the load)."""
+    style = _dev(style, "style")
+    B, D2 = style.shape
+    D = D2 // 2
+    d = VqDecodeDesc()
+    T, q = None, 0
+    for r in range(3):
+        c, ws = codes[r], weights[r]
+        n = 0 if c is None else c.shape[1]
+        if n != len(ws):
+            raise ValueError(f"vq_decode: RVQ {r} has {n} code rows but {len(ws)} weight sets")
+        if c is not None:
+            if not c.is_cuda:
+                raise _lib.FacodecHipError(f"codes must live on the GPU (got {c.device}); there is no CPU path")
+            assert c.dtype == torch.int64 and c.dim() == 3 and c.shape[0] == B and (c.stride(-1) == 1 or c.shape[-1] == 1)
+            if T is None:
+                T = c.shape[-1]
+            assert c.shape[-1] == T
+            d.codes[r], d.codes_bs[r], d.codes_qs[r] = c.data_ptr(), c.stride(0), c.stride(1)
+        d.n_q[r] = n
+        for cb, wv, sc, bo in ws:
+            if q >= _lib.VQ_DECODE_MAX_Q:
+                raise ValueError(f"vq_decode: more than {_lib.VQ_DECODE_MAX_Q} quantizers")
+            d.codebook[q], d.w_out[q], d.b_out[q] = _dev(cb, "codebook").data_ptr(), _dev(wv, "weight_v").data_ptr(), _dev(bo, "bias").data_ptr()
+            d.w_out_scale[q] = _dev(sc, "scale").data_ptr() if sc is not None else None
+            q += 1
+    if T is None:
+        raise ValueError("vq_decode: no codes (the frame count comes from them)")
+    if out is None:
+        out = torch.empty(B, D, T, device=style.device, dtype=torch.float32)
+    d.style, d.outs = style.data_ptr(), out.data_ptr()
+    for r in range(3):
+        zo = z_out[r]
+        if zo is not None:
+            assert zo.is_contiguous() and tuple(zo.shape) == (B, D, T) and zo.dtype == torch.float32
+        d.z[r] = zo.data_ptr() if zo is not None else None
+    assert out.is_contiguous() and tuple(out.shape) == (B, D, T)
+    d.B, d.D, d.T, d.Kc = B, D, T, Kc
+    _lib.check(_lib.load().fac_vq_decode(C.byref(d), _stream()), "fac_vq_decode")
+    return out
 
 
 def vq_loss_tiles(T):

@@ -49,6 +49,17 @@ class VectorQuantize(nn.Module):
         v = self.out_proj.weight_v.detach()
         return self.in_proj.packed(), v, ops.wn_scale(v, self.out_proj.weight_g.detach())
 
+    def decode_weights(self):
+        """(codebook (Kc, 8), out_proj weight_v (D, 8, 1), its weight-norm scale (D,), bias (D,)): what fac_vq_decode reads."""
+        v = self.out_proj.weight_v.detach()
+        return self.codebook.weight.detach(), v, ops.wn_scale(v, self.out_proj.weight_g.detach()), self.out_proj.bias.detach()
+
+    @torch.no_grad()
+    def decode_code(self, embed_id):
+        """dac/nn/quantize.py:72-76: codes (B, T) int64 -> raw codebook rows (B, 8, T)."""
+        check_codes([embed_id.unsqueeze(1)], self.codebook_size)
+        return ops.embed_sum(embed_id.unsqueeze(1).contiguous(), self.codebook.weight.detach().unsqueeze(0))
+
     def forward(self, z):
         B, D, T = z.shape
         codes = torch.empty(B, T, device=z.device, dtype=torch.int64)
@@ -107,6 +118,39 @@ class ResidualVectorQuantize(nn.Module):
         per = lp.sum(2) / float(8 * T)       # (n, B)  mean over (8, T) per sample
         loss = per.mean(1).sum()             # mean over batch, summed over quantizers
         return z_q, codes, latents, loss, loss.clone()
+
+
+    @torch.no_grad()
+    def from_codes(self, codes):
+        """dac/nn/quantize.py:200-220: codes (B, N, T) int64, N <= n_codebooks -> (z_q (B, D, T), z_p (B, 8N, T) = the looked-up
+        codebook rows, codes).  z_q is the sum of the first N quantizers' out_proj(codebook[code]) (fac_vq_decode)."""
+        B, N, T = codes.shape
+        if N > self.n_codebooks:
+            raise ValueError(f"from_codes: {N} code rows for {self.n_codebooks} quantizers")
+        check_codes([codes], self.codebook_size)
+        D = self.quantizers[0].input_dim
+        z_q = torch.empty(B, D, T, device=codes.device, dtype=torch.float32)
+        style = torch.zeros(B, 2 * D, device=codes.device, dtype=torch.float32)       # the kernel's normed output is not used
+        ops.vq_decode([codes, None, None], [[q.decode_weights() for q in self.quantizers[:N]], [], []], style,
+                      self.codebook_size, z_out=(z_q, None, None))
+        z_p = [self.quantizers[i].decode_code(codes[:, i]) for i in range(N)]
+        return z_q, (torch.cat(z_p, dim=1) if z_p else z_q.new_zeros(B, 0, T)), codes
+
+
+def check_codes(codes, codebook_size):
+    """Host-side validation of code tensors before a decode: int64, on the GPU, every index in [0, codebook_size) -- the range
+    check is one device-to-host read for all tensors.  The kernels clamp indices only to stay inside the codebook."""
+    flags = []
+    for c in codes:
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.int64:
+            raise TypeError(f"codes must be int64 tensors (got {getattr(c, 'dtype', type(c))})")
+        if not c.is_cuda:
+            from ._lib import FacodecHipError
+            raise FacodecHipError(f"codes must live on the GPU (got {c.device}); there is no CPU path")
+        if c.numel():
+            flags.append(((c < 0) | (c >= codebook_size)).any())
+    if flags and bool(torch.stack(flags).any()):
+        raise ValueError(f"codes outside [0, {codebook_size})")
 
 
 # ------------------------------------------------------------------------------------ WaveNet
@@ -472,3 +516,63 @@ class FAquantizer(nn.Module):
         return outs, quantized, commitment, codebook, timbre
 
     forward_v2 = forward
+
+    def decode_weights(self):
+        """Per RVQ (prosody, content, residual) the decode_weights() of every quantizer."""
+        return [[q.decode_weights() for q in rvq.quantizers]
+                for rvq in (self.prosody_quantizer, self.content_quantizer, self.residual_quantizer)]
+
+    def _check_decode_inputs(self, codes, timbre):
+        """-> quantizer counts (n_p, n_c, n_r) from the code tensors' row counts; validates the rest (ValueError / TypeError, and
+        FacodecHipError for CPU tensors like every product call)."""
+        if not isinstance(codes, (list, tuple)) or len(codes) != 3:
+            raise ValueError("codes must be [codes_p (B,n_p,T), codes_c (B,n_c,T), codes_r (B,n_r,T)]")
+        for c in codes:
+            if not isinstance(c, torch.Tensor) or c.dim() != 3:
+                raise ValueError("every code tensor must be (B, N, T)")
+        B, T = codes[0].shape[0], codes[0].shape[2]
+        for c, rvq in zip(codes, (self.prosody_quantizer, self.content_quantizer, self.residual_quantizer)):
+            if c.shape[0] != B or c.shape[2] != T:
+                raise ValueError(f"code tensors disagree on (B, T): {[tuple(x.shape) for x in codes]}")
+            if c.shape[1] > rvq.n_codebooks:
+                raise ValueError(f"{c.shape[1]} code rows for an RVQ of {rvq.n_codebooks} quantizers")
+        if T < 1:
+            raise ValueError("codes have no frames")
+        if not isinstance(timbre, torch.Tensor) or tuple(timbre.shape) != (B, self.in_dim) or timbre.dtype != torch.float32:
+            raise ValueError(f"timbre must be float32 ({B}, {self.in_dim}), got {getattr(timbre, 'shape', None)}")
+        if not timbre.is_cuda:
+            from ._lib import FacodecHipError
+            raise FacodecHipError(f"timbre must live on the GPU (got {timbre.device}); there is no CPU path")
+        check_codes(codes, self.prosody_quantizer.codebook_size)
+        return [c.shape[1] for c in codes]
+
+    def _decode(self, codes, timbre, want_quantized):
+        n_q = self._check_decode_inputs(codes, timbre)
+        B, T = codes[0].shape[0], codes[0].shape[2]
+        style = self.timbre_linear(timbre.contiguous())                    # (B, 2D) = [gamma | beta]
+        weights = [w[:n] for w, n in zip(self.decode_weights(), n_q)]
+        z = [torch.empty(B, self.in_dim, T, device=timbre.device, dtype=torch.float32) for _ in range(3)] if want_quantized else None
+        outs = ops.vq_decode([c if n else None for c, n in zip(codes, n_q)], weights, style, self.prosody_quantizer.codebook_size,
+                             z_out=z if want_quantized else (None, None, None))
+        return outs, z
+
+    @torch.no_grad()
+    @cached_forward
+    def from_codes(self, codes, timbre):
+        """Codes + timbre -> decoder input: per RVQ ResidualVectorQuantize.from_codes (dac/nn/quantize.py:200-220), then the tail
+        of forward_v2 (modules/quantize.py:436-449, eval: res_mask = 1) -- what `forward` hands the decoder, minus the
+        ulp-level straight-through term z_e + (z_q - z_e).  The reference's own `decode` (:244-255) reads a timbre_quantizer
+        that the shipped configuration (timbre_norm=True) does not build.
+
+        codes = [codes_p (B, n_p, T), codes_c (B, n_c, T), codes_r (B, n_r, T)] int64 as `forward(..., return_codes=True)`
+        returns them; the quantizer counts come from the row counts (0 included: n_c = 1, no residual ...).  timbre (B, 1024):
+        the clip's own (`forward`'s 5th output) or another speaker's (timbre swap, the paper's zero-shot voice conversion).
+        -> (outs (B, 1024, T), [z_p, z_c, z_r]).  One fac_vq_decode launch; codes outside [0, codebook_size) raise ValueError."""
+        outs, z = self._decode(codes, timbre, True)
+        return outs, z
+
+    @torch.no_grad()
+    @cached_forward
+    def decode_input(self, codes, timbre):
+        """`from_codes(codes, timbre)[0]` without writing the per-RVQ sums (the decode path)."""
+        return self._decode(codes, timbre, False)[0]

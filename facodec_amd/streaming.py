@@ -31,6 +31,7 @@ import torch
 from . import ops
 from .dac_model import FUSED_RU_CHANNELS, DecoderBlock, EncoderBlock
 from .layers import ConvWeights
+from .quantize import check_codes
 
 LSTM_REAL_COLUMNS = os.environ.get("FAC_STREAM_LSTM_REAL_COLUMNS", "1") != "0"     # _LSTMState.run
 HOP = 480            # samples per streaming hop (20 ms @ 24 kHz)
@@ -495,3 +496,138 @@ class StreamingCodec:
         if self.n_samples % FRAME:
             raise ValueError("finish(): stream length must be a multiple of 300 samples")
         return self._step(None, final=True)
+
+
+class StreamingDecoder:
+    """Receiver side of a streaming codec: codes in, audio out, over B parallel streams with a timbre fixed for the session.
+
+        rx = StreamingDecoder(model, timbre)                 # model = build_model(...) (causal), timbre (B, 1024)
+        wave = rx.prime(codes)                               # first chunk: >= rx.min_prime frames
+        wave = rx.push(codes)                                # any chunk of k >= 1 frames -> (B, 1, 300 k)
+
+    `codes` = [codes_p (B, n_p, k), codes_c (B, n_c, k), codes_r (B, n_r, k)] int64, the layout StreamingCodec emits
+    (`out["codes"]`); the row counts are fixed by prime().  The concatenated output equals decode_codes() of all codes
+    (commons.py) within fp32 noise: the codes-to-latent step is fac_vq_decode on a static code buffer, the decoder is the
+    sender's _DecoderStream (causal convs with left-context buffers, carried LSTM state).
+
+    Codes are NOT range checked per push (that would be one device-to-host read per hop and end the hop's independence from
+    the host): an index outside [0, codebook_size) decodes as the clamped index, without reading outside the codebook.
+    prime() does check its codes.
+
+    With use_graphs the hop is captured into one HIP graph per (previous k, k, LSTM step parity) -- a push's launches depend on
+    its own size, through the left-context shifts (fac_stream_push) on the previous push's, and through the LSTM's alternating
+    hidden-state buffers (fac_lstm_layer_fwd: they swap on every step) on the parity of the frames decoded so far -- after one
+    eager push with that key, and replayed from the third such push on, the host-side counters advanced by the delta the
+    captured push made (as in StreamingCodec.push, whose 5-hop period is 8 frames: even).  The hop is one chain on the caller's stream (no side-stream fork inside the graph).  With graphs the
+    returned wave is a static buffer, valid until the next call.
+    """
+
+    def __init__(self, model, timbre, use_graphs=True, max_frames=16):
+        q, dec = model.quantizer, model.decoder
+        self.device = timbre.device
+        self.B = timbre.shape[0]
+        self.max_frames = int(max_frames)
+        self._counters = []
+        for m in list(q.modules()) + list(dec.modules()):
+            if isinstance(m, ConvWeights):
+                m.freeze_packed = True               # inference: materialise w = g v/||v|| once
+        self.q = q
+        if tuple(timbre.shape) != (self.B, q.in_dim) or timbre.dtype != torch.float32:
+            raise ValueError(f"timbre must be float32 (B, {q.in_dim}), got {tuple(timbre.shape)} {timbre.dtype}")
+        with torch.no_grad():
+            self.style = q.timbre_linear(timbre.contiguous()).contiguous()         # (B, 2D) = [gamma | beta], fixed
+            self._weights = q.decode_weights()
+        self.dec = _DecoderStream(self, dec, self.B, self.max_frames)
+        self.min_prime = self._min_prime()
+        self.use_graphs = use_graphs
+        self.frames = 0
+        self._n_q = None
+        self._codes = None
+        self._last_k = 0
+        self._graphs = {}
+        self._warm = set()
+
+    def _min_prime(self):
+        """Fewest frames the first chunk may have: every causal conv of the decoder reflect-pads the start of the signal by
+        pad = (k - 1) d + 1 - s columns (_Tap), which needs more than `pad` input columns; a tap running at `rate` columns per
+        frame therefore needs floor(pad / rate) + 1 frames (k7 with dilation 9 at 6 columns per frame: 10 frames)."""
+        taps = [self.dec.tap0, self.dec.tap_out] + [u.tap for units in self.dec.units for u in units]
+        need = 1
+        for tap in taps:
+            assert tap.s == 1                             # the decoder's causal convs are unstrided (upsampling: ConvTranspose)
+            rate = (tap.buf.shape[-1] - tap.hist) // self.max_frames
+            need = max(need, tap.pad // rate + 1)
+        return need
+
+    def _check(self, codes):
+        if not isinstance(codes, (list, tuple)) or len(codes) != 3:
+            raise ValueError("codes must be [codes_p, codes_c, codes_r], each (B, n, k) int64")
+        k = codes[0].shape[-1]
+        for c in codes:
+            if not isinstance(c, torch.Tensor) or c.dtype != torch.int64 or c.dim() != 3 or c.shape[0] != self.B or c.shape[-1] != k:
+                raise ValueError(f"codes must be three int64 (B={self.B}, n, k) tensors with the same k")
+        if k < 1 or k > self.max_frames:
+            raise ValueError(f"a chunk of {k} frames (1 .. max_frames = {self.max_frames})")
+        if self._n_q is not None and [c.shape[1] for c in codes] != self._n_q:
+            raise ValueError(f"code row counts {[c.shape[1] for c in codes]} differ from the session's {self._n_q}")
+        return k
+
+    def _step(self, k):
+        codes = [self._codes[r][:, :, :k] if self._n_q[r] else None for r in range(3)]
+        outs = ops.vq_decode(codes, self._wsel, self.style, self.q.prosody_quantizer.codebook_size)
+        return self.dec.run(outs)
+
+    def _load(self, codes, k):
+        for r in range(3):
+            if self._n_q[r]:
+                self._codes[r][:, :, :k].copy_(codes[r])
+
+    def prime(self, codes):
+        if self._n_q is not None:
+            raise RuntimeError("prime() must be the first call")
+        k = self._check(codes)
+        if k < self.min_prime:
+            raise ValueError(f"prime() needs at least {self.min_prime} frames (the decoder's reflect-padded first taps), got {k}")
+        rvqs = (self.q.prosody_quantizer, self.q.content_quantizer, self.q.residual_quantizer)
+        for c, rvq in zip(codes, rvqs):
+            if c.shape[1] > rvq.n_codebooks:
+                raise ValueError(f"{c.shape[1]} code rows for an RVQ of {rvq.n_codebooks} quantizers")
+        check_codes(codes, self.q.prosody_quantizer.codebook_size)
+        self._n_q = [c.shape[1] for c in codes]
+        self._wsel = [w[:n] for w, n in zip(self._weights, self._n_q)]
+        self._codes = [torch.zeros(self.B, max(n, 1), self.max_frames, dtype=torch.int64, device=self.device) for n in self._n_q]
+        self._load(codes, k)
+        with torch.no_grad():
+            wave = self._step(k)
+        self.frames, self._last_k = k, k
+        return wave
+
+    def _state(self):
+        return [list(o.c) for o in self._counters]
+
+    def push(self, codes):
+        if self._n_q is None:
+            raise RuntimeError("call prime() first")
+        k = self._check(codes)
+        key = (self._last_k, k, self.dec.lstm.c[0] & 1 if self.dec.lstm is not None else 0)
+        self._last_k = k
+        self.frames += k
+        self._load(codes, k)
+        with torch.no_grad():
+            if not self.use_graphs or key not in self._warm:
+                self._warm.add(key)                       # first push with this key: eager (also warms every kernel up)
+                return self._step(k)
+            if key not in self._graphs:                   # second: capture (capture does not execute: replay once)
+                before = self._state()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    wave = self._step(k)
+                g.replay()
+                delta = [[a - b for a, b in zip(sa, sb)] for sa, sb in zip(self._state(), before)]
+                self._graphs[key] = (g, wave, delta)
+                return wave
+            g, wave, delta = self._graphs[key]
+            g.replay()
+            for o, d in zip(self._counters, delta):
+                o.c[:] = [ci + di for ci, di in zip(o.c, d)]
+            return wave

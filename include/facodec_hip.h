@@ -550,6 +550,32 @@ int fac_vq_fwd(const fac_vq_desc* d, fac_stream_t stream);
 /* Number of time tiles fac_vq_fwd cuts T frames into (= the row length of loss_part; 16 frames per workgroup). */
 int fac_vq_loss_tiles(int T);
 
+/* Codes -> decoder input (dac/nn/quantize.py:72-76 decode_code + :200-220 ResidualVectorQuantize.from_codes for the
+ * prosody, content and residual RVQs, then the tail of FAquantizer.forward_v2, modules/quantize.py:436-449, eval):
+ *   z_q_i = W_out_i cb_i[code_i] + b_out_i  (W_out = weight_v * scale, 1x1 conv 8 -> D);  z_r = 0 + z_q_0 + z_q_1 + ... per RVQ;
+ *   outs = LayerNorm_C((z[0] + z[1]) + z[2]) (eps 1e-5, no affine) * gamma + beta,  style (B, 2D) = [gamma | beta].
+ * Per value the same roundings as fac_vq_fwd's out-projection, fac_add and fac_layernorm_c_affine.  Any number of
+ * quantizers per RVQ (0 included: that RVQ's sum is 0), at most FAC_VQ_DECODE_MAX_Q in all.  Codes are NOT range
+ * checked: an index outside [0, Kc) is clamped for the load (memory safety only; validate on the host). */
+#define FAC_VQ_DECODE_MAX_Q 16
+typedef struct fac_vq_decode_desc {
+  const int64_t* codes[3];  /* RVQ r (0 prosody, 1 content, 2 residual): code of its quantizer i for clip b, frame t at
+                               codes[r][b*codes_bs[r] + i*codes_qs[r] + t]; may be NULL when n_q[r] == 0 */
+  int64_t codes_bs[3];
+  int64_t codes_qs[3];
+  int32_t n_q[3];           /* quantizers of each RVQ */
+  const float* codebook[FAC_VQ_DECODE_MAX_Q];    /* (Kc, 8) raw rows; quantizers of RVQ 0, then RVQ 1, then RVQ 2 */
+  const float* w_out[FAC_VQ_DECODE_MAX_Q];       /* (D, 8) out_proj weight_v ([c][d], torch layout (D,8,1)) */
+  const float* w_out_scale[FAC_VQ_DECODE_MAX_Q]; /* (D) weight-norm scale from fac_wn_scale, or NULL (== 1) */
+  const float* b_out[FAC_VQ_DECODE_MAX_Q];       /* (D) */
+  const float* style;       /* (B, 2D) = [gamma | beta] */
+  float* outs;              /* (B, D, T) decoder input */
+  float* z[3];              /* (B, D, T) per-RVQ sums z_p / z_c / z_r, each NULL to skip */
+  int32_t B, D, T, Kc;
+} fac_vq_decode_desc;
+
+int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream);
+
 /* Nearest-code search only, on already-projected latents (N, 8) row-major -> idx (N) int64.
  * The isolated kernel of dac/nn/quantize.py:78-94 / quantize/fvq.py:101-116. */
 int fac_vq_search(const float* latents, const float* codebook, int64_t* idx, int64_t N, int Kc,
