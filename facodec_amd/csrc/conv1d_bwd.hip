@@ -505,8 +505,10 @@ extern "C" int fac_pad_fold_edges(float* dxpad, int B, int C, int T, int Tp, int
   FAC_REQUIRE(dxpad && B > 0 && C > 0 && T > 0 && pad_left >= 0 && Tp >= pad_left + T, "pad_fold_edges: bad arguments");
   const int pad_right = Tp - pad_left - T;
   // a sample must not be both a mirror target of the left edge and of the right edge, and the mirrored ranges must lie inside
-  // the signal: T > pad_left + pad_right keeps the two edge regions disjoint (each thread then owns its target)
-  FAC_REQUIRE(T > pad_left + pad_right, "pad_fold_edges: signal shorter than its padding (use fac_pad_fold_bwd)");
+  // the signal: the left edge adds onto x[1 .. pad_left], the right edge onto x[T - 1 - pad_right .. T - 2], so T > pad_left +
+  // pad_right + 1 keeps the two target ranges disjoint (each thread then owns its target; at T = pad_left + pad_right + 1 both
+  // edges would add onto x[pad_left] without atomics)
+  FAC_REQUIRE(T > pad_left + pad_right + 1, "pad_fold_edges: signal too short for its padding (use fac_pad_fold_bwd)");
   if (pad_left + pad_right == 0) return FAC_OK;
   const long long n = (long long)B * C * (pad_left + pad_right);
   const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);

@@ -258,6 +258,10 @@ static int wk1_taps_geometry(int B, int C_in, int Tx, int C_out, int T_out, int 
   return (int)S;
 }
 
+// The kernel reads dy (and, for k = 1, x) with 16-byte loads: rows start 16-byte aligned only if the tensor's base does (T % 4 == 0
+// is part of the geometry).  A contiguous view with a storage offset can break that.
+static inline bool wk1_aligned16(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15) == 0; }
+
 }  // namespace fac
 
 // Row length the padded input of fac_conv1d_bwd_weight_taps must have (zeros behind the last position a valid output reads).
@@ -278,6 +282,12 @@ extern "C" int64_t fac_conv1d_bwd_weight_taps_ws_bytes(int B, int C_in, int C_ou
   return S > 0 ? (int64_t)S * a.wpr * ((int64_t)C_out * C_in * K + C_out) * 4 : -1;
 }
 
+extern "C" int64_t fac_conv1d_bwd_weight_taps_ws_bytes_for(const float* dy, int B, int C_in, int C_out, int T_out, int K, int K1,
+                                                           int dilation, int dilation2) {
+  if (!fac::wk1_aligned16(dy)) return -1;
+  return fac_conv1d_bwd_weight_taps_ws_bytes(B, C_in, C_out, T_out, K, K1, dilation, dilation2);
+}
+
 // xpad (B, C_in, Tx): the conv's PADDED input (position p of the output's receptive field origin at p = t), Tx >= fac_..._taps_tx.
 // dW (C_out, C_in, K)[co][ci][k] = sum over (b, t < T_out) of dy[b][co][t] * xpad[b][ci][t + (k / K1) * dilation2 + (k % K1) * dilation].
 extern "C" int fac_conv1d_bwd_weight_taps(const float* xpad, const float* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int B,
@@ -288,6 +298,7 @@ extern "C" int fac_conv1d_bwd_weight_taps(const float* xpad, const float* dy, fl
   int RB, CB;
   const int S = wk1_taps_geometry(B, C_in, Tx, C_out, T_out, K, K1, dilation, dilation2, &a, &RB, &CB);
   FAC_REQUIRE(xpad && dy && dw && ws && S > 0, "conv1d_bwd_weight_taps: shape not supported (query fac_conv1d_bwd_weight_taps_ws_bytes / _tx)");
+  FAC_REQUIRE(wk1_aligned16(dy), "conv1d_bwd_weight_taps: dy must be 16-byte aligned (query fac_conv1d_bwd_weight_taps_ws_bytes_for)");
   const int64_t n_dw = (int64_t)C_out * C_in * K;
   FAC_REQUIRE(ws_bytes >= (int64_t)S * a.wpr * (n_dw + C_out) * 4, "conv1d_bwd_weight_taps: workspace too small");
   a.x = xpad; a.dy = dy; a.part = reinterpret_cast<float*>(ws); a.with_db = db != nullptr ? 1 : 0;
@@ -310,6 +321,11 @@ extern "C" int64_t fac_conv1d_bwd_weight_k1_ws_bytes(int B, int C_in, int C_out,
   return S > 0 ? (int64_t)S * a.wpr * ((int64_t)C_out * C_in + C_out) * 4 : -1;
 }
 
+extern "C" int64_t fac_conv1d_bwd_weight_k1_ws_bytes_for(const float* x, const float* dy, int B, int C_in, int C_out, int T) {
+  if (!fac::wk1_aligned16(x) || !fac::wk1_aligned16(dy)) return -1;
+  return fac_conv1d_bwd_weight_k1_ws_bytes(B, C_in, C_out, T);
+}
+
 extern "C" int fac_conv1d_bwd_weight_k1(const float* x, const float* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int B,
                                         int C_in, int C_out, int T, fac_stream_t stream) {
   using namespace fac;
@@ -317,6 +333,7 @@ extern "C" int fac_conv1d_bwd_weight_k1(const float* x, const float* dy, float* 
   int Q;
   const int S = wk1_geometry(B, C_in, C_out, T, &a, &Q);
   FAC_REQUIRE(x && dy && dw && ws && S > 0, "conv1d_bwd_weight_k1: shape not supported (query fac_conv1d_bwd_weight_k1_ws_bytes)");
+  FAC_REQUIRE(wk1_aligned16(x) && wk1_aligned16(dy), "conv1d_bwd_weight_k1: x and dy must be 16-byte aligned (query fac_conv1d_bwd_weight_k1_ws_bytes_for)");
   FAC_REQUIRE(ws_bytes >= (int64_t)S * a.wpr * ((int64_t)C_out * C_in + C_out) * 4, "conv1d_bwd_weight_k1: workspace too small");
   a.x = x; a.dy = dy; a.part = reinterpret_cast<float*>(ws); a.with_db = db != nullptr ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;

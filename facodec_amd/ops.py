@@ -1274,7 +1274,7 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
         assert dxpad.shape[-1] == tp, (dxpad.shape, tp)
     if tp == t_in and FOLD_IN_PLACE in (1, 2):
         return dxpad                                  # no padding (the 1x1 convs): the padded gradient IS the gradient
-    if allow_view and FOLD_IN_PLACE in (1, 3) and dxpad.is_contiguous() and (pad_mode == PAD_ZERO or t_in > pad_left + pad_right):
+    if allow_view and FOLD_IN_PLACE in (1, 3) and dxpad.is_contiguous() and (pad_mode == PAD_ZERO or t_in > pad_left + pad_right + 1):
         if pad_mode == PAD_REFLECT:
             _lib.check(_lib.load().fac_pad_fold_edges(_ptr(dxpad), B, c_in, t_in, tp, pad_left, _stream()), "fac_pad_fold_edges")
         return dxpad[:, :, pad_left:pad_left + t_in]
@@ -1365,7 +1365,7 @@ def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, 
     if WGRAD_K1_STREAM and BF16_SPLIT and k == 1 and stride == 1 and pad_left == 0 and t_in == t_out and k1 in (0, 1):
         # few channels, long signal (the ResidualUnit tails at C = 64 / 96 / 192): both tensors once through the fp32 matrix pipe
         # instead of two operand-split passes + plane reads (conv1d_wgrad_k1.hip); the bias gradient rides on the dy fragments
-        nb = lib.fac_conv1d_bwd_weight_k1_ws_bytes(B, c_in, c_out, t_in)
+        nb = lib.fac_conv1d_bwd_weight_k1_ws_bytes_for(_ptr(x), _ptr(dy), B, c_in, c_out, t_in)     # -1 also for misaligned x / dy
         if nb > 0:
             ws = _wgrad_workspace(x.device, nb)
             _lib.check(lib.fac_conv1d_bwd_weight_k1(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nb, B, c_in, c_out, t_in, _stream()),
@@ -1376,7 +1376,7 @@ def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, 
         # are shifted views of one or two input rows -- the same kernel with virtual rows (fac_conv1d_bwd_weight_taps) on the padded input
         kk1 = k1 if 0 < k1 < k else k
         d2 = dilation2 if 0 < k1 < k else 0
-        nb = lib.fac_conv1d_bwd_weight_taps_ws_bytes(B, c_in, c_out, t_out, k, kk1, dilation, d2)
+        nb = lib.fac_conv1d_bwd_weight_taps_ws_bytes_for(_ptr(dy), B, c_in, c_out, t_out, k, kk1, dilation, d2)
         if nb > 0:
             tx = lib.fac_conv1d_bwd_weight_taps_tx(t_out, k, kk1, dilation, d2)
             need = (t_out - 1) + (k // kk1 - 1) * d2 + (kk1 - 1) * dilation + 1          # positions of the padded input the outputs read

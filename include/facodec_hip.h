@@ -455,7 +455,7 @@ int fac_pad_fold_bwd(const float* dxpad, float* dx, int B, int C, int T, int Tp,
                      fac_stream_t stream);
 /* fac_pad_fold_bwd in place for reflect padding, edges only: adds every mirrored padded position of dxpad (B, C, Tp) onto the sample
  * it mirrors (dac/model/encodec.py:96-113 backward); afterwards dx[b][c][j] IS dxpad[b][c][pad_left + j].  Needs T > pad_left +
- * pad_right.  Zero padding needs no call at all (the window is the gradient). */
+ * pad_right + 1 (the two edges' target samples disjoint).  Zero padding needs no call at all (the window is the gradient). */
 int fac_pad_fold_edges(float* dxpad, int B, int C, int T, int Tp, int pad_left, fac_stream_t stream);
 /* dW (C_out, C_in, K) = sum over (b, t) of dy[b][co][t] * xpad[b][ci][t*stride + k*dilation]; ws: scratch of
  * fac_conv1d_bwd_weight_ws_bytes(...) bytes (partial sums per (b, t) range, added in a fixed order). */
@@ -469,6 +469,9 @@ int fac_conv1d_bwd_weight(const float* x, const float* dy, float* dw, void* ws, 
  * workgroups, added in a fixed order) or -1 when the shape does not run here (channel counts: multiples of 32 in [64, 192];
  * T >= 4096, T % 4 == 0). */
 int64_t fac_conv1d_bwd_weight_k1_ws_bytes(int B, int C_in, int C_out, int T);
+/* The same query for the tensors at hand: also -1 when x or dy is not 16-byte aligned (the kernel reads both with 16-byte loads;
+ * fac_conv1d_bwd_weight_k1 refuses such pointers). */
+int64_t fac_conv1d_bwd_weight_k1_ws_bytes_for(const float* x, const float* dy, int B, int C_in, int C_out, int T);
 int fac_conv1d_bwd_weight_k1(const float* x, const float* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int B, int C_in, int C_out,
                              int T, fac_stream_t stream);   /* db: (C_out) bias gradient sum over (b, t) of dy, or NULL */
 /* The same kernel for stride-1 convs with few input channels and taps (first layers: the encoder's 1 -> 64 k = 7 conv,
@@ -479,6 +482,9 @@ int fac_conv1d_bwd_weight_k1(const float* x, const float* dy, float* dw, float* 
  * (K1 = K: plain taps).  C_out = 32 or 64, C_in * K <= 64, T_out >= 4096; the query returns -1 otherwise.  db as above. */
 int64_t fac_conv1d_bwd_weight_taps_tx(int T_out, int K, int K1, int dilation, int dilation2);
 int64_t fac_conv1d_bwd_weight_taps_ws_bytes(int B, int C_in, int C_out, int T_out, int K, int K1, int dilation, int dilation2);
+/* ... and for the dy at hand: also -1 when dy is not 16-byte aligned (xpad may sit anywhere: its taps are 4-byte aligned loads). */
+int64_t fac_conv1d_bwd_weight_taps_ws_bytes_for(const float* dy, int B, int C_in, int C_out, int T_out, int K, int K1, int dilation,
+                                                int dilation2);
 int fac_conv1d_bwd_weight_taps(const float* xpad, const float* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int B, int C_in, int Tx,
                                int C_out, int T_out, int K, int K1, int dilation, int dilation2, fac_stream_t stream);
 /* The same gradient on the bf16 matrix pipe with fp32-grade operand splitting (conv1d_wgrad_split.hip; same arguments

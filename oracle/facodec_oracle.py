@@ -316,10 +316,11 @@ def residual_vq_forward(x, sd, p, num_quantizers, training=False, n_quantizers=N
 # ---------------------------------------------------------------------------------------------
 
 
-def hann_periodic(n):
-    """torch.hann_window(n, periodic=True) == scipy.signal.get_window('hann', n) (fftbins=True)."""
+def hann_periodic(n, dtype=torch.float32):
+    """torch.hann_window(n, periodic=True) == scipy.signal.get_window('hann', n) (fftbins=True); built in float64, returned
+    in `dtype` (float32 by default; float64 for the fp64 restatement of the discriminator)."""
     k = torch.arange(n, dtype=torch.float64)
-    return (0.5 - 0.5 * torch.cos(2.0 * math.pi * k / n)).to(torch.float32)
+    return (0.5 - 0.5 * torch.cos(2.0 * math.pi * k / n)).to(dtype)
 
 
 def mel_filterbank_htk(n_freqs, n_mels, sample_rate, f_min=0.0, f_max=None):
@@ -747,7 +748,7 @@ def stft_match_stride(wave2d, window_length):
     right_pad = math.ceil(T / hop) * hop - T
     pad = (window_length - hop) // 2
     x = F.pad(wave2d.unsqueeze(1), (pad, pad + right_pad), mode="reflect").squeeze(1)
-    win = torch.as_tensor(hann_periodic(window_length), dtype=torch.float32)
+    win = hann_periodic(window_length, wave2d.dtype)             # the input's precision (float32 calls: unchanged)
     s = torch.stft(x, n_fft=window_length, hop_length=hop, window=win, center=True, pad_mode="reflect", return_complex=True)
     return s[..., 2:-2]
 

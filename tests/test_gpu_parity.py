@@ -1958,6 +1958,139 @@ def test_discriminator_forward_backward(O, cuda, golden_dir):
     assert worst[1] < 2e-3, worst
 
 
+def _disc_fp64_grads(O, sd, x, xr, kinks=None, l1_signs=None):
+    """Gradients of loss_d + 0.5 loss_g + 0.25 loss_feature (as above) through the oracle in float64, from the same fp32 values.
+    kinks: None, or one boolean mask per LeakyReLU call of the two forwards (fake clip, then real clip; call order = feature-map
+    order): the slope-1 side is taken where the mask is set, whatever the sign of the fp64 pre-activation -- float64 arithmetic on
+    the kink pattern of another evaluation.  l1_signs: None, or sign(fake - real) per feature-matching map (the L1 loss's kink):
+    the feature loss is then taken as mean(sign * (fake - real)), whose gradient is that of the L1 loss on those signs.  Returns (waveform gradient, {parameter: gradient}, (fake maps, real maps) detached,
+    {first MPD conv: conditioning max over its weights of sum|x dy| / |sum x dy|})."""
+    import torch.nn.functional as F
+    leaves = {k: v.double().clone().requires_grad_() for k, v in sd.items()}
+    xf = x.double().clone().requires_grad_()
+    first = []
+    conv2d, leaky = F.conv2d, F.leaky_relu
+    masks = iter(kinks) if kinks is not None else None
+
+    def conv_spy(inp, w, *a, **kw):
+        out = conv2d(inp, w, *a, **kw)
+        if w.shape[1] == 1 and w.shape[2:] == (5, 1) and out.requires_grad:
+            out.retain_grad()
+            first.append((inp, out, a, kw))
+        return out
+
+    def leaky_kinked(inp, slope, *a, **kw):
+        m = next(masks)
+        assert m.shape == inp.shape, (m.shape, inp.shape)
+        return torch.where(m, inp, inp * slope)
+
+    O.F.conv2d = conv_spy
+    if masks is not None:
+        O.F.leaky_relu = leaky_kinked
+    try:
+        df, dr = O.discriminator_forward(leaves, xf), O.discriminator_forward(leaves, xr.double())
+    finally:
+        O.F.conv2d, O.F.leaky_relu = conv2d, leaky
+    if masks is not None:
+        assert next(masks, None) is None
+    ld, lg, lf = O.gan_losses(df, dr)
+    if l1_signs is not None:
+        sg = iter(l1_signs)
+        lf = sum((next(sg) * (a[j] - b[j].detach())).mean() for a, b in zip(df, dr) for j in range(len(a) - 1))
+    (ld + 0.5 * lg + 0.25 * lf).backward()
+    cond = {}
+    for i, (inp, out, a, kw) in enumerate(first[:len(first) // 2]):      # the fake clip's five first convs (the real ones follow)
+        stride = kw.get("stride", 1)
+        padding = kw.get("padding", 0)
+        num = torch.nn.grad.conv2d_weight(inp.detach().abs(), (out.shape[1], 1, 5, 1), out.grad.abs(), stride=stride, padding=padding)
+        den = torch.nn.grad.conv2d_weight(inp.detach(), (out.shape[1], 1, 5, 1), out.grad, stride=stride, padding=padding)
+        cond[f"discriminators.{i}.convs.0.0"] = float((num / den.abs().clamp_min(1e-300)).max())
+    maps = tuple([[m.detach() for m in d] for d in dd] for dd in (df, dr))
+    return xf.grad, {k: v.grad for k, v in leaves.items()}, maps, cond
+
+
+def _starts(maps):
+    """Index of each discriminator's first activated map in _activated(maps)."""
+    out, n = [], 0
+    for d in maps:
+        out.append(n)
+        n += len(d) - 1
+    return out
+
+
+def _activated(maps):
+    """The LeakyReLU outputs among a discriminator output structure: every map but each discriminator's last (its logits)."""
+    return [m for d in maps for m in d[:-1]]
+
+
+# Bars on the max-relative error of every discriminator parameter gradient (worst tensor) and of the waveform gradient, against
+# float64 autograd (a) on the HIP forward's own kinks and (b) plainly.  Measured on MI355X (2 clips each):
+#   (a) worst tensor 7.0e-7 (T = 24000), 6.4e-7 (2310), 3.5e-6 (1500); waveform 1.0e-7, 3.2e-8, 1.3e-7.  This is the kernels' error.
+#   (b) worst tensor 5.6e-4 (T = 24000, discriminators.5.band_convs.2.0.0.weight_v), 2.0e-5 (2310), 1.2e-2 (1500,
+#       discriminators.6.band_convs.0.3.0.weight_v); waveform 2.1e-7, 3.3e-8, 2.5e-5.  The excess over (a) is kinks, not rounding:
+#       at T = 24000 the HIP forward puts 13 LeakyReLU pre-activations (both clips) and 10 feature-matching differences
+#       (fake - real) on the other side of 0 from fp64; at T = 1500 a single feature-matching difference of the 1024-point MRD's
+#       lowest band does (its map has 6 frames per clip, so one element's sign(fake - real) carries a 1/n that large), and at
+#       T = 2310 one of the first period discriminator.  With the same kinks as the HIP forward, fp64 agrees to (a).
+DISC_KINKED_BARS = {24000: (5e-6, 1e-6), 2310: (5e-6, 3e-7), 1500: (2e-5, 1e-6)}
+DISC_FP64_BARS = {24000: (1e-3, 1e-6), 2310: (1e-4, 2e-7), 1500: (2e-2, 1e-4)}
+
+
+@pytest.mark.parametrize("T", [24000, 2310, 1500], ids=["T24000", "T2310_full_period_pads", "T1500_shorter_than_mrd_window"])
+def test_discriminator_gradients_against_fp64(O, cuda, T):
+    """Every discriminator parameter gradient and the waveform gradient of the HIP path against float64 autograd through the
+    oracle, from the same fp32-rounded clips and weights.  T = 2310: every period divides T (MPD pads a full period); T = 1500:
+    shorter than the 2048-point MRD window, long enough for its reflect pads.
+
+    LeakyReLU is not differentiable at 0: where a pre-activation lies within rounding of 0, fp32 and fp64 can take different sides,
+    and the gradient through that element moves by 0.9 |dy| -- not a rounding error.  So the HIP forward's pre-activation signs
+    (the sign of each activated map: LeakyReLU keeps it) are compared with fp64's for BOTH clips, and the gradients are compared
+    twice: against fp64 evaluated on the HIP forward's kink pattern, which isolates the kernels' own error, and against plain
+    fp64.  The same holds for the feature-matching L1 (|fake - real| at fake ~ real), whose signs are matched too."""
+    from facodec_amd import discriminator as D
+    disc = D.Discriminator(sample_rate=24000)
+    sd = synth.load_synthetic(disc, seed=0, prefix="discriminator.")
+    x = synth.synth_clips(2, T, seed=5)
+    xr = synth.synth_clips(2, T, seed=6)
+    disc.to(cuda)
+    xf = x.to(cuda).requires_grad_()
+    d_fake, d_real = disc(xf), disc(xr.to(cuda))
+    loss_d, loss_g, loss_f = D.gan_losses(d_fake, d_real)
+    (loss_d + 0.5 * loss_g + 0.25 * loss_f).backward()
+    torch.cuda.synchronize()
+    hip_maps = [m.detach().cpu() for m in _activated(d_fake) + _activated(d_real)]
+    gx, gp, maps64, cond = _disc_fp64_grads(O, sd, x, xr)
+    ref_maps = _activated(maps64[0]) + _activated(maps64[1])
+    names = [f"{c}.d{i}.m{j}" for c, mm in (("fake", maps64[0]), ("real", maps64[1])) for i, d in enumerate(mm) for j in range(len(d) - 1)]
+    flips = {n: int(((h > 0) != (r > 0)).sum()) for n, h, r in zip(names, hip_maps, ref_maps)}
+    flips = {n: c for n, c in flips.items() if c}
+    fwd_err = max(rel(h, r) for h, r in zip(hip_maps, ref_maps))
+    errs = {n: rel(p.grad, gp[n]) for n, p in disc.named_parameters()}
+    worst = max(errs.items(), key=lambda kv: kv[1])
+    ex = rel(xf.grad, gx)
+    # the feature-matching loss is an L1 of (fake - real): a second kind of kink, where the two clips' maps nearly agree
+    hf, hr = [[m.detach().cpu().double() for m in d[:-1]] for d in d_fake], [[m.detach().cpu().double() for m in d[:-1]] for d in d_real]
+    hip_l1 = [torch.sign(a - b) for da, db in zip(hf, hr) for a, b in zip(da, db)]
+    ref_l1 = [torch.sign(a - b) for da, db in zip(maps64[0], maps64[1]) for a, b in zip(da[:-1], db[:-1])]
+    l1_flips = {f"d{i}": int(sum(int((a != b).sum()) for a, b in zip(hip_l1[n0:n0 + len(d) - 1], ref_l1[n0:n0 + len(d) - 1])))
+                for i, (d, n0) in enumerate(zip(maps64[0], _starts(maps64[0])))}
+    l1_flips = {k: v for k, v in l1_flips.items() if v}
+    gxk, gpk, _, _ = _disc_fp64_grads(O, sd, x, xr, kinks=[h > 0 for h in hip_maps], l1_signs=hip_l1)
+    errs_k = {n: rel(p.grad, gpk[n]) for n, p in disc.named_parameters()}
+    worst_k = max(errs_k.items(), key=lambda kv: kv[1])
+    ex_k = rel(xf.grad, gxk)
+    rep = dict(worst_parameter=list(worst), waveform=ex, hip_kink_flips_vs_fp64=flips, hip_l1_sign_flips_vs_fp64=l1_flips,
+               worst_feature_map=fwd_err,
+               kinked_worst_parameter=list(worst_k), kinked_waveform=ex_k, first_conv_conditioning=cond,
+               top5=sorted(errs.items(), key=lambda kv: -kv[1])[:5])
+    _record(f"discriminator_fp64_T{T}", rep)
+    print(f"[disc fp64 T={T}] {rep}")
+    bar_p, bar_x = DISC_FP64_BARS[T]
+    bar_pk, bar_xk = DISC_KINKED_BARS[T]
+    assert ex_k < bar_xk and worst_k[1] < bar_pk, (ex_k, worst_k)
+    assert ex < bar_x and worst[1] < bar_p, (ex, worst)
+
+
 def test_full_train_step_runs(cuda):
     """train.py:265-374 minus the predictor losses: discriminator step + generator step on a small batch; finite losses,
     every model key's parameters move."""

@@ -20,7 +20,9 @@ LOSS_TOL = 1e-5          # north_star asks for 1e-4 relative; measured <= 2.2e-7
 # profiles/r03_gradient_conditioning_cpu.json.  A 1e-3 error in one discriminator weight gradient would pass these bars.  The
 # guard is the per-tensor NORM check next to it (`w[1] < 2e-4` below: relative error of every probed tensor's gradient norm,
 # measured <= 7.6e-6), plus the five whole-key gradient norms at 2e-4 and the per-op backward tests against torch autograd in
-# tests/test_gpu_parity.py (every trained tensor at <= 2e-4).
+# tests/test_gpu_parity.py.  For the discriminator that is test_discriminator_gradients_against_fp64: every parameter tensor against
+# float64 autograd through the oracle on the HIP forward's own LeakyReLU / L1 kinks at <= 2e-5 (measured <= 3.5e-6), three clip
+# lengths.  Plain fp64 differs by up to 1.2e-2 there, all of it from a few elements on the other side of a kink (see its comment).
 PROBE_BAR = dict(discriminator=3e-3, encoder=5e-4, quantizer=5e-4, decoder=5e-4, fa_predictors=5e-5)
 
 
