@@ -5,10 +5,10 @@ TAG=${1:-r06fin4}
 R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir -p $OUT
 O=$OUT/$TAG; mkdir -p $O
 cd $R
-python bench.py --no-cpu-baseline --no-streaming --record-train-loss > $O/record_line.json 2> $O/record.err
+python bench.py --full --no-cpu-baseline --no-streaming --record-train-loss > $O/record_line.json 2> $O/record.err
 cp tests/golden/bench_train_seeded.json $O/bench_train_seeded.json
 t0=$(date +%s)
-python bench.py --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
 echo "default bench wall seconds: $(( $(date +%s) - t0 ))" | tee $O/bench_wall.txt
 python - <<PY
 import json

@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/../.." && pwd); OUT=${FAC_TUNE_OUT:-$R/tune_out}; mkdir 
 O=$OUT/$TAG; mkdir -p $O
 cd $R
 t0=$(date +%s)
-python bench.py --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
 echo "default bench wall seconds: $(( $(date +%s) - t0 ))" | tee $O/bench_wall.txt
 python - <<PY
 import json
