@@ -142,6 +142,8 @@ SIGNATURES = {
     "fac_mish_bwd": (_i, [_p, _p, _p, _i64, _p]),
     "fac_glu_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_mul_scaled": (_i, [_p, _p, _p, _f, _i64, _p]),
+    "fac_embed_sum_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fac_gate_bwd_cond": (_i, [_p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "fac_masked_mean_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_attention_probs": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_attention_pv": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),

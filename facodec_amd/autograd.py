@@ -5,7 +5,8 @@ dac/model/dac.py + dac/model/encodec.py).
 Layer by layer (no cross-layer fusion yet: every Function keeps what its backward needs):
   conv        y = SConv1d(x)                  bwd: fac_conv1d_fwd on flipped weights + fac_pad_fold_bwd,
                                                    fac_conv1d_bwd_weight, fac_weight_norm_bwd, fac_bias_grad
-  conv_tr     y = SConvTranspose1d(x)         bwd: strided forward conv, weight-gradient kernel with swapped roles
+  conv_tr     y = SConvTranspose1d(x)         bwd: strided forward conv, weight-gradient kernel with swapped roles (non-causal:
+                                                   both read dy at the trim offset ceil(s/2))
   snake       y = x + sin^2(a x)/(a + 1e-9)   bwd: fac_snake_bwd
   tanh                                        bwd: fac_tanh_bwd
   lstm        SLSTM (dac/model/encodec.py:282-288): training forward stores gates / cell states; BPTT = per step one
@@ -100,10 +101,15 @@ class _Conv(Function):
 
 class _ConvTr(Function):
     @staticmethod
-    def forward(ctx, x, v, g, bias, stride):
+    def forward(ctx, x, v, g, bias, stride, causal):
         vd, gd = v.detach(), (g.detach() if g is not None else None)
-        ctx.stride = stride
+        ctx.stride, ctx.causal = stride, causal
         ctx.save_for_backward(x, v, g, bias)
+        if not causal:
+            # non-causal (the redecoder's decoder): the launch of SConvTranspose1d.run in eval mode -- polyphase layout, trim by the
+            # kernel's phase_shift -- so train and eval forwards agree
+            wt = ops.convtr_weight_for(vd, gd, stride, x.shape[-1], causal=False, batch=x.shape[0])
+            return ops.conv_transpose1d(x.detach(), wt, v.shape[1], stride, bias=bias.detach() if bias is not None else None, causal=False)
         if ops.flat_convtr_ok(v.shape[0], v.shape[1], stride, x.shape[0], x.shape[-1] + 1):
             # short clips: a zero column in front of every clip (the x[t - 1] of its first frame), one flattened signal; the s output
             # samples of that column are dropped
@@ -123,12 +129,12 @@ class _ConvTr(Function):
         x, v, g, bias = ctx.saved_tensors
         dy = dy.contiguous()
         vd, gd = v.detach(), (g.detach() if g is not None else None)
-        dx, dw = ops.conv_transpose1d_bwd(x.detach(), dy, vd, gd, ctx.stride)
+        dx, dw = ops.conv_transpose1d_bwd(x.detach(), dy, vd, gd, ctx.stride, causal=ctx.causal)
         if g is not None:
             dv, dg = ops.weight_norm_bwd(vd, gd, dw)
         else:
             dv, dg = dw, None
-        return dx, dv, dg, (ops.bias_grad(dy) if bias is not None else None), None
+        return dx, dv, dg, (ops.bias_grad(dy) if bias is not None else None), None, None
 
 
 class _Snake(Function):
@@ -345,10 +351,8 @@ def conv(m, x, act=ops.ACT_NONE):
 
 
 def conv_tr(m, x):
-    if not m.causal:
-        raise NotImplementedError("training path: non-causal SConvTranspose1d backward is not built yet")
     v, g = _wn(m.w)
-    return _ConvTr.apply(x, v, g, m.w.bias, m.stride)
+    return _ConvTr.apply(x, v, g, m.w.bias, m.stride, m.causal)
 
 
 def snake(m, x):

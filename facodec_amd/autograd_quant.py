@@ -33,6 +33,39 @@ class _Gate(Function):
         return da
 
 
+class _GateCond(Function):
+    """The gate with a per-clip conditioning row g (B, 2C) added before tanh / sigmoid (WN with gin_channels, modules/wavenet.py:
+    143-155).  One backward launch gives da and dg = sum over time of da (fac_gate_bwd_cond, fixed summation order)."""
+
+    @staticmethod
+    def forward(ctx, a, g):
+        ctx.save_for_backward(a, g)
+        return ops.gate_tanh_sigmoid(a.detach(), g.detach())
+
+    @staticmethod
+    def backward(ctx, d):
+        a, g = ctx.saved_tensors
+        B, c2, _ = a.shape
+        dg = torch.empty(B, c2, device=a.device, dtype=torch.float32)
+        da = ops.gate_bwd_cond(a.detach(), g.detach(), d.contiguous(), dg)
+        return da, dg
+
+
+class _CondSplit(Function):
+    """cond (B, n w) -> the n per-layer rows (B, w) as views (the gate kernel reads them with a row stride); backward joins the n
+    gradients into one (B, n w) tensor (data movement only), so the engine never sums zero-padded slice gradients."""
+
+    @staticmethod
+    def forward(ctx, cond, n):
+        w = cond.shape[1] // n
+        cd = cond.detach()
+        return tuple(cd[:, i * w:(i + 1) * w] for i in range(n))
+
+    @staticmethod
+    def backward(ctx, *d):
+        return torch.cat(d, dim=1), None
+
+
 class _Mish(Function):
     @staticmethod
     def forward(ctx, x):
@@ -179,11 +212,18 @@ def plain_conv(m, x, act=ops.ACT_NONE):
     return A._Conv.apply(x, m.weight, None, m.bias, (m.k, 1, 1, ops.PAD_ZERO, False, act))
 
 
-def wavenet(m, x, p_dropout=0.2, use_dropout=True):
-    """WN.forward in training mode, g = None, mask of ones."""
+def wavenet(m, x, p_dropout=0.2, use_dropout=True, g=None):
+    """WN.forward in training mode, mask of ones.  g: optional (B, gin) conditioning (the redecoder's timbre vector).  g itself
+    takes no gradient -- the timbre comes from the frozen codec -- but cond_layer does: its output rows get dcond from the
+    conditioned gate backward, and the 1x1 conv's own backward turns that into the weight-norm and bias gradients."""
     out = torch.zeros_like(x)
+    conds = None
+    if g is not None:
+        cond = A.conv(m.cond_layer, g.detach().reshape(g.shape[0], -1, 1))           # (B, 2 H L, 1)
+        conds = _CondSplit.apply(cond.reshape(g.shape[0], -1), m.n_layers)
     for i in range(m.n_layers):
-        acts = dropout(_Gate.apply(A.conv(m.in_layers[i], x)), p_dropout, use_dropout)
+        a = A.conv(m.in_layers[i], x)
+        acts = dropout(_Gate.apply(a) if conds is None else _GateCond.apply(a, conds[i]), p_dropout, use_dropout)
         rs = A.conv(m.res_skip_layers[i], acts)
         x, out = _ResSkip.apply(x, out, rs, i == m.n_layers - 1)
     return out

@@ -32,17 +32,22 @@ def recursive_munch(d):
     return d
 
 
-def build_model(args, stage="codec"):
+def build_model(args, stage="codec", with_discriminator=False):
     """modules/commons.py:283-348.  Returns Munch(encoder, quantizer, decoder, discriminator, fa_predictors)
-    with the reference's key order."""
+    with the reference's key order.  with_discriminator: stage 'redecoder' also builds its discriminator (:401-407), for
+    training (train_redecoder.RedecoderTrainStep); by default that stage returns exactly {encoder, decoder}."""
     from .dac_model import Encoder, Decoder
     from .quantize import FAquantizer
 
-    if stage == "redecoder":      # modules/commons.py:385-413 (discriminator: train-only, not built)
+    if stage == "redecoder":      # modules/commons.py:385-413 (discriminator: train-only, on request)
         from .redecoder import Redecoder
-        return Munch(encoder=Redecoder(args),
+        nets = Munch(encoder=Redecoder(args),
                      decoder=Decoder(input_channel=1024, channels=args.DAC.decoder_dim, rates=args.DAC.decoder_rates,
                                      causal=args.decoder_causal, lstm=args.decoder_lstm))
+        if with_discriminator:
+            from .train_redecoder import redecoder_discriminator
+            nets.discriminator = redecoder_discriminator(args.DAC.sr)
+        return nets
     if stage == "encoder":        # modules/commons.py:414-439
         return Munch(encoder=Encoder(d_model=args.DAC.encoder_dim, strides=args.DAC.encoder_rates, d_latent=1024,
                                      causal=args.encoder_causal, lstm=args.encoder_lstm),

@@ -1093,6 +1093,32 @@ def embed_sum(codes, tables, code_row0=0, out=None):
     return out
 
 
+def embed_sum_bwd(dx, codes, n_tab, V, code_row0=0):
+    """Adjoint of embed_sum (fac_embed_sum_bwd): dx (B, E, T), codes (B, N, T) int64 -> (n_tab, V, E), the gradient of table i
+    summed over the frames whose code row code_row0 + i selects each entry.  Deterministic (fixed order, no atomics)."""
+    dx = _dev(dx, "dx")
+    B, E, T = dx.shape
+    if codes.dtype != torch.int64 or not codes.is_cuda or codes.shape[0] != B or codes.shape[2] != T:
+        raise _lib.FacodecHipError(f"embed_sum_bwd: codes must be (B, N, T) int64 on the GPU, got {tuple(codes.shape)} {codes.dtype}")
+    codes = codes.contiguous()
+    out = torch.empty(n_tab, V, E, device=dx.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_embed_sum_bwd(_ptr(dx), _ptr(codes), _ptr(out), B, n_tab, codes.shape[1], code_row0, V, E, T, _stream()),
+               "fac_embed_sum_bwd")
+    return out
+
+
+def gate_bwd_cond(a, g, d, dcond):
+    """Backward of gate_tanh_sigmoid(a, g) with conditioning (fac_gate_bwd_cond): -> da (B, 2C, T); writes
+    dcond[b, :2C] = sum_t da[b, :, t] into `dcond` ((B, >= 2C) rows, may be a strided slice of a wider tensor)."""
+    a, d = _dev(a, "a"), _dev(d, "d")
+    B, c2, T = a.shape
+    assert g.stride(1) == 1 and dcond.stride(1) == 1 and dcond.shape == (B, c2), (g.stride(), dcond.shape)
+    da = torch.empty_like(a)
+    _lib.check(_lib.load().fac_gate_bwd_cond(_ptr(a), _ptr(g), g.stride(0), _ptr(d), _ptr(da), _ptr(dcond), dcond.stride(0), B, c2 // 2, T,
+                                             _stream()), "fac_gate_bwd_cond")
+    return da
+
+
 def glu_residual(a, res):
     a, res = _dev(a), _dev(res)
     B, c2, T = a.shape
@@ -1455,24 +1481,32 @@ def bias_grad(dy):
     return db
 
 
-def conv_transpose1d_bwd(x, dy, v, g, stride):
-    """Causal SConvTranspose1d (kernel 2*stride): -> (dx, dW (C_in, C_out, K)).  dx is the strided forward conv of dy
-    on the same weights; dW the weight-gradient kernel with the roles of input and output swapped."""
+def conv_transpose1d_bwd(x, dy, v, g, stride, causal=True):
+    """SConvTranspose1d (kernel 2*stride): -> (dx, dW (C_in, C_out, K)).  dx is the strided forward conv of dy
+    on the same weights; dW the weight-gradient kernel with the roles of input and output swapped.
+    The full transposed output has (T_in + 1) s columns; the causal layer keeps the first T_in s, the non-causal one drops
+    ceil(s/2) on the left and floor(s/2) on the right (dac/model/encodec.py:265-269, conv_transpose1d's phase_shift).  So dy sits
+    at offset `shift` = 0 or ceil(s/2) inside the full-length gradient, whose trimmed columns are zero: both launches read dy with
+    that zero-padded offset (pad_left = shift), no copy."""
     x, dy = _dev(x, "x"), _dev(dy, "dy")
     B, c_in, t_in = x.shape
     c_out, k = v.shape[1], v.shape[2]
     assert k == 2 * stride and dy.shape == (B, c_out, t_in * stride)
+    shift = 0 if causal else stride - stride // 2
     if pw_taps_ok(c_out, c_in, k, stride, False, B, t_in):         # stride 2, few channels: the streaming kernel with taps (fp32 pack)
-        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=0, pad_mode=PAD_ZERO, t_out=t_in)
+        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in)
     elif gemm_split_strided_ok(c_in, c_out, k, stride, B, t_in):   # the strided conv of dy on the split GEMM kernel
-        dx = conv1d(dy, None, c_in, k, stride=stride, pad_left=0, pad_mode=PAD_ZERO, t_out=t_in,
+        dx = conv1d(dy, None, c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in,
                     w_split=pack_gemm_weight_split(v, g, in_stride=stride))
-    elif flat_strided_ok(c_in, c_out, k, stride, B, t_in):         # short clips: zeros on the right of every clip, one flattened signal
-        dx = conv1d_flat_strided(torch.nn.functional.pad(dy, (0, stride)), pack_gemm_weight_split(v, g, in_stride=stride), c_in, k, stride)
+    elif flat_strided_ok(c_in, c_out, k, stride, B, t_in):
+        # short clips: every clip gets its s columns of zeros (shift in front, s - shift behind) and the clips run as one flattened
+        # signal -- the kernel cannot offset inside the concatenation, so this is the one path that pads with a copy (as causal)
+        dx = conv1d_flat_strided(torch.nn.functional.pad(dy, (shift, stride - shift)), pack_gemm_weight_split(v, g, in_stride=stride),
+                                 c_in, k, stride)
     else:
-        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=0, pad_mode=PAD_ZERO, t_out=t_in)
+        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in)
     dw = torch.empty(c_in, c_out, k, device=x.device, dtype=torch.float32)
-    _bwd_weight_launch(dy, x, dw, B, c_out, t_in * stride, c_in, t_in, k, stride, 1, 0, PAD_ZERO)
+    _bwd_weight_launch(dy, x, dw, B, c_out, t_in * stride, c_in, t_in, k, stride, 1, shift, PAD_ZERO)
     return dx, dw
 
 

@@ -4,6 +4,7 @@ timbre vector -> 1x1 conv back to the 1024-d latent that the (non-causal, LSTM-f
 The `mamba` branch of the reference imports a module that is not in its tree (modules.mamba): not built."""
 import torch
 from torch import nn
+from torch.autograd import Function
 
 from . import ops
 from .quantize import WN, _PlainConv
@@ -30,8 +31,12 @@ class Redecoder(nn.Module):
         self.prosody_embed = nn.ModuleList([_Embedding(self.codebook_size, self.embed_dim) for _ in range(self.n_p_codebooks)])
         self.content_embed = nn.ModuleList([_Embedding(self.codebook_size, self.embed_dim) for _ in range(self.n_c_codebooks)])
 
-    def forward(self, p_code, c_code, timbre_vec, use_p_code=True, use_c_code=True, n_c=2):
-        """p_code (B, n_p, T), c_code (B, >= n_c, T) int64; timbre_vec (B, 1024) -> (B, 1024, T)."""
+    def forward(self, p_code, c_code, timbre_vec, use_p_code=True, use_c_code=True, n_c=2, dropout=True):
+        """p_code (B, n_p, T), c_code (B, >= n_c, T) int64; timbre_vec (B, 1024) -> (B, 1024, T).
+        In .train() mode the pass runs with autograd (_forward_train); dropout=False there turns the WaveNet's dropout off
+        (golden tests)."""
+        if self.training:
+            return self._forward_train(p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, dropout)
         B, _, T = p_code.shape
         x = torch.zeros(B, self.embed_dim, T, device=p_code.device, dtype=torch.float32)
         if use_p_code and self.n_p_codebooks:
@@ -42,3 +47,43 @@ class Redecoder(nn.Module):
             ops.embed_sum(c_code, tabs, 0, out=x)
         x = self.encoder(x, None, g=timbre_vec)
         return self.conv_out.run(x)
+
+    def _forward_train(self, p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, dropout):
+        """Training mode (train_redecoder.py:220-228): the embedding tables in use (prosody, the first n_c content tables), the
+        WaveNet (its cond_layer included, dropout p = 0.2 after every gate) and conv_out get gradients; the codes and the
+        timbre vector, outputs of the frozen codec, do not."""
+        from . import autograd_quant as AQ
+        p_tabs = [e.weight for e in self.prosody_embed] if use_p_code and self.n_p_codebooks else []
+        c_tabs = [e.weight for e in list(self.content_embed)[:n_c]] if use_c_code and n_c else []
+        x = _EmbedSum.apply(p_code, c_code, len(p_tabs), self.embed_dim, *p_tabs, *c_tabs)
+        x = AQ.wavenet(self.encoder, x, p_dropout=0.2, use_dropout=dropout, g=timbre_vec)
+        return AQ.plain_conv(self.conv_out, x)
+
+
+class _EmbedSum(Function):
+    """x (B, E, T) = sum of the prosody tables at p_code rows + the content tables at c_code rows (the launches of the eval
+    forward); backward: one deterministic fac_embed_sum_bwd launch per code tensor for the dense table gradients."""
+
+    @staticmethod
+    def forward(ctx, p_code, c_code, n_p, E, *tabs):
+        B, _, T = p_code.shape
+        ctx.n_p, ctx.V = n_p, tabs[0].shape[0] if tabs else 0
+        ctx.save_for_backward(p_code, c_code)
+        x = torch.zeros(B, E, T, device=p_code.device, dtype=torch.float32)
+        if n_p:
+            ops.embed_sum(p_code, torch.stack([t.detach() for t in tabs[:n_p]]), 0, out=x)
+        if len(tabs) > n_p:
+            ops.embed_sum(c_code, torch.stack([t.detach() for t in tabs[n_p:]]), 0, out=x)
+        ctx.n_c = len(tabs) - n_p
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        p_code, c_code = ctx.saved_tensors
+        dx = dx.contiguous()
+        grads = []
+        if ctx.n_p:
+            grads += list(ops.embed_sum_bwd(dx, p_code, ctx.n_p, ctx.V).unbind(0))
+        if ctx.n_c:
+            grads += list(ops.embed_sum_bwd(dx, c_code, ctx.n_c, ctx.V).unbind(0))
+        return (None, None, None, None, *grads)

@@ -360,6 +360,17 @@ int fac_mish_fwd(const float* x, float* y, int64_t n, fac_stream_t stream);
 int fac_mish_bwd(const float* x, const float* d, float* dx, int64_t n, fac_stream_t stream);
 int fac_glu_bwd(const float* a, const float* d, float* da, int B, int C, int T, fac_stream_t stream);
 int fac_mul_scaled(const float* a, const float* b, float* out, float scale, int64_t n, fac_stream_t stream);
+/* Training path of the voice-conversion Redecoder (train_redecoder.py:195-328).  Both kernels are deterministic: no floating-point
+ * atomics, every sum in one fixed order, so the same inputs give bit-identical outputs.
+ *   fac_embed_sum_bwd   adjoint of fac_embed_sum: dtables (n_tab, V, E) = for table i, the sum over (b, t) of dx[b, :, t] into row
+ *                       codes[b, code_row0 + i, t] (frames added in order b, then t; rows no frame uses are zero).  V <= 1024;
+ *                       codes outside [0, V) contribute nothing.  dx (B, E, T), codes (B, n_codes, T) int64.
+ *   fac_gate_bwd_cond   backward of fac_gate_tanh_sigmoid WITH conditioning g (row b at g + b*g_bs): da (B, 2C, T) from
+ *                       d (B, C, T), and dcond[b*dcond_bs + j] = sum over t of da[b, j, t] (j < 2C), summed in a fixed order. */
+int fac_embed_sum_bwd(const float* dx, const int64_t* codes, float* dtables, int B, int n_tab, int n_codes, int code_row0, int V,
+                      int E, int T, fac_stream_t stream);
+int fac_gate_bwd_cond(const float* a, const float* g, int64_t g_bs, const float* d, float* da, float* dcond, int64_t dcond_bs,
+                      int B, int C, int T, fac_stream_t stream);
 int fac_masked_mean_bwd(const float* dout, const float* mask, float* dx, int B, int C, int T, fac_stream_t stream);
 int fac_attention_probs(const float* q, const float* k, const float* mask, float* P, int B, int H, int dk, int T,
                         fac_stream_t stream);
