@@ -151,7 +151,7 @@ extern "C" int fac_aa_snakebeta_bwd(const float* x, const float* alpha_log, cons
                                     const float* dy, float* dx, float* dalpha, float* dbeta, float* scratch, int B, int C,
                                     int T, fac_stream_t stream) {
   using namespace fac;
-  FAC_REQUIRE(x && alpha_log && beta_log && filter12 && dy && dx && dalpha && dbeta && scratch && B > 0 && C > 0 && T > 1,
+  FAC_REQUIRE(x && alpha_log && beta_log && filter12 && dy && dx && dalpha && dbeta && scratch && B > 0 && C > 0 && T > 0,
               "aa_snakebeta_bwd: bad arguments");
   FAC_REQUIRE((long long)B * C <= 65535, "aa_snakebeta_bwd: B*C too large");
   const int n_tiles = 1;                    // one partial pair per (b, c) row

@@ -1736,9 +1736,10 @@ def test_flat_adamw_matches_torch(cuda):
     """Fused arena AdamW + clip + ExponentialLR against torch.optim.AdamW / clip_grad_norm_ / ExponentialLR on CPU."""
     from facodec_amd.optim import FlatAdamW
     g = _g(77)
-    shapes = [(64, 32, 7), (64, 1, 1), (64,), (1, 96, 1), (300, 17)]
+    shapes = [(64, 32, 7), (64, 1, 1), (64,), (1, 96, 1), (300, 17), (3 * 2048 + 5,)]     # the last: whole 2048-element chunks
     ref = [torch.randn(*s, generator=g).requires_grad_() for s in shapes]
     ours = [r.detach().clone().to(cuda).requires_grad_() for r in ref]
+    p0 = [r.detach().clone() for r in ref]
     opt_ref = torch.optim.AdamW(ref, lr=1e-3, betas=(0.9, 0.98), eps=1e-9, weight_decay=0.1)
     sch = torch.optim.lr_scheduler.ExponentialLR(opt_ref, gamma=0.99)
     opt = FlatAdamW(ours, lr=1e-3, gamma=0.99, max_norm=2.0)
@@ -1754,6 +1755,13 @@ def test_flat_adamw_matches_torch(cuda):
         assert abs(float(opt.grad_norm()) - float(nrm)) / float(nrm) < 1e-5
     for r, o in zip(ref, ours):
         assert rel(o, r) < 1e-5
+    # the accumulated UPDATE, relative to the largest update: four steps move a parameter by about 4e-3, so the bar on p above is
+    # 1e-2 of the movement.  Both sides round p (|p| < 8: half an ulp is at most 2^-22) once per step, so the two differ by at
+    # most 8 * 2^-22 = 1.9e-6 = 4.8e-4 of a 4e-3 movement, plus the same fp32 formula in another order (a few 1e-7 relative):
+    # bar 1e-3, a tenth of what a wrong bias correction at steps 1 .. 4 shows (> 1e-2).
+    for r, o, p in zip(ref, ours, p0):
+        du, du_ref = o.detach().cpu().double() - p.double(), r.detach().double() - p.double()
+        assert float((du - du_ref).abs().max() / du_ref.abs().max()) < 1e-3
 
 
 def test_gather_copy_folds_many_tensors_bit_exactly(cuda, monkeypatch):
