@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-# FAC_BUILD_TAG=<tag> builds a tuning variant (e.g. with FAC_EXTRA_FLAGS=-DFAC_ABL_...) next to the product library:
+# FAC_BUILD_TAG=<tag> builds a variant (with FAC_EXTRA_FLAGS) next to the product library:
 # libfacodec_hip_<tag>.so, objects under csrc/build_<tag>/; select it at run time with FAC_LIB_PATH.
 TAG = os.environ.get("FAC_BUILD_TAG", "")
 LIB = os.path.join(HERE, "libfacodec_hip%s.so" % ("_" + TAG if TAG else ""))

@@ -14,32 +14,29 @@ static int select_variant(const fac_conv_desc* d) {
   // k = 1 convs re-use nothing across taps: per staged byte they do 7x less MFMA work than k = 7 and are
   // LDS-DMA-bound on 128-wide time tiles; long sequences take 256-wide tiles with 8 MFMA waves
   // (measured +15..30 % on the k = 1 layers, neutral on k = 7).
-  static const bool k1_wide = !(getenv("FAC_K1_WIDE") && getenv("FAC_K1_WIDE")[0] == '0');
-  const bool wide = k1_wide && d->K == 1 && d->n_phase == 1 && d->T_out >= 512;   // (wide tiles measured slower for K = 2)
+  const bool wide = d->K == 1 && d->n_phase == 1 && d->T_out >= 512;   // (wide tiles measured slower for K = 2)
   // 2 s clips are 160 latent frames: a 160-wide tile wastes nothing where 128 + 32 would waste 37 %
   if (d->T_out > 128 && d->T_out <= 160 && co > 64) return 8;
   if (co % 128 != 0 && co % 96 == 0) return wide ? 6 : 3;
   return wide ? 5 : 4;
 }
 
-#if defined(FAC_PROF) || defined(FAC_PROF2)
-unsigned long long* g_conv_dbg = nullptr;
-#endif
-
 // One or two output channels, plain stride-1 conv with nothing but bias / activation in the epilogue.
 // (it parallelises over (batch, 1024-step tile) only: with fewer than ~128 such tiles -- the period discriminators' 1024 -> 1
 // output conv over one row-concatenated signal -- the MFMA tile is 10x faster despite wasting 31 of its 32 rows)
-static const bool NARROW_TWO_LEVEL = !(getenv("FAC_NARROW_TWO_LEVEL") && getenv("FAC_NARROW_TWO_LEVEL")[0] == '0');
 static bool narrow_ok(const fac_conv_desc* d) {
   return d->C_out <= 2 && d->stride == 1 && d->n_phase == 1 && d->phase_shift == 0 && d->y_tstride == 1 && !d->res && !d->y2 &&
          !d->w_batched && d->y && (long long)d->B <= 65535 && (long long)d->B * ((d->T_out + 1023) / 1024) >= 128;
 }
 
-}  // namespace fac
+// FAC_PW=0 sends the k = 1 / stride-2 streaming kernels' layers back to the MFMA tiles: the independent second path of
+// tests/test_train_golden.py (a child process's environment), read once.
+static bool pw_enabled() {
+  static const bool on = !(getenv("FAC_PW") && getenv("FAC_PW")[0] == '0');
+  return on;
+}
 
-#if defined(FAC_PROF) || defined(FAC_PROF2)
-extern "C" void fac_debug_set_buffer(void* p) { fac::g_conv_dbg = (unsigned long long*)p; }
-#endif
+}  // namespace fac
 
 extern "C" int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream) {
   using namespace fac;
@@ -112,7 +109,7 @@ extern "C" int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream) {
     return conv_dispatch_bsplit2(a, s);
   }
   FAC_REQUIRE(!conv_two_level(a) || d->w, "conv1d: two-level taps outside the split kernel's shapes need fp32 weights");
-  static const bool pw_on = !(getenv("FAC_PW") && getenv("FAC_PW")[0] == '0');
+  const bool pw_on = pw_enabled();
   // stride-2 layers with few channels (weights resident in LDS as bf16 planes, inputs streamed): conv1d_pw_split.hip
   if (pw_on && d->pw_split && d->w && conv_pwt_ok(a)) return conv_dispatch_pwt(a, s);
   // 1- / 2-tap convs with split weights in the GEMM layout (fac_pack_gemm_w_split): the bf16 matrix pipe, fp32-grade
@@ -136,7 +133,7 @@ extern "C" int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream) {
               "conv1d: shape does not qualify for a split-bf16 kernel (K=%d stride=%d C_in=%d C_out=%d columns=%lld) and no fp32 "
               "weights were given", d->K, d->stride, d->C_in, d->C_out, (long long)d->B * d->T_out);
   if (!two_level && conv_skinny_ok(a, d->ws, d->ws_bytes)) return conv_dispatch_skinny(a, d->ws, d->ws_bytes, s);
-  if (narrow_ok(d) && (!two_level || (NARROW_TWO_LEVEL && (a.KV - 1) * a.dil <= 64))) return conv_dispatch_narrow(a, s);
+  if (narrow_ok(d) && (!two_level || (a.KV - 1) * a.dil <= 64)) return conv_dispatch_narrow(a, s);
   if (conv_thin_ok(a, d->ws, d->ws_bytes)) return conv_dispatch_thin(a, d->ws, s);   // C_out <= 2 without enough tiles for narrow
   if (conv_cin1_ok(a)) return conv_dispatch_cin1(a, s);
   if (pw_on && d->pw_split && conv_pw_ok(a) && conv_pws_ok(a)) return conv_dispatch_pws(a, s);   // k = 1 tails at C <= 192 on the bf16 pipe
@@ -164,7 +161,7 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
     if (name && name_len > 0) snprintf(name, name_len, "conv1d_mfma_kernel<C/32,1,1,4,7,fused RU> Cx128");
     return 7;
   }
-  if (d->pw_split && d->w && !(getenv("FAC_PW") && getenv("FAC_PW")[0] == '0')) {
+  if (d->pw_split && d->w && pw_enabled()) {
     ConvArgs a{};
     a.K = d->K; a.K1 = d->K1 > 0 ? d->K1 : d->K; a.stride = d->stride; a.dil = d->dilation; a.rp = d->row_phases > 1 ? d->row_phases : 1;
     a.pad_left = d->pad_left; a.pad_mode = d->pad_mode; a.w = d->w; a.x = d->x; a.n_phase = d->n_phase; a.phase_shift = d->phase_shift;
@@ -215,7 +212,7 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
   }
   {
     const bool two = d->K1 > 0 && d->K1 < d->K;
-    if (narrow_ok(d) && (!two || (NARROW_TWO_LEVEL && (d->K1 - 1) * d->dilation <= 64))) {
+    if (narrow_ok(d) && (!two || (d->K1 - 1) * d->dilation <= 64)) {
       if (name && name_len > 0) snprintf(name, name_len, two ? "conv1d_narrow_kernel (VALU, C_out<=2, two-level taps)" : "conv1d_narrow_kernel (VALU, C_out<=2)");
       return 9;
     }
@@ -240,7 +237,7 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
       return 12;
     }
     a.K = d->K; a.pad_left = d->pad_left; a.T_in = d->T_in; a.C_out_pad = d->C_out_pad; a.w = d->w;
-    static const bool pw_on = !(getenv("FAC_PW") && getenv("FAC_PW")[0] == '0');
+    const bool pw_on = pw_enabled();
     a.x_p8 = reinterpret_cast<const unsigned char*>(d->x_p8);
     if (pw_on && d->pw_split && conv_pw_ok(a) && conv_pws_ok(a)) {
       if (name && name_len > 0) snprintf(name, name_len, "conv1d_pws_kernel (k=1 streaming, W planes in LDS, bf16x3 split, fp32-grade)");

@@ -34,14 +34,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BS_CO = 64;
 constexpr int BS_NSW = 4;   // staging waves
-#ifndef FAC_BS_NSW_WIDE
-#define FAC_BS_NSW_WIDE 4
-#endif
-constexpr int BS_NSW_WIDE = FAC_BS_NSW_WIDE;
+constexpr int BS_NSW_WIDE = 4;
 constexpr int BS_XU = 3;    // (ci group, 64-column block) staging units per staging wave
-#ifndef FAC_BS_PERSIST
-#define FAC_BS_PERSIST 1
-#endif
 static int conv_device_cus() {
   static int cus[16] = {0};
   int dev = 0, v = 0;
@@ -57,10 +51,7 @@ static int conv_device_cus() {
 //   The boundary was 160 channels while the MFMA waves ran the epilogue alone; with the all-waves epilogue the wide shape
 //   wins from 64 channels up (C = 128: 140 -> 161, C = 96: 112 -> 126, C = 64: 110 -> 118 TFLOP/s-eq), so narrow is left for
 //   the 32- and 48-channel layers (MPD).
-#ifndef FAC_BS_WIDE_MIN
-#define FAC_BS_WIDE_MIN 64
-#endif
-constexpr int BS_WIDE_MIN = FAC_BS_WIDE_MIN;
+constexpr int BS_WIDE_MIN = 64;
 __host__ __device__ constexpr int bs_group(int C_in) { return C_in >= BS_WIDE_MIN ? 2 : 1; }
 
 __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
@@ -191,9 +182,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
   decode(fresh_args(), vb, t0, co0, b);
   const bool has_nt = overlap && vb + (int)gridDim.x < n_tiles;
 
-#ifdef FAC_PROF
-  unsigned long long pf0 = 0, pf1 = 0, pf2 = 0;
-#endif
   if constexpr (STAGING) {
     // ===================== staging waves
     const int lw = wave - NMW;
@@ -225,7 +213,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
     static_assert(W_STAGE % 1024 == 0 && ND + NX <= 63 && NX == 24, "vmcnt is a 6-bit counter; FAC_XREGS24_* list 24 registers per set");
     // (used by the narrow shape; a fully unrolled version with clamped block indices made hipcc spill 443 registers there)
     auto stage_w = [&](int chunk, int buf) {
-#if !defined(FAC_ABL_NOSTAGE) && !defined(FAC_ABL_NOSTAGE_W)
       constexpr int N16 = W_STAGE / 16;
       const unsigned char* src = wsrc + (long long)chunk * W_STAGE;
       unsigned char* dst = Wbuf + buf * STG;
@@ -234,10 +221,8 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
         if (q < N16)
           __builtin_amdgcn_global_load_lds((glb_void_t*)(src + (long long)q * 16), (lds_void_t*)(dst + i * 1024), 16, 0, 0);
       }
-#endif
     };
     auto write_x = [&](int buf, const float (&xr)[BS_XU][8]) {       // xr: landed samples, padding lanes already zero
-#if !defined(FAC_ABL_NOSTAGE) && !defined(FAC_ABL_NOSTAGE_X)
       unsigned char* xd = Xbuf + buf * STG;
 #pragma unroll
       for (int j = 0; j < BS_XU; ++j) {
@@ -253,7 +238,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
         *reinterpret_cast<bf16x8*>(xd + ((1 * G + u_g[j]) * XW + u_c[j]) * 16) = m;
         *reinterpret_cast<bf16x8*>(xd + ((2 * G + u_g[j]) * XW + u_c[j]) * 16) = l;
       }
-#endif
     };
     // Every instruction of the staging waves costs the SIMD's MFMA wave issue time, so the loads are kept to one instruction
     // each: the channel row is a uniform (scalar) base, the column a per-lane 32-bit byte offset resolved once per tile; lanes on
@@ -353,20 +337,16 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
         tile_params(nt0, nb, nco0, nboff, nmask, nxg, nws);
       }
       auto load_a = [&](const float* xgp, const unsigned (&u_boff)[BS_XU], int chunk) {
-#if !defined(FAC_ABL_NOSTAGE) && !defined(FAC_ABL_NOSTAGE_X)
         const float* grp[BS_XU];
 #pragma unroll
         for (int j = 0; j < BS_XU; ++j) grp[j] = xgp + (long long)((chunk * G + u_g[j]) * 8) * xcs;
         FAC_XREGS24_A(BS_LD)
-#endif
       };
       auto load_b = [&](const float* xgp, const unsigned (&u_boff)[BS_XU], int chunk) {
-#if !defined(FAC_ABL_NOSTAGE) && !defined(FAC_ABL_NOSTAGE_X)
         const float* grp[BS_XU];
 #pragma unroll
         for (int j = 0; j < BS_XU; ++j) grp[j] = xgp + (long long)((chunk * G + u_g[j]) * 8) * xcs;
         FAC_XREGS24_B(BS_LD)
-#endif
       };
       auto take_a = [&](float (&xr)[BS_XU][8], const unsigned long long (&u_mask)[BS_XU]) { FAC_XREGS24_A(BS_RD) };
       auto take_b = [&](float (&xr)[BS_XU][8], const unsigned long long (&u_mask)[BS_XU]) { FAC_XREGS24_B(BS_RD) };
@@ -382,12 +362,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
       typedef float wv4 __attribute__((ext_vector_type(4)));
       const int wblk0 = min(lw * ND, NBLK - ND);
       const unsigned lane16 = (unsigned)lane * 16u;
-#ifdef FAC_PROF2
-      long long pq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define BSQ(k) q[k] = clock64();
-#else
-#define BSQ(k)
-#endif
       for (int base = first ? -2 : 0; base < n_chunks; base += 2) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {                                // c + 1 has parity 1 - i: its stage and its register set
@@ -397,10 +371,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
           const bool has_next = c + 1 >= 0 && (!nx1 || has_nt), has_next2 = !nx2 || has_nt;
           float xr[BS_XU][8];
           wv4 wv[ND];
-#ifdef FAC_PROF2
-          long long q[7];
-          for (int k = 0; k < 7; ++k) q[k] = clock64();
-#endif
           if (has_next) {
             // this wave's ND consecutive 1 KiB blocks of the slab (the last wave's range is shifted back onto its neighbour's
             // instead of running over the end: the same bytes go to the same place twice) -- one lane offset for all of them, block
@@ -410,12 +380,10 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
             for (int j = 0; j < ND; ++j)
               asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(wv[j]) : "v"(lane16), "s"(src + j * 1024) : "memory");
             asm volatile("s_waitcnt vmcnt(%0)" : : "n"(ND) : "memory");
-            BSQ(1)
             unsigned long long u_mask[BS_XU];
 #pragma unroll
             for (int j = 0; j < BS_XU; ++j) u_mask[j] = nx1 ? nmask[j] : cmask[j];
             if (i == 0) take_b(xr, u_mask); else take_a(xr, u_mask);
-            BSQ(2)
           }
           if (has_next2) {
             unsigned u_boff[BS_XU];
@@ -425,16 +393,10 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
             const int chunk = nx2 ? c + 2 - n_chunks : c + 2;
             if (i == 0) load_a(xgp, u_boff, chunk); else load_b(xgp, u_boff, chunk);
           }
-          BSQ(3)
           if (has_next) {
             write_x(1 - i, xr);
-#ifdef FAC_PROF2
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-            BSQ(4)
             if (has_next2) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NX) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            BSQ(5)
             unsigned char* dst = Wbuf + (1 - i) * STG + wblk0 * 1024 + lane16;
 #pragma unroll
             for (int j = 0; j < ND; ++j) {
@@ -444,15 +406,8 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
           }
           if (c >= -1) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            BSQ(6)
             __builtin_amdgcn_s_barrier();      // c = -1: chunk 0 staged; later: pairs with the MFMA waves' barrier behind chunk c
             asm volatile("" ::: "memory");
-#ifdef FAC_PROF2
-            if (c >= 0 && c + 2 < n_chunks) {      // steady-state iterations only
-              pq[0] += q[1] - q[0]; pq[1] += q[2] - q[1]; pq[2] += q[3] - q[2]; pq[3] += q[4] - q[3]; pq[4] += q[5] - q[4];
-              pq[5] += q[6] - q[5]; pq[6] += clock64() - q[6]; pq[7] += 1;
-            }
-#endif
           }
         }
       }
@@ -465,13 +420,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
         cxg = nxg;
         cws = nws;
       }
-#ifdef FAC_PROF2
-      if (a.dbg && lw == 0 && lane == 0) {
-        unsigned long long* d = a.dbg + (long long)blockIdx.x * 16 + 8;
-        for (int k = 0; k < 8; ++k) d[k] = (unsigned long long)pq[k];
-      }
-#endif
-#undef BSQ
 #undef BS_LD
 #undef BS_RD
     } else {
@@ -481,7 +429,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
 #pragma unroll
       for (int j = 0; j < BS_XU; ++j) u_off[j] = u_idx[j] >= 0 ? u_idx[j] : 0;
       auto load_x = [&](int chunk, float (&xr)[BS_XU][8]) {
-#if !defined(FAC_ABL_NOSTAGE) && !defined(FAC_ABL_NOSTAGE_X)
 #pragma unroll
         for (int j = 0; j < BS_XU; ++j) {
           const float* grp = xg + (long long)((chunk * G + u_g[j]) * 8) * xcs;
@@ -491,7 +438,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
             xr[j][i] = u_idx[j] >= 0 ? v : 0.f;
           }
         }
-#endif
       };
       float xa[BS_XU][8], xb[BS_XU][8];
       load_x(0, xa);
@@ -518,14 +464,7 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
     __builtin_amdgcn_s_setprio(0);
   } else {
   // ========================= MFMA waves
-#ifdef FAC_PROF
-  const unsigned long long tp0 = wall_clock64();
-#endif
   __builtin_amdgcn_s_setprio(FAC_PRIO_MFMA);
-#ifdef FAC_PROF2
-  const long long ck0 = clock64();
-  const unsigned long long wk0 = wall_clock64();
-#endif
   const int l31 = lane & 31;
   const int kq = lane >> 5;
   const int n0 = wave * 64;
@@ -544,13 +483,7 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
   const int x_step = (G == 2 ? dil : 2 * dil) * 16;
 
   if (first) __syncthreads();   // chunk 0 staged (a tile started by the previous tile's last step needs no barrier: overlap mode)
-#ifdef FAC_PROF
-  const unsigned long long tp1 = wall_clock64();
-#endif
-#ifndef FAC_BS_PIPE
-#define FAC_BS_PIPE 1
-#endif
-  if constexpr (NMW == 4 && FAC_BS_PIPE) {
+  if constexpr (NMW == 4) {
     // ---- wide shape, round 4: the fragment pipeline runs ACROSS the stage barrier.
     // A stage is H / 2 steps of 24 MFMAs; the fragments of step s + 1 are requested while step s multiplies (two register sets).
     //  * The 12 ds_read_b128 of the next step are interleaved with the MFMAs of the current one (sched_group_barrier: 2 MFMAs,
@@ -632,28 +565,16 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
     if (co0 + 32 >= a.C_out) pipeline(std::integral_constant<int, 1>{});
     else pipeline(std::integral_constant<int, MB>{});
   } else {
-#ifdef FAC_PROF2
-  long long pm[3] = {0, 0, 0};
-#endif
   for (int chunk = 0; chunk < n_chunks; ++chunk) {
-#ifdef FAC_PROF2
-    const long long m0 = clock64();
-#endif
     const int buf = chunk & 1;
     const unsigned char* Wb = Wbuf + buf * STG + (kq * BS_CO + l31) * 16;          // half slot 2s + kq
     const unsigned char* Xb = Xbuf + buf * STG + (n0 + l31) * 16 + x_lane;
-    // A fragments are requested one step ahead (register double buffer); B fragments at the start of their
-    // step, in the order the six terms consume them (the compiler waits per fragment, and the second workgroup
-    // on the CU covers what latency remains) -- keeps the kernel under the 170 VGPRs of 3 waves per SIMD.
-#ifndef FAC_BS_BDBL
-#define FAC_BS_BDBL 1
-#endif
-    constexpr bool BDBL = FAC_BS_BDBL && NMW == 4;     // B fragments requested one step ahead as well (two register sets)
-    bf16x8 A[2][MB][3], Bf[BDBL ? 2 : 1][NB][3];
+    // narrow shape: 8 MFMA waves (2 per SIMD, 3 waves per SIMD in all -> 170 VGPRs).  The sibling wave hides the LDS latency, so
+    // the A and B fragments are fetched at the start of their step, B in the order the six terms consume them (the compiler
+    // waits per fragment), and one register set of each is used (set 0; the array shapes are the ones the register allocation,
+    // and with it the measured instruction text, was built from).
+    bf16x8 A[2][MB][3], Bf[1][NB][3];
     auto ldA = [&](int st, bf16x8 (&Ad)[MB][3]) {
-#ifdef FAC_ABL_NOLDS
-      if (st > 1) return;
-#endif
 #pragma unroll
       for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -661,9 +582,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
           Ad[m][p] = *reinterpret_cast<const bf16x8*>(Wb + ((p * H + 2 * st) * BS_CO + m * 32) * 16);
     };
     auto ldB = [&](int st, bf16x8 (&Bd)[NB][3]) {
-#ifdef FAC_ABL_NOLDS
-      if (st > 0) return;
-#endif
       const int xo = st * x_step;
       constexpr int PO[3] = {1, 0, 2};   // planes in order of first use: mid, hi, lo
 #pragma unroll
@@ -672,74 +590,27 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
         for (int n = 0; n < NB; ++n)
           Bd[n][PO[pi]] = *reinterpret_cast<const bf16x8*>(Xb + xo + (PO[pi] * G * XW + n * 32) * 16);
     };
-    // 8 MFMA waves (2 per SIMD, 3 waves per SIMD in all -> 170 VGPRs): the sibling wave hides the LDS latency,
-    // so A is fetched at the start of its step too and only one A buffer is kept
-    constexpr bool ADBL = NMW == 4;
-    if (ADBL) ldA(0, A[0]);
-    if (BDBL) ldB(0, Bf[0]);
 #pragma unroll
     for (int st = 0; st < H / 2; ++st) {
-      if (BDBL) {
-        if (st + 1 < H / 2) ldB(st + 1, Bf[(st + 1) & 1]);
-      } else {
-        ldB(st, Bf[0]);
-      }
-      if (ADBL) {
-        if (st + 1 < H / 2) ldA(st + 1, A[(st + 1) & 1]);
-      } else {
-        ldA(st, A[0]);
-      }
+      ldB(st, Bf[0]);
+      ldA(st, A[0]);
       __builtin_amdgcn_sched_barrier(0);
-      const int s = ADBL ? (st & 1) : 0;
-      const int sb = BDBL ? (st & 1) : 0;
       // smallest terms first: mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi.  The term loop is OUTSIDE the
       // block loops so that consecutive MFMAs write different accumulators (no back-to-back dependency).
       constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};
-#ifndef FAC_ABL_NOMFMA
 #pragma unroll
       for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
           for (int n = 0; n < NB; ++n)
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s][m][TA[q]], Bf[sb][n][TB[q]], acc[m][n], 0, 0, 0);
-#else
-#pragma unroll
-      for (int m = 0; m < MB; ++m)
-#pragma unroll
-        for (int n = 0; n < NB; ++n) acc[m][n][st & 15] += (float)A[s][m][0][0] * (float)Bf[sb][n][1][1] + (float)A[s][m][2][3] + (float)Bf[sb][n][2][5] + (float)A[s][m][1][7] * (float)Bf[sb][n][0][2];
-#endif
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0][m][TA[q]], Bf[0][n][TB[q]], acc[m][n], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef FAC_PROF2
-    const long long m1 = clock64();
-#endif
     __syncthreads();
-#ifdef FAC_PROF2
-    pm[0] += m1 - m0; pm[1] += clock64() - m1; pm[2] += 1;
-#endif
   }
-#ifdef FAC_PROF2
-  if (a.dbg && wave == 0 && lane == 0) {
-    unsigned long long* d = a.dbg + (long long)blockIdx.x * 16;
-    d[0] = (unsigned long long)pm[0]; d[1] = (unsigned long long)pm[1]; d[2] = (unsigned long long)pm[2];
   }
-#endif
-
-  }
-#ifdef FAC_PROF
-  const unsigned long long tp2 = wall_clock64();
-  pf0 = tp0; pf1 = tp1; pf2 = tp2;
-#endif
   __builtin_amdgcn_s_setprio(0);
-#ifdef FAC_PROF2
-  if (a.dbg && wave == 0 && lane == 0) {      // shader clock (s_memtime) against the constant 100 MHz clock over the main loop
-    unsigned long long* d = a.dbg + (long long)blockIdx.x * 16;
-    d[3] = (unsigned long long)(clock64() - ck0);
-    d[4] = wall_clock64() - wk0;
-    d[5] = (unsigned long long)n_chunks;
-  }
-#endif
   // ---- accumulators -> LDS (both stage buffers are free now; overlap mode: stage 1 is, stage 0 already holds the next tile's
   // chunk 0): tile[co][t] fp32, row pitch BS_TT + 4 floats.
   // C/D layout of the 32x32 block: register r <-> row (r & 3) + 8 (r >> 2) + 4 kq, column l31.
@@ -821,12 +692,6 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
       }
     }
   }
-#ifdef FAC_PROF
-  if (a.dbg && tid == 0) {
-    unsigned long long* d = a.dbg + (long long)blockIdx.x * 8;
-    d[0] = pf0; d[1] = pf1; d[2] = pf2; d[3] = wall_clock64(); d[4] = 0; d[5] = 0;
-  }
-#endif
   first = !overlap;
   if (vb + (int)gridDim.x < n_tiles) __syncthreads();     // the epilogue has read its tile: the stage buffers may be written again
   }   // tiles of this workgroup
@@ -873,10 +738,10 @@ static int bsplit_launch(ConvArgs& a, hipStream_t s) {
   }
   // One workgroup per CU walking several tiles, the next tile's first chunk staged under the last chunk of the current one
   // (kernel header): wide shape with fp32 inputs, an even number of chunks (stage / register-set parity continues across tiles),
-  // more tiles than CUs, and the epilogue tile must fit behind stage 0.  FAC_BS_PERSIST=0 restores one tile per workgroup.
+  // more tiles than CUs, and the epilogue tile must fit behind stage 0.
   const int n_chunks = (a.C_in + 8 * G - 1) / (8 * G);
   int cus = conv_device_cus() & ~7;
-  a.persist = (FAC_BS_PERSIST && G == 2 && NMW == 4 && a.x_p8 == nullptr && n_chunks % 2 == 0 && cus >= 8 && n_wg > cus &&
+  a.persist = (G == 2 && NMW == 4 && a.x_p8 == nullptr && n_chunks % 2 == 0 && cus >= 8 && n_wg > cus &&
                stg + (stg > epi ? stg : epi) <= 160 * 1024) ? 1 : 0;
   size_t lds = a.persist ? stg + (stg > epi ? stg : epi) : (2 * stg > epi ? 2 * stg : epi);
   if (lds > 160 * 1024) {
@@ -890,9 +755,6 @@ static int bsplit_launch(ConvArgs& a, hipStream_t s) {
     attr_set = true;
   }
   a.n_tiles = (int)n_wg;
-#if defined(FAC_PROF) || defined(FAC_PROF2)
-  a.dbg = g_conv_dbg;
-#endif
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.persist ? cus : n_wg)), dim3((NMW + NSW) * 64), lds, s, a);
   return check_launch("conv1d_bsplit");
 }

@@ -205,20 +205,12 @@ __global__ __launch_bounds__(512, 2) void conv1d_bsplit2_kernel(ConvArgs a) {
       for (int j = 0; j < XU; ++j) {
         if (u_c[j] < 0) continue;
         bf16x8 h, m, l;
-#if defined(FAC_ABL2_NOSTAGE_X)
-        continue;                      // ablation builds only (tools/tune/abl_bsplit2.py): results are wrong, timing is the point
-#elif defined(FAC_ABL2_NOSPLIT)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = (__bf16)xr[j][i];
-        m = h; l = h;
-#else
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           __bf16 p0, p1, p2;
           b2_split3(xr[j][i], p0, p1, p2);
           h[i] = p0; m[i] = p1; l[i] = p2;
         }
-#endif
         *reinterpret_cast<bf16x8*>(xd + u_pos[j]) = h;
         *reinterpret_cast<bf16x8*>(xd + XWT * 16 + u_pos[j]) = m;
         *reinterpret_cast<bf16x8*>(xd + 2 * XWT * 16 + u_pos[j]) = l;
@@ -379,8 +371,6 @@ __global__ __launch_bounds__(512, 2) void conv1d_bsplit2_kernel(ConvArgs a) {
 
 // (K1, stride) pairs built: (9, 1), (9, 2), (3, 1).  Zero padding, no Snake prologue, at most 32 output channels.
 bool conv_bsplit2_ok(const ConvArgs& a) {
-  static const bool on = !(getenv("FAC_BSPLIT2") && getenv("FAC_BSPLIT2")[0] == '0');
-  if (!on) return false;
   if (!(a.dil == 1 && a.n_phase == 1 && a.phase_shift == 0 && a.y_tstride == 1 && a.rp == 1 && !a.alpha_in && !a.w1 && !a.w_batched &&
         a.pad_mode == FAC_PAD_ZERO))
     return false;

@@ -594,9 +594,8 @@ extern "C" int fac_snake_bwd_fused_rs(const float* x, const float* alpha, const 
   using namespace fac;
   FAC_REQUIRE(x && alpha && dy && dx && dalpha && scratch && B > 0 && C > 0 && T > 0 && dy_row_stride >= T, "snake_bwd_fused: bad arguments");
   float* part2 = dbias ? scratch + (long long)RED_NS * C : nullptr;
-  static const bool v4_on = !(getenv("FAC_SNAKE_BWD_V4") && getenv("FAC_SNAKE_BWD_V4")[0] == '0');
   auto al = [](const void* p, unsigned m) { return (reinterpret_cast<unsigned long long>(p) & m) == 0; };
-  if (v4_on && (T & 3) == 0 && (dy_row_stride & 1) == 0 && al(x, 15) && al(dx, 15) && (!add || al(add, 15)) && al(dy, 7))
+  if ((T & 3) == 0 && (dy_row_stride & 1) == 0 && al(x, 15) && al(dx, 15) && (!add || al(add, 15)) && al(dy, 7))
     hipLaunchKernelGGL(snake_bwd_fused_v4_kernel, dim3(C, red_slices((long long)B * T / 4)), dim3(256), 0, (hipStream_t)stream, x, alpha, dy, add,
                        dx, scratch, part2, B, C, T, dy_row_stride);
   else

@@ -52,11 +52,7 @@ __device__ __forceinline__ void gs_split3(float x, __bf16& h, __bf16& m, __bf16&
 // kernel, 0.00 on the others: profiles/r06_pmc_train.json).  f = bit 2 | (bit 1 ^ bit 3) << 1 keeps the fragment reads (16-lane groups
 // {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} over a 256-byte window, rows shifted by the tap) conflict-free and makes 8 aligned
 // consecutive rows hit 8 different 16-byte slots (exhaustive search over the GF(2)-linear maps of the row bits: tools/tune/lds_swizzle_search.py).
-#ifdef FAC_GS_OLD_SWZ   // tuning builds: the swizzle of rounds 3 - 5
-__device__ __forceinline__ int gs_xswz(int row) { return (row >> 2) & 3; }
-#else
 __device__ __forceinline__ int gs_xswz(int row) { return ((row >> 2) & 1) | ((((row >> 1) ^ (row >> 3)) & 1) << 1); }
-#endif
 
 __device__ __forceinline__ void gs_barrier() {
   asm volatile("" ::: "memory");
@@ -590,8 +586,6 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
 
 // Shapes the kernel takes.  K = 1: pad_left 0, T_in >= T_out; K = 2: zero padding (pad_left 0 or 1), per-clip tiles.
 bool conv_gsplit_ok(const ConvArgs& a) {
-  static const bool on = !(getenv("FAC_GEMM_SPLIT") && getenv("FAC_GEMM_SPLIT")[0] == '0');
-  if (!on) return false;
   const bool strided = a.stride > 1;          // K <= 2 * stride taps as 2 taps of `stride` phase sub-signals
   if (!(a.dil == 1 && a.n_phase == 1 && a.phase_shift == 0 && a.y_tstride == 1 && !a.alpha_in && !a.w1 && !a.w_batched &&
         !conv_two_level(a)))
@@ -629,10 +623,9 @@ static int gsplit_launch(ConvArgs& a, hipStream_t s) {
   const int rows = a.rp > 1 ? a.C_out_pad : a.C_out;
   const int n_rt = (rows + GS_ROWS - 1) / GS_ROWS;
   const long long n_wg = (long long)a.n_t_tiles * n_rt * (a.gflat ? 1 : a.B);
-  // order of the tiles inside an XCD's share (see the kernel): FAC_GS_ROW_FAST = 0 / 1 forces, default = by bytes: keep the
+  // order of the tiles inside an XCD's share (see the kernel), by bytes: keep the
   // weights resident when re-reading the input per row tile is the cheaper side, else the input
   {
-    static const int env = [] { const char* e = getenv("FAC_GS_ROW_FAST"); return e == nullptr ? -1 : (e[0] != '0' ? 1 : 0); }();
     // bytes that leave the L2s under either order (model): x = the input, W = all split weights, n_ct column tiles.
     //   row tile slowest: the input once per row tile, the weights once                          -> x * n_rt + W
     //   row tile fastest: the input once; the weights stay in an XCD's 4 MB L2 if they fit (8 copies), else they are streamed
@@ -644,7 +637,7 @@ static int gsplit_launch(ConvArgs& a, hipStream_t s) {
     const double slow = x_bytes * n_rt + w_bytes;
     const double fast = x_bytes + (w_bytes <= 3.5 * 1048576.0 ? 8.0 * w_bytes : w_bytes * n_ct / g);
     const bool by_bytes = n_rt > 1 && fast < 0.8 * slow;
-    a.grt = (env >= 0 ? env == 1 : by_bytes) ? n_rt : 0;
+    a.grt = by_bytes ? n_rt : 0;
   }
   if (n_wg > 0x7fffffffll) {
     set_error("conv1d(gemm split): too many workgroups (%lld)", n_wg);

@@ -62,9 +62,6 @@ struct ConvArgs {
   int XQ, XR;  // 4 / XB, 4 % XB: (row, block) advance of one wave per staging iteration
   int n_t_tiles;
   int n_tiles, persist;   // conv1d_bsplit.hip: tiles of the launch; 1 = workgroups walk several tiles as one chunk stream
-#if defined(FAC_PROF) || defined(FAC_PROF2)
-  unsigned long long* dbg;   // per-workgroup cycle counters (tuning builds only)
-#endif
   int x_off;   // columns staged to the left of the receptive field so that the slab starts 16-B aligned
   int gflat;   // conv1d_gemm_split.hip: columns are the flattened (clip, time) index (K = 1)
   int grt;     // conv1d_gemm_split.hip: > 0 = number of row tiles, and the row tile is the FASTEST index of the logical order
@@ -104,11 +101,9 @@ constexpr int conv_cic() {
   return ((KT == 2 || KT == 3) && T_TILE >= 256) ? 8 : ConvUnroll<KT>::CIC;
 }
 
-#ifndef FAC_CONV_WPE
-#define FAC_CONV_WPE 4
-#endif
+constexpr int CONV_WPE = 4;   // workgroups per CU the 4-MFMA-wave tiles are compiled for (register budget)
 template <int MB, int NB, int WM, int WN, int KT, bool FUSE = false>
-__global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 3)) void conv1d_mfma_kernel(ConvArgs a) {
+__global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? CONV_WPE : 3)) void conv1d_mfma_kernel(ConvArgs a) {
   constexpr int NMW = WM * WN;   // MFMA waves (4 or 8); 4 staging waves follow them
   constexpr int CO_TILE = 32 * MB * WM;
   constexpr int T_TILE = 32 * NB * WN;
@@ -169,9 +164,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
     // cycles to ISSUE one chunk's loads; MFMA waves then idled 47 % of their life at the barrier).
     // The staging stream is short (a few hundred instructions per chunk), so it runs at raised priority
     // and the MFMA waves absorb the few lost slots.
-#ifndef FAC_ABL_NOPRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
     const float* xg = a.x + (long long)b * a.x_bs;
     const int w_rows_total = cin_pad_dev(a.C_in) * a.K;   // rows C_in*K.. are zero (fac_pack_conv_w); a.K = K2v * K
     const float* wg = a.w + (long long)phase * w_rows_total * a.C_out_pad +
@@ -186,18 +179,11 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
     const bool x_dma = a.alpha_in == nullptr && vec_ok && tin0 >= 0 && tin0 + (K2v - 1) * dil2 + XW <= a.T_in &&
                        (K2v == 1 || (dil2 & 3) == 0);
 
-#ifdef FAC_PROF
-    unsigned long long lt_issue = 0, lt_wait = 0, lt_store = 0, lt_bar = 0;
-#endif
     auto stage = [&](int chunk, int buf) {
-#ifdef FAC_PROF
-      const unsigned long long q0 = __builtin_readcyclecounter();
-#endif
       // weight slab by LDS-DMA: flat float4 index q -> (row, col4); 64 lanes = 1 KiB contiguous in
       // LDS.  The packed buffer carries ZERO rows up to fac_cin_pad(C_in) channels, so a partially
       // filled last stage multiplies zeros whatever the input slab holds there; columns past
       // C_out_pad are clamped to valid weights and only feed output rows that are never stored.
-#ifndef FAC_ABL_NOW
       {
         const int n4 = cic * K * CO4;
         const int row_base = chunk * cic * K;
@@ -216,10 +202,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
           }
         }
       }
-#endif
-#ifdef FAC_ABL_NOX
-      return;
-#endif
       // input slab: slot j of this wave covers row r, float4 column cb*64 + lane; all loads are
       // issued first, then Snake is applied on the way into LDS (once per staged element).
       // Interior + 16-B aligned rows move as float4; edges (reflection / zero padding / ragged ends)
@@ -242,9 +224,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
             __builtin_amdgcn_global_load_lds((glb_void_t*)src, (lds_void_t*)(dst + r * XW + (it - r * XB) * 256), 16, 0, 0);
           }
         }
-#ifdef FAC_PROF
-        lt_issue += __builtin_readcyclecounter() - q0;
-#endif
         return;
       }
       float4 xr[CONV_XMAX];
@@ -283,13 +262,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
           if (cb >= XB) { cb -= XB; ++r; }
         }
       }
-#ifdef FAC_PROF
-      const unsigned long long q1 = __builtin_readcyclecounter();
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      const unsigned long long q2 = __builtin_readcyclecounter();
-      lt_issue += q1 - q0;
-      lt_wait += q2 - q1;
-#endif
       {
         float* dst = Xbuf + buf * x_stage;
         int r = r_first, cb = cb_first;
@@ -312,26 +284,13 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
           if (cb >= XB) { cb -= XB; ++r; }
         }
       }
-#ifdef FAC_PROF
-      lt_store += __builtin_readcyclecounter() - q2;
-#endif
     };
 
     stage(0, 0);
     __syncthreads();   // the barrier's release also drains the LDS-DMA (vmcnt(0))
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
-#ifndef FAC_ABL_NOSTAGE
       if (chunk + 1 < n_chunks) stage(chunk + 1, (chunk & 1) ^ 1);
-#endif
-#ifdef FAC_PROF
-      const unsigned long long qb = __builtin_readcyclecounter();
-#endif
-#ifndef FAC_ABL_NOBAR
       __syncthreads();
-#endif
-#ifdef FAC_PROF
-      lt_bar += __builtin_readcyclecounter() - qb;
-#endif
     }
     if constexpr (FUSE) {
       // fused ResidualUnit: every stage buffer is free now -- DMA the whole 1x1 weight matrix
@@ -348,20 +307,10 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
       }
       __syncthreads();
     }
-#ifdef FAC_PROF
-    if (a.dbg && lane == 0) {
-      unsigned long long* d = a.dbg + (1ll << 21) + ((long long)blockIdx.x * 4 + lw) * 4;
-      d[0] = lt_issue; d[1] = lt_wait; d[2] = lt_store; d[3] = lt_bar;
-    }
-#endif
     if constexpr (!ALLW) return;
     __builtin_amdgcn_s_setprio(0);
   }
 
-#ifdef FAC_PROF
-  unsigned long long pf_first = 0, pf_bar = 0, pf_loop = 0;
-  const unsigned long long pf_start = __builtin_readcyclecounter();
-#endif
   if (wave < NMW) {
   // ========================= MFMA waves
   const int l31 = lane & 31;
@@ -383,13 +332,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
   const int dil = a.dil;
   const int nstride = 32 * a.stride;
 
-#ifdef FAC_PROF
-  unsigned long long t_start = __builtin_readcyclecounter(), t_bar = 0, t_first = 0;
-#endif
   __syncthreads();   // chunk 0 staged
-#ifdef FAC_PROF
-  t_first = __builtin_readcyclecounter() - t_start;
-#endif
   for (int chunk = 0; chunk < n_chunks; ++chunk) {
     const int buf = chunk & 1;
     const float* Wb = Wbuf + buf * w_stage + a_off + kq * wrow_stride;
@@ -403,17 +346,10 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
       float av[3][MB], bv[3][NB];
       auto ldfrag = [&](int pos, float* avp, float* bvp) {
         const int c2 = (pos / KT) * 2, kk = pos % KT;
-#ifdef FAC_ABL_NOLDS
-#pragma unroll
-        for (int m = 0; m < MB; ++m) avp[m] = (float)(pos + m) * 1e-3f + (float)lane;
-#pragma unroll
-        for (int n = 0; n < NB; ++n) bvp[n] = (float)(pos - n) * 1e-3f;
-#else
 #pragma unroll
         for (int m = 0; m < MB; ++m) avp[m] = Wb[c2 * wrow_stride + kk * CO_TILE + m * 32];
 #pragma unroll
         for (int n = 0; n < NB; ++n) bvp[n] = Xb[c2 * XW + kk * dil + n * nstride];
-#endif
       };
       ldfrag(0, av[0], bv[0]);
       if constexpr (P > 1) ldfrag(1, av[1], bv[1]);
@@ -425,11 +361,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
         for (int m = 0; m < MB; ++m)
 #pragma unroll
           for (int n = 0; n < NB; ++n)
-#ifdef FAC_ABL_NOMFMA
-            acc[m][n][pos & 15] += av[pos % 3][m] * bv[pos % 3][n];
-#else
             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[pos % 3][m], bv[pos % 3][n], acc[m][n], 0, 0, 0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
@@ -451,20 +383,8 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
         }
       }
     }
-#ifdef FAC_PROF
-    const unsigned long long tb0 = __builtin_readcyclecounter();
-#endif
-#ifndef FAC_ABL_NOBAR
     __syncthreads();
-#endif
-#ifdef FAC_PROF
-    t_bar += __builtin_readcyclecounter() - tb0;
-#endif
   }
-#ifdef FAC_PROF
-  const unsigned long long t_loop = __builtin_readcyclecounter() - t_start;
-  pf_first = t_first; pf_bar = t_bar; pf_loop = __builtin_readcyclecounter() - pf_start;
-#endif
 
   if constexpr (ALLW) {
     constexpr int EP = T_TILE + 4;
@@ -584,12 +504,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
       emit_block(acc2, cb, a.bias1, nullptr, FAC_ACT_NONE);
     }
   }
-#ifdef FAC_PROF
-  if (a.dbg && lane == 0) {
-    unsigned long long* d = a.dbg + ((long long)blockIdx.x * 4 + (wave & 3)) * 4;
-    d[0] = t_first; d[1] = t_bar; d[2] = t_loop; d[3] = __builtin_readcyclecounter() - t_start;
-  }
-#endif
   }   // !ALLW epilogue
   }   // MFMA waves
 
@@ -706,18 +620,8 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? FAC_CONV_WPE : 
         }
       }
     }
-#ifdef FAC_PROF
-    if (a.dbg && lane == 0 && wave < 4) {
-      unsigned long long* d = a.dbg + ((long long)blockIdx.x * 4 + wave) * 4;
-      d[0] = pf_first; d[1] = pf_bar; d[2] = pf_loop; d[3] = __builtin_readcyclecounter() - pf_start;
-    }
-#endif
   }
 }
-
-#if defined(FAC_PROF) || defined(FAC_PROF2)
-extern unsigned long long* g_conv_dbg;
-#endif
 
 // Picks channels-per-stage and launches one instantiation.
 template <int MB, int NB, int WM, int WN, int KT, bool FUSE = false>
@@ -776,9 +680,6 @@ int launch_cfg(ConvArgs& a, hipStream_t s) {
     attr_set = true;
   }
   a.n_t_tiles = (a.T_out + T_TILE - 1) / T_TILE;
-#ifdef FAC_PROF
-  a.dbg = g_conv_dbg;
-#endif
   if (a.rp > 1 && !((WM * WN == 8) && !FUSE && CO_TILE == 128)) {
     set_error("conv1d: row_phases needs the 128-row all-waves-epilogue tile");
     return FAC_ERR_ARG;

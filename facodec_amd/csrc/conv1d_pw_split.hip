@@ -373,9 +373,8 @@ static int pws_slice_channels(int C) {
 }
 
 bool conv_pws_ok(const ConvArgs& a) {
-  static const bool on = !(getenv("FAC_PW_SPLIT") && getenv("FAC_PW_SPLIT")[0] == '0');
-  if (!on || !(a.K == 1 && a.stride == 1 && a.n_phase == 1 && a.phase_shift == 0 && a.y_tstride == 1 && a.pad_left == 0 && !a.alpha_in &&
-               !a.w1 && !a.w_batched && !conv_two_level(a) && a.T_in >= a.T_out && a.C_in == a.C_out && !a.x_p8))
+  if (!(a.K == 1 && a.stride == 1 && a.n_phase == 1 && a.phase_shift == 0 && a.y_tstride == 1 && a.pad_left == 0 && !a.alpha_in &&
+        !a.w1 && !a.w_batched && !conv_two_level(a) && a.T_in >= a.T_out && a.C_in == a.C_out && !a.x_p8))
     return false;
   const int co = pws_slice_channels(a.C_out);
   if (!co || a.C_out_pad != a.C_out) return false;
@@ -430,9 +429,7 @@ static int pwt_shape(const ConvArgs& a) {
 }
 
 bool conv_pwt_ok(const ConvArgs& a) {
-  static const bool on = !(getenv("FAC_PW_TAPS") && getenv("FAC_PW_TAPS")[0] == '0') &&
-                         !(getenv("FAC_PW_SPLIT") && getenv("FAC_PW_SPLIT")[0] == '0');
-  if (!on || !pwt_shape(a) || !a.w || !a.x) return false;
+  if (!pwt_shape(a) || !a.w || !a.x) return false;
   if (!(a.dil == 1 && a.n_phase == 1 && a.phase_shift == 0 && a.y_tstride == 1 && !a.alpha_in && !a.alpha_out && a.act == FAC_ACT_NONE &&
         !a.res && !a.w1 && !a.w_batched && !conv_two_level(a) && !a.x_p8 && !a.y2_p8))
     return false;

@@ -338,12 +338,10 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvArgs a) {
   if (a.y2) { const float al2 = a.alpha2[co]; a.y2[o] = snake_apply(v, al2, snake_inv(al2)); }
 }
 
-static int skinny_env(const char* name, int dflt);
 // 8 or 4 channels per workgroup, or 0: not a shape for this kernel
 static int gemv_co(const ConvArgs& a) {
-  const bool on = skinny_env("FAC_GEMV", 1) != 0;            // (read per launch: tools/tune/stream_ab_inproc.py flips it between sessions)
-  static const long long max_wg = (long long)skinny_env("FAC_GEMV_MAX_WG_KB", 100) * 1024;   // weights one workgroup may walk
-  if (!on || (long long)a.B * a.T_out > 4 || a.phase_shift != 0) return 0;
+  constexpr long long max_wg = 100 * 1024;   // weights one workgroup may walk
+  if ((long long)a.B * a.T_out > 4 || a.phase_shift != 0) return 0;
   if (a.act == FAC_ACT_GATE || a.act == FAC_ACT_WN_RES_SKIP) {
     if (a.n_phase != 1 || a.y_tstride != 1) return 0;
     if (a.act == FAC_ACT_GATE) return a.C_out % 8 == 0 && (long long)a.C_in * a.K * 32 <= max_wg ? 8 : 0;
@@ -355,14 +353,10 @@ static int gemv_co(const ConvArgs& a) {
 }
 static bool gemv_ok(const ConvArgs& a) { return gemv_co(a) != 0; }
 
-// tuning knobs (tools/tune/skinny_probe.py): workgroups aimed at, fewest (ci-pair, tap) rows per slice, rows in flight per wave
-static int skinny_env(const char* name, int dflt) {   // (declared above for gemv_ok)
-  const char* v = getenv(name);
-  return v && v[0] ? atoi(v) : dflt;
-}
-static const int kSkinnyWgs = skinny_env("FAC_SKINNY_WGS", 512);
-static const int kSkinnyMinRows = skinny_env("FAC_SKINNY_MIN_ROWS", 32);
-static const int kSkinnyU = skinny_env("FAC_SKINNY_U", 8);
+// tuned with tools/tune/skinny_probe.py: workgroups aimed at, fewest (ci-pair, tap) rows per slice, rows in flight per wave
+constexpr int kSkinnyWgs = 512;
+constexpr int kSkinnyMinRows = 32;
+constexpr int kSkinnyU = 8;
 
 static SkinnyGeom skinny_geom(const ConvArgs& a, int* n_tiles) {
   SkinnyGeom g;
@@ -375,7 +369,7 @@ static SkinnyGeom skinny_geom(const ConvArgs& a, int* n_tiles) {
   if (tiles >= 128) S = 1;                                // enough tiles already: skip the reduce kernel
   // >= 8 rows per wave; >= 4 for the short reductions (k = 1 with <= 512 channels: otherwise one workgroup per tile, a handful of
   // workgroups on the chip and the whole epilogue in them -- 17 -> 10 us for the 64- / 96-channel ResidualUnit tails of a hop)
-  const int min_rows = g.rows <= 256 ? (kSkinnyMinRows < 16 ? kSkinnyMinRows : 16) : kSkinnyMinRows;
+  const int min_rows = g.rows <= 256 ? 16 : kSkinnyMinRows;
   const int max_s = g.rows / min_rows > 0 ? g.rows / min_rows : 1;
   if (S > max_s) S = max_s;
   if (S > SK_MAX_S) S = SK_MAX_S;
@@ -413,20 +407,12 @@ int conv_dispatch_skinny(ConvArgs& a, void* ws, long long ws_bytes, hipStream_t 
   (void)ws_bytes;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_skinny_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_skinny_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_skinny_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_skinny_kernel<kSkinnyU>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     attr_set = true;
   }
   float* part = reinterpret_cast<float*>(ws);
   const dim3 grid(g.co_tiles, g.S, g.n_cb * a.n_phase);
-  const int per_wave = (g.rows_per_slice + 3) / 4;
-  if (kSkinnyU >= 32 && per_wave > 16)
-    hipLaunchKernelGGL(conv1d_skinny_kernel<32>, grid, dim3(256), 65536, s, a, g, part);
-  else if (kSkinnyU >= 16 && per_wave > 8)
-    hipLaunchKernelGGL(conv1d_skinny_kernel<16>, grid, dim3(256), 65536, s, a, g, part);
-  else
-    hipLaunchKernelGGL(conv1d_skinny_kernel<8>, grid, dim3(256), 65536, s, a, g, part);
+  hipLaunchKernelGGL(conv1d_skinny_kernel<kSkinnyU>, grid, dim3(256), 65536, s, a, g, part);
   if (a.act == FAC_ACT_GATE)
     hipLaunchKernelGGL(conv1d_skinny_reduce_gate_kernel, dim3(tiles * 2), dim3(256), 0, s, a, g, part);
   else if (g.S > 1)

@@ -505,10 +505,11 @@ struct WkArgs {
   int B, C_in_real, CV, C_out, K, stride, dil, K2, dil2s;
   int NBk;                   // blocks = ceil(CV / 32) * K
   int n_tt, tiles_per_split;
-  int MT;                    // 128-row tiles per workgroup (1 or 2)
+  int unused;                // (was the row-tile count of a retired 256-row variant; kept so that the argument layout, and with it the
+                             // kernels' instruction text, is the measured one)
   int gx, gy, gz, per_xcd;   // logical grid (row tiles, column-block quads, (b, t) slices) and workgroups per XCD (0: plain 3-D grid)
-  int narrow_rows;           // bit 0: row tiles with <= 96 real output channels run the column-split wave layouts (FAC_WGRAD_NARROW=0: off);
-                             // bit 1: their clamped duplicate rows are not staged (FAC_WGRAD_SKIP_DUP=0: staged as before)
+  int narrow_rows;           // 3 (0 with FAC_WGRAD_NARROW=0) -- bit 0: row tiles with <= 96 real output channels run the column-split
+                             // wave layouts; bit 1: their clamped duplicate rows are not staged
 };
 
 __device__ __forceinline__ void wk_barrier() {
@@ -517,20 +518,14 @@ __device__ __forceinline__ void wk_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// MT = row tiles of 128 per workgroup.  MT = 1: 4 MFMA waves (64 x 64 each) + 4 DMA waves, three LDS stages of 48 KB.
-// MT = 2 (round 4, C_out > 128): 256 x 128 tile, EIGHT MFMA waves -- two per SIMD, so one wave's fragment reads and barrier skew hide
-// under the other's MFMAs -- + 4 DMA waves, two stages of 72 KB.  What the stage costs the matrix pipe is its LDS WRITE traffic
-// (DESIGN 9.2), and a 128 x 128 tile writes 48 KB per 48 MFMAs of a wave; 256 x 128 writes 72 KB per 96 MFMAs of a SIMD: a quarter
-// less per MFMA, and half the barriers.
-template <int MT, bool KSP = false>
-__global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
-  static_assert(!KSP || MT == 1, "the k-split wave layout is a 128 x 128 tile");
-  constexpr int NMW = 4 * MT;                     // MFMA waves
-  constexpr int A_PLANE = MT * WK_PLANE;          // one plane of the dy operand
-  constexpr int A_OPND = 3 * A_PLANE;
-  constexpr int STAGE = A_OPND + WK_OPND;
-  constexpr int NST = MT == 1 ? 3 : 2;
-  constexpr int PA = WK_PIECES * MT, PB = WK_PIECES;      // 16-byte pieces per staging lane, operand and stage
+// 128 x 128 tile: 4 MFMA waves (64 x 64 each) + 4 DMA waves, three LDS stages of 48 KB.  (A 256 x 128 tile with eight MFMA waves
+// and two stages of 72 KB measured slower on every layer, C = 512 k7: 145 vs 163 TFLOP/s-eq, LSTM W_ih: 121 vs 135,
+// profiles/r04_wgrad_wide_tile.log: two stages expose the DMA latency that three hide.)
+template <bool KSP = false>
+__global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
+  constexpr int NMW = 4;                          // MFMA waves
+  constexpr int NST = WK_NST;
+  constexpr int PA = WK_PIECES, PB = WK_PIECES;   // 16-byte pieces per staging lane, operand and stage
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -548,7 +543,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
     by = r % a.gy;
     bz = r / a.gy;
   }
-  const int co0 = bx * 128 * MT;
+  const int co0 = bx * 128;
   const int gb0 = by * 4;
   const int z = bz;
   const int tile_lo = z * a.tiles_per_split;
@@ -564,8 +559,8 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
       const int blk = j * 4 + lw;                 // 1 KB block of the operand: 16 rows of one plane
-      const int plane = blk / (8 * MT);
-      const int row = (blk - plane * 8 * MT) * 16 + (lane >> 2);
+      const int plane = blk / 8;
+      const int row = (blk - plane * 8) * 16 + (lane >> 2);
       const int piece = (lane & 3) ^ ((row >> 2) & 3);      // the global piece that belongs in this lane's slot
       const int co = co0 + row < a.C_out ? co0 + row : a.C_out - 1;        // rows past C_out: computed, never stored
       a_off[j] = (unsigned)(plane * a.a_plane_bytes + ((long long)co * a.UA + 8 * piece) * 2);
@@ -590,8 +585,8 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
     // [0, 32 / 64 / 96) only) does not stage them: 18 / 12 / 6 of the stage's 48 KB stay in the L2s.  These launches are bound by the
     // traffic into LDS (32 real rows: 12 MFMAs per wave and 48 KB stage), not by the matrix pipe.  Block j of this wave is 16 rows
     // of one plane; which blocks it skips is wave-uniform, and so is the number n_a it issues per stage (0, 3 or 6).
-    int need_rows = 128 * MT;
-    if (MT == 1 && (a.narrow_rows & 2)) {
+    int need_rows = 128;
+    if (a.narrow_rows & 2) {
       const int real = a.C_out - co0;
       if (KSP) need_rows = real <= 64 ? 64 : (real <= 96 ? 96 : 128);        // (the k-split layout reads at least two row blocks)
       else need_rows = real <= 32 ? 32 : (real <= 64 ? 64 : (real <= 96 ? 96 : 128));
@@ -601,8 +596,8 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
       const int blk = j * 4 + lw;
-      const int plane = blk / (8 * MT);
-      need_a[j] = (blk - plane * 8 * MT) * 16 < need_rows;
+      const int plane = blk / 8;
+      need_a[j] = (blk - plane * 8) * 16 < need_rows;
       n_a += need_a[j] ? 1 : 0;
     }
     auto issue = [&](int chunk, int buf) {
@@ -611,13 +606,13 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
       const int t0 = (tile - b * a.n_tt) * WS_TT;
       const unsigned char* ab = a.ap + ((long long)b * a.C_out * a.UA + t0) * 2;                 // uniform
       const unsigned char* bb = a.bp + ((long long)b * a.C_in_real * s * a.UB + t0) * 2;        // uniform
-      unsigned char* st = sm + buf * STAGE;
+      unsigned char* st = sm + buf * WK_STAGE;
 #pragma unroll
       for (int j = 0; j < PA; ++j)
         if (need_a[j]) __builtin_amdgcn_global_load_lds((glb_void_t*)(ab + a_off[j]), (lds_void_t*)(st + (j * 4 + lw) * 1024), 16, 0, 0);
 #pragma unroll
       for (int j = 0; j < PB; ++j)
-        __builtin_amdgcn_global_load_lds((glb_void_t*)(bb + b_off[j]), (lds_void_t*)(st + A_OPND + (j * 4 + lw) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_void_t*)(bb + b_off[j]), (lds_void_t*)(st + WK_OPND + (j * 4 + lw) * 1024), 16, 0, 0);
     };
     // everything but the youngest stage's loads has landed (loads return in order)
     auto landed = [&](bool younger_in_flight) {
@@ -628,8 +623,8 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     issue(0, 0);
-    if (NST == 3 && n_chunks > 1) issue(1, 1);
-    landed(NST == 3 && n_chunks > 1);
+    if (n_chunks > 1) issue(1, 1);
+    landed(n_chunks > 1);
     wk_barrier();                                 // stage 0 visible to the MFMA waves
     for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
@@ -638,7 +633,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
         if (c < n_chunks) {
           // stage (c + NST - 1) % NST was read during iteration c - 1, which every wave has left
           if (c + NST - 1 < n_chunks) issue(c + NST - 1, (i + NST - 1) % NST);
-          if (c + 1 < n_chunks) landed(NST == 3 && c + 2 < n_chunks);
+          if (c + 1 < n_chunks) landed(c + 2 < n_chunks);
           wk_barrier();
         }
       }
@@ -672,7 +667,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
     const int sw = (l31 >> 2) & 3;
     const int po = ((kh * 2 + kq) ^ sw) * 16;
     const int aoff = ((CS ? 0 : wh * 64) + l31) * WK_ROWB + po;
-    const int boff = A_OPND + ((CS ? wh * 64 : 0) + l31) * WK_ROWB + po;
+    const int boff = WK_OPND + ((CS ? wh * 64 : 0) + l31) * WK_ROWB + po;
     f32x16 acc[MB][NB];
 #pragma unroll
     for (int m = 0; m < MB; ++m)
@@ -685,7 +680,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
     bf16x8 Ahi[2][MB], Bhi[2][NB], Amid[MB], Bmid[NB], Alo[MB], Blo[NB];
     auto rd_a = [&](const unsigned char* st, int plane, bf16x8 (&d)[MB]) {
 #pragma unroll
-      for (int m = 0; m < MB; ++m) d[m] = *reinterpret_cast<const bf16x8*>(st + aoff + plane * A_PLANE + m * 32 * WK_ROWB);
+      for (int m = 0; m < MB; ++m) d[m] = *reinterpret_cast<const bf16x8*>(st + aoff + plane * WK_PLANE + m * 32 * WK_ROWB);
     };
     auto rd_b = [&](const unsigned char* st, int plane, bf16x8 (&d)[NB]) {
 #pragma unroll
@@ -705,8 +700,8 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
       for (int i = 0; i < 6; ++i) {
         const int chunk = base + i;
         if (chunk < n_chunks) {
-          const unsigned char* st = sm + (i % 3) * STAGE;
-          const unsigned char* stn = sm + ((i + 1) % 3) * STAGE;
+          const unsigned char* st = sm + (i % 3) * WK_STAGE;
+          const unsigned char* stn = sm + ((i + 1) % 3) * WK_STAGE;
           const int cur = i & 1, nxt = cur ^ 1;
           rd_a(st, 1, Amid); rd_b(st, 1, Bmid);
           __builtin_amdgcn_sched_barrier(0);
@@ -771,132 +766,130 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
   const int mh = wave >> 1, nh = wave & 1;
   const int sw = (l31 >> 2) & 3;
   const int aoff = (mh * 64 + l31) * WK_ROWB;
-  const int boff = A_OPND + (nh * 64 + l31) * WK_ROWB;
+  const int boff = WK_OPND + (nh * 64 + l31) * WK_ROWB;
   int poff[WS_TT / 16];
 #pragma unroll
   for (int ks = 0; ks < WS_TT / 16; ++ks) poff[ks] = ((ks * 2 + kq) ^ sw) * 16;
 
-  if constexpr (MT == 1) {
-    // ---- at most 32 real output channels in this row tile (round 6: the multi-resolution discriminator's 32-channel stacks and
-    // the 1-channel output convs -- 75 + of the step's 227 weight gradients): three quarters of the 128 x 128 tile's MFMAs
-    // multiplied padding rows.  The four MFMA waves share the ONE real 32-row block and take 32 columns each (wave w: columns
-    // [32 w, 32 w + 32) of the tile): 24 MFMAs per 16-step slab instead of 96; the staging waves and the barrier protocol are
-    // untouched.  Two accumulators per wave (products 0 / 2 / 4 and 1 / 3 / 5) so that consecutive MFMAs do not depend on each other.
-    if (a.narrow_rows && a.C_out - co0 <= 32) {
-      const int aoff1 = l31 * WK_ROWB;
-      const int boff1 = A_OPND + (wave * 32 + l31) * WK_ROWB;
-      f32x16 acc_a, acc_b;
+  // ---- at most 32 real output channels in this row tile (round 6: the multi-resolution discriminator's 32-channel stacks and
+  // the 1-channel output convs -- 75 + of the step's 227 weight gradients): three quarters of the 128 x 128 tile's MFMAs
+  // multiplied padding rows.  The four MFMA waves share the ONE real 32-row block and take 32 columns each (wave w: columns
+  // [32 w, 32 w + 32) of the tile): 24 MFMAs per 16-step slab instead of 96; the staging waves and the barrier protocol are
+  // untouched.  Two accumulators per wave (products 0 / 2 / 4 and 1 / 3 / 5) so that consecutive MFMAs do not depend on each other.
+  if (a.narrow_rows && a.C_out - co0 <= 32) {
+    const int aoff1 = l31 * WK_ROWB;
+    const int boff1 = WK_OPND + (wave * 32 + l31) * WK_ROWB;
+    f32x16 acc_a, acc_b;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { acc_a[r] = 0.f; acc_b[r] = 0.f; }
-      bf16x8 A1[2][3], B1[2][3];
-      auto ld1 = [&](const unsigned char* st, int ks, bf16x8 (&Ad)[3], bf16x8 (&Bd)[3]) {
+    for (int r = 0; r < 16; ++r) { acc_a[r] = 0.f; acc_b[r] = 0.f; }
+    bf16x8 A1[2][3], B1[2][3];
+    auto ld1 = [&](const unsigned char* st, int ks, bf16x8 (&Ad)[3], bf16x8 (&Bd)[3]) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          Ad[p] = *reinterpret_cast<const bf16x8*>(st + aoff1 + p * A_PLANE + poff[ks]);
-          Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
-        }
-      };
-      wk_barrier();   // stage 0 staged
-      for (int base = 0; base < n_chunks; base += NST) {
+      for (int p = 0; p < 3; ++p) {
+        Ad[p] = *reinterpret_cast<const bf16x8*>(st + aoff1 + p * WK_PLANE + poff[ks]);
+        Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
+      }
+    };
+    wk_barrier();   // stage 0 staged
+    for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
-        for (int i = 0; i < NST; ++i) {
-          const int chunk = base + i;
-          if (chunk < n_chunks) {
-            const unsigned char* st = sm + i * STAGE;
-            ld1(st, 0, A1[0], B1[0]);
+      for (int i = 0; i < NST; ++i) {
+        const int chunk = base + i;
+        if (chunk < n_chunks) {
+          const unsigned char* st = sm + i * WK_STAGE;
+          ld1(st, 0, A1[0], B1[0]);
 #pragma unroll
-            for (int ks = 0; ks < WS_TT / 16; ++ks) {
-              if (ks + 1 < WS_TT / 16) ld1(st, ks + 1, A1[(ks + 1) & 1], B1[(ks + 1) & 1]);
-              __builtin_amdgcn_sched_barrier(0);
-              constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};     // smallest terms first
+          for (int ks = 0; ks < WS_TT / 16; ++ks) {
+            if (ks + 1 < WS_TT / 16) ld1(st, ks + 1, A1[(ks + 1) & 1], B1[(ks + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};     // smallest terms first
 #pragma unroll
-              for (int q = 0; q < 6; q += 2) {
-                acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][TA[q]], B1[ks & 1][TB[q]], acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][TA[q + 1]], B1[ks & 1][TB[q + 1]], acc_b, 0, 0, 0);
-              }
-              __builtin_amdgcn_sched_barrier(0);
+            for (int q = 0; q < 6; q += 2) {
+              acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][TA[q]], B1[ks & 1][TB[q]], acc_a, 0, 0, 0);
+              acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][TA[q + 1]], B1[ks & 1][TB[q + 1]], acc_b, 0, 0, 0);
             }
-            wk_barrier();
+            __builtin_amdgcn_sched_barrier(0);
           }
+          wk_barrier();
         }
       }
-      float* pz1 = a.part + (long long)z * a.C_out * a.NBk * 32;
-      const int gb = gb0 + wave;
-      if (gb < a.NBk) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int co = co0 + (r & 3) + 8 * (r >> 2) + 4 * kq;
-          if (co < a.C_out) pz1[((long long)co * a.NBk + gb) * 32 + l31] = acc_a[r] + acc_b[r];
-        }
-      }
-      return;
     }
-    // ---- 33 .. 96 real output channels (C = 64 / 96 layers, the second row tile of the C = 192 layers; round 6): the same column
-    // split with R = 2 / 3 row blocks per wave -- wave w: R x 32 rows x columns [32 w, 32 w + 32), 6 R MFMAs per 16-step slab
-    // instead of 24 of which a half / a quarter multiplied clamped duplicate rows.  One accumulator per (row block, column block)
-    // and the product order of the 64 x 64 layout: the same sums in the same order, bit for bit.
-    auto colsplit = [&](auto r_tag) {
-      constexpr int R = decltype(r_tag)::value;
-      const int aoff1 = l31 * WK_ROWB;
-      const int boff1 = A_OPND + (wave * 32 + l31) * WK_ROWB;
-      f32x16 accr[R];
+    float* pz1 = a.part + (long long)z * a.C_out * a.NBk * 32;
+    const int gb = gb0 + wave;
+    if (gb < a.NBk) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int co = co0 + (r & 3) + 8 * (r >> 2) + 4 * kq;
+        if (co < a.C_out) pz1[((long long)co * a.NBk + gb) * 32 + l31] = acc_a[r] + acc_b[r];
+      }
+    }
+    return;
+  }
+  // ---- 33 .. 96 real output channels (C = 64 / 96 layers, the second row tile of the C = 192 layers; round 6): the same column
+  // split with R = 2 / 3 row blocks per wave -- wave w: R x 32 rows x columns [32 w, 32 w + 32), 6 R MFMAs per 16-step slab
+  // instead of 24 of which a half / a quarter multiplied clamped duplicate rows.  One accumulator per (row block, column block)
+  // and the product order of the 64 x 64 layout: the same sums in the same order, bit for bit.
+  auto colsplit = [&](auto r_tag) {
+    constexpr int R = decltype(r_tag)::value;
+    const int aoff1 = l31 * WK_ROWB;
+    const int boff1 = WK_OPND + (wave * 32 + l31) * WK_ROWB;
+    f32x16 accr[R];
+#pragma unroll
+    for (int m = 0; m < R; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accr[m][r] = 0.f;
+    bf16x8 A1[2][R][3], B1[2][3];
+    auto ld1 = [&](const unsigned char* st, int ks, bf16x8 (&Ad)[R][3], bf16x8 (&Bd)[3]) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+#pragma unroll
+        for (int m = 0; m < R; ++m) Ad[m][p] = *reinterpret_cast<const bf16x8*>(st + aoff1 + p * WK_PLANE + m * 32 * WK_ROWB + poff[ks]);
+        Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
+      }
+    };
+    wk_barrier();   // stage 0 staged
+    for (int base = 0; base < n_chunks; base += NST) {
+#pragma unroll
+      for (int i = 0; i < NST; ++i) {
+        const int chunk = base + i;
+        if (chunk < n_chunks) {
+          const unsigned char* st = sm + i * WK_STAGE;
+          ld1(st, 0, A1[0], B1[0]);
+#pragma unroll
+          for (int ks = 0; ks < WS_TT / 16; ++ks) {
+            if (ks + 1 < WS_TT / 16) ld1(st, ks + 1, A1[(ks + 1) & 1], B1[(ks + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};     // smallest terms first
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+              for (int m = 0; m < R; ++m)
+                accr[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][m][TA[q]], B1[ks & 1][TB[q]], accr[m], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          wk_barrier();
+        }
+      }
+    }
+    float* pzr = a.part + (long long)z * a.C_out * a.NBk * 32;
+    const int gb = gb0 + wave;
+    if (gb < a.NBk) {
 #pragma unroll
       for (int m = 0; m < R; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) accr[m][r] = 0.f;
-      bf16x8 A1[2][R][3], B1[2][3];
-      auto ld1 = [&](const unsigned char* st, int ks, bf16x8 (&Ad)[R][3], bf16x8 (&Bd)[3]) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-          for (int m = 0; m < R; ++m) Ad[m][p] = *reinterpret_cast<const bf16x8*>(st + aoff1 + p * A_PLANE + m * 32 * WK_ROWB + poff[ks]);
-          Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
+        for (int r = 0; r < 16; ++r) {
+          const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq;
+          if (co < a.C_out) pzr[((long long)co * a.NBk + gb) * 32 + l31] = accr[m][r];
         }
-      };
-      wk_barrier();   // stage 0 staged
-      for (int base = 0; base < n_chunks; base += NST) {
-#pragma unroll
-        for (int i = 0; i < NST; ++i) {
-          const int chunk = base + i;
-          if (chunk < n_chunks) {
-            const unsigned char* st = sm + i * STAGE;
-            ld1(st, 0, A1[0], B1[0]);
-#pragma unroll
-            for (int ks = 0; ks < WS_TT / 16; ++ks) {
-              if (ks + 1 < WS_TT / 16) ld1(st, ks + 1, A1[(ks + 1) & 1], B1[(ks + 1) & 1]);
-              __builtin_amdgcn_sched_barrier(0);
-              constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};     // smallest terms first
-#pragma unroll
-              for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int m = 0; m < R; ++m)
-                  accr[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][m][TA[q]], B1[ks & 1][TB[q]], accr[m], 0, 0, 0);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            wk_barrier();
-          }
-        }
-      }
-      float* pzr = a.part + (long long)z * a.C_out * a.NBk * 32;
-      const int gb = gb0 + wave;
-      if (gb < a.NBk) {
-#pragma unroll
-        for (int m = 0; m < R; ++m)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq;
-            if (co < a.C_out) pzr[((long long)co * a.NBk + gb) * 32 + l31] = accr[m][r];
-          }
-      }
-    };
-    if (a.narrow_rows && a.C_out - co0 <= 64) {
-      colsplit(std::integral_constant<int, 2>());
-      return;
     }
-    if (a.narrow_rows && a.C_out - co0 <= 96) {
-      colsplit(std::integral_constant<int, 3>());
-      return;
-    }
+  };
+  if (a.narrow_rows && a.C_out - co0 <= 64) {
+    colsplit(std::integral_constant<int, 2>());
+    return;
+  }
+  if (a.narrow_rows && a.C_out - co0 <= 96) {
+    colsplit(std::integral_constant<int, 3>());
+    return;
   }
 
   f32x16 acc[2][2];
@@ -912,7 +905,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
     for (int p = 0; p < 3; ++p)
 #pragma unroll
       for (int m = 0; m < 2; ++m)
-        A[m][p] = *reinterpret_cast<const bf16x8*>(st + aoff + p * A_PLANE + m * 32 * WK_ROWB + poff[ks]);
+        A[m][p] = *reinterpret_cast<const bf16x8*>(st + aoff + p * WK_PLANE + m * 32 * WK_ROWB + poff[ks]);
   };
   auto ld_b = [&](const unsigned char* st, int ks, bf16x8 (&Bf)[2][3]) {
 #pragma unroll
@@ -923,24 +916,21 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
   };
 
   wk_barrier();   // stage 0 staged
-  // MT = 1: both operands' fragments are requested a step ahead (two register sets).  MT = 2 (three waves per SIMD: 168 registers):
-  // only the dy fragments are; the x fragments are requested at the start of their step and the sibling MFMA wave covers the wait.
-  constexpr int NBS = MT == 1 ? 2 : 1;
-  bf16x8 A[2][2][3], Bf[NBS][2][3];
+  // both operands' fragments are requested a step ahead (two register sets)
+  bf16x8 A[2][2][3], Bf[2][2][3];
   for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
     for (int i = 0; i < NST; ++i) {
       const int chunk = base + i;
       if (chunk < n_chunks) {
-        const unsigned char* st = sm + i * STAGE;
+        const unsigned char* st = sm + i * WK_STAGE;
         ld_a(st, 0, A[0]);
-        if (NBS == 2) ld_b(st, 0, Bf[0]);
+        ld_b(st, 0, Bf[0]);
 #pragma unroll
         for (int ks = 0; ks < WS_TT / 16; ++ks) {
-          if (NBS == 1) ld_b(st, ks, Bf[0]);
           if (ks + 1 < WS_TT / 16) {
             ld_a(st, ks + 1, A[(ks + 1) & 1]);
-            if (NBS == 2) ld_b(st, ks + 1, Bf[(ks + 1) & 1]);
+            ld_b(st, ks + 1, Bf[(ks + 1) & 1]);
           }
           __builtin_amdgcn_sched_barrier(0);
           constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};     // smallest terms first (see above)
@@ -950,7 +940,7 @@ __global__ __launch_bounds__((4 * MT + 4) * 64, MT == 1 ? 2 : 1) void conv1d_wgr
             for (int m = 0; m < 2; ++m)
 #pragma unroll
               for (int n = 0; n < 2; ++n)
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ks & 1][m][TA[q]], Bf[NBS == 2 ? (ks & 1) : 0][n][TB[q]], acc[m][n], 0, 0, 0);
+                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ks & 1][m][TA[q]], Bf[ks & 1][n][TB[q]], acc[m][n], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
         wk_barrier();
@@ -1003,8 +993,6 @@ __global__ __launch_bounds__(256) void wgrad_kmajor_reduce_kernel(const float* _
 // block of 32 lanes would hold one or two useful columns (the 1- and 2-channel input layers), where the kernel above is better.
 static int wk_geometry(int B, int C_in_real, int T_in, int C_out, int T_out, int K_total, int stride, int dil, int K1, int dil2,
                        WkArgs* a, int* splits) {
-  static const bool on = !(getenv("FAC_WGRAD_KMAJOR") && getenv("FAC_WGRAD_KMAJOR")[0] == '0');
-  if (!on) return -1;
   if (K1 <= 0 || K1 > K_total) K1 = K_total;
   if (K_total % K1 != 0) return -1;
   const int K2 = K_total / K1, K = K1, CV = C_in_real * K2;
@@ -1022,12 +1010,7 @@ static int wk_geometry(int B, int C_in_real, int T_in, int C_out, int T_out, int
   a->b_plane_bytes = (long long)B * C_in_real * stride * a->UB * 2;
   if (3 * a->a_plane_bytes >= (1ll << 32) || 3 * a->b_plane_bytes >= (1ll << 32)) return -1;     // 32-bit per-lane offsets
   const long long tiles = (long long)B * a->n_tt;
-  // measured SLOWER than the 128-row tile on every layer (C = 512 k7: 145 vs 163 TFLOP/s-eq, LSTM W_ih: 121 vs 135,
-  // profiles/r04_wgrad_wide_tile.log): two LDS stages expose the DMA latency that three stages hide, and that outweighs the
-  // quarter fewer LDS writes per MFMA.  Opt-in (FAC_WGRAD_WIDE=1).
-  static const bool wide_on = getenv("FAC_WGRAD_WIDE") && getenv("FAC_WGRAD_WIDE")[0] == '1';
-  a->MT = (wide_on && C_out > 128) ? 2 : 1;
-  const long long wgs = (long long)((C_out + 128 * a->MT - 1) / (128 * a->MT)) * ((a->NBk + 3) / 4);
+  const long long wgs = (long long)((C_out + 127) / 128) * ((a->NBk + 3) / 4);
   const long long per_split_bytes = (long long)C_out * a->NBk * 32 * 4;
   long long s_max = (2048 + wgs - 1) / wgs;
   if (s_max > tiles) s_max = tiles;
@@ -1155,38 +1138,32 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
                          pad_left, pad_mode, k.b_plane_bytes);
       static bool attr_set = false;
       if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
         attr_set = true;
       }
-      dim3 grid((C_out + 128 * k.MT - 1) / (128 * k.MT), (k.NBk + 3) / 4, S);
+      dim3 grid((C_out + 127) / 128, (k.NBk + 3) / 4, S);
       // Measured policy (profiles/r05_wgrad_xcd_ksplit.log, same box, B = 16 training shapes):
       //  * XCD-aware order when the launch has at least 5 (b, t) slices: +4 .. +20 % on the ResidualUnit / strided / transposed
       //    layers (each XCD then works on whole slices); with 2 - 4 slices (LSTM input projections, the 1024 -> 1536 conv at
       //    T = 160) an XCD gets a fraction of a slice and the plain order measured 3 - 9 % faster;
       //  * k-split wave layout for the k = 7 stride-1 layers whose slice is at most one round of workgroups: +2 .. +5 % there,
       //    -2 .. -8 % on 1-tap / strided / wide layers (their loops are short: the end-of-loop exchange shows).
-      static const int xcd_env = [] { const char* e = getenv("FAC_WGRAD_XCD"); return e == nullptr ? -1 : (e[0] != '0' ? 1 : 0); }();
-      static const int ksp_env = [] { const char* e = getenv("FAC_WGRAD_KSPLIT"); return e == nullptr ? -1 : (e[0] != '0' ? 1 : 0); }();
-      const bool xcd_order = xcd_env >= 0 ? xcd_env == 1 : S >= 5;
-      const bool ksplit = k.MT == 1 && (ksp_env >= 0 ? ksp_env == 1
-                                                     : (k.K == 7 && k.K2 == 1 && stride == 1 && (long long)grid.x * grid.y <= 256 && S >= 4));
+      const bool xcd_order = S >= 5;
+      const bool ksplit = k.K == 7 && k.K2 == 1 && stride == 1 && (long long)grid.x * grid.y <= 256 && S >= 4;
+      // FAC_WGRAD_NARROW=0 (a child process of tests/test_wgrad_split.py): the 64 x 64 layout on duplicate rows, the bit-identity reference
       static const bool narrow_on = !(getenv("FAC_WGRAD_NARROW") && getenv("FAC_WGRAD_NARROW")[0] == '0');
-      static const bool skip_dup = !(getenv("FAC_WGRAD_SKIP_DUP") && getenv("FAC_WGRAD_SKIP_DUP")[0] == '0');
-      k.narrow_rows = narrow_on ? (skip_dup ? 3 : 1) : 0;      // bit 0: column-split layouts; bit 1: their duplicate rows are not staged
+      k.narrow_rows = narrow_on ? 3 : 0;      // bit 0: column-split layouts; bit 1: their duplicate rows are not staged
       k.gx = (int)grid.x; k.gy = (int)grid.y; k.gz = (int)grid.z; k.per_xcd = 0;
       if (xcd_order) {
         const long long total = (long long)grid.x * grid.y * grid.z;
         k.per_xcd = (int)((total + 7) / 8);
         grid = dim3((unsigned)(8 * k.per_xcd), 1, 1);
       }
-      if (k.MT == 2) hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<2>, grid, dim3(768), (size_t)2 * (3 * 2 * WK_PLANE + WK_OPND), st, k);
-      else if (ksplit) hipLaunchKernelGGL((conv1d_wgrad_kmajor_kernel<1, true>), grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
-      else hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<1>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
+      if (ksplit) hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<true>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
+      else hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<false>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
       const long long n = (long long)C_out * k.NBk * 32;
       const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
       hipLaunchKernelGGL(wgrad_kmajor_reduce_kernel, dim3(blocks), dim3(256), 0, st, k.part, dw, S, C_out, k.NBk, k.K, k.CV);

@@ -14,7 +14,7 @@
 //     "finished step t" into flags[i]; a waiter reads all flags with ONE wave-wide sc1 load per poll (no read-modify-write,
 //     nothing serialises on a counter) and then reads h_t with plain loads -- no XCD can hold an older copy of lines that
 //     did not exist before.  No buffer_wbl2 / buffer_inv on the step path: the memory-model fences of a textbook grid
-//     barrier measured 25-92 us per step on this part (exchange modes below).  The flags hold epoch + step;
+//     barrier measured 25-92 us per step on this part.  The flags hold epoch + step;
 //     the epoch advances by T per launch (last workgroup out), so a replayed hipGraph needs no host-side reset.  A
 //     waiter that sees no progress for ~4 s traps (loud launch failure) instead of hanging the queue.
 // Requirements (fac_lstm_persist_ok): H a multiple of 256 with H/64 in {8, 16, 24}, B <= 32, H/8 <= CUs of the device,
@@ -62,14 +62,12 @@ constexpr long long LSTM_SPIN_LIMIT = 400000000ll;   // wall_clock64 ticks (100 
 __device__ unsigned g_lstm_abort;
 __device__ unsigned* g_lstm_host_timeouts;
 
-// wave 0: wait until flags[first .. first+count) have all reached `target`; then the workgroup passes a barrier (mode 0
-// only: and every wave takes an agent-scope acquire that drops stale L1 / L2 lines of the exchanged buffers).
-// Exchange modes.  0: cache maintenance (buffer_wbl2 / buffer_inv) around plain accesses.  1: every exchanged word moves with
-// agent-scope (sc1) stores and loads, ordered by s_waitcnt only -- no L2 write-back / invalidate per step, but every
-// workgroup's copy of h_t comes from the memory side.  2: sc1 stores into a FRESH region per step, each workgroup writing
-// whole cache lines of its own; the consumers read with plain loads: no XCD can hold an older copy of a line that did
-// not exist before, so the first reader of an XCD misses to memory and the other 23 workgroups of that XCD hit its L2.
-__device__ __forceinline__ void wait_flags(const unsigned* flags, int first, int count, unsigned target, int mode) {
+// wave 0: wait until flags[first .. first+count) have all reached `target`; then the workgroup passes a barrier.
+// The exchange: sc1 stores into a FRESH region per step, each workgroup writing whole cache lines of its own; the consumers
+// read with plain loads: no XCD can hold an older copy of a line that did not exist before, so the first reader of an XCD
+// misses to memory and the other 23 workgroups of that XCD hit its L2.  (Cache maintenance around plain accesses, and sc1
+// loads of a double buffer, were the two slower forms: DESIGN 3.2.)
+__device__ __forceinline__ void wait_flags(const unsigned* flags, int first, int count, unsigned target) {
   if ((threadIdx.x >> 6) == 0) {
     const int lane = threadIdx.x & 63;
     const long long t0 = wall_clock64();
@@ -102,28 +100,16 @@ __device__ __forceinline__ void wait_flags(const unsigned* flags, int first, int
     }
   }
   __syncthreads();
-  if (mode == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
-__device__ __forceinline__ f32x4 load_agent_x4(const f32x4* p) {
-  f32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
 __device__ __forceinline__ void store_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float load_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// the stores of this workgroup (issued by threads tid < n_store, a multiple of 64) become visible device-wide, then flag
-__device__ __forceinline__ void publish_flag(unsigned* flag, unsigned value, int n_store, int mode) {
-  if (mode == 0) {
-    if ((int)threadIdx.x < n_store) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the write-through (sc1) stores of this wave are acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+// the stores of this workgroup become visible device-wide, then flag
+__device__ __forceinline__ void publish_flag(unsigned* flag, unsigned value) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the write-through (sc1) stores of this wave are acknowledged
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __device__ __forceinline__ unsigned launch_epoch(LstmSync* sync, unsigned* s_base) {
@@ -145,7 +131,7 @@ __device__ __forceinline__ void leave_launch(LstmSync* sync, unsigned base, unsi
 
 // Contraction index <-> hidden unit.  Within every 16 units, unit 8p + e sits at k = 4*(e>>1) + 2p + (e&1): the 8 units a
 // workgroup produces per step then fill, for all 16 columns, the float4s of 32 consecutive lanes of one fragment block --
-// 512 contiguous bytes = four whole 128-byte lines that no other workgroup writes (mode 2 relies on this).
+// 512 contiguous bytes = four whole 128-byte lines that no other workgroup writes (the exchange relies on this).
 __host__ __device__ __forceinline__ int k_of_unit(int unit) {
   const int u16 = unit & 15, p = u16 >> 3, e = u16 & 7;
   return (unit & ~15) + ((e >> 1) << 2) + 2 * p + (e & 1);
@@ -170,7 +156,7 @@ __device__ __forceinline__ long long frag_index(int unit, int col, int H, int KS
 // partial results of the workgroup meet in `red`.
 template <int KS, int NCB>
 __device__ __forceinline__ void wave_product(const float4 (&a4)[KS / 2], const float* frag, int wave, int lane,
-                                             float (*red)[32][NCB * 16 + 1], int mode) {
+                                             float (*red)[32][NCB * 16 + 1]) {
   f32x4 acc[2][NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
@@ -184,15 +170,8 @@ __device__ __forceinline__ void wave_product(const float4 (&a4)[KS / 2], const f
   for (int cb = 0; cb < NCB; ++cb) {
     const f32x4* bp = reinterpret_cast<const f32x4*>(frag) + ((long long)(cb * 16 + wave) * (KS / 4)) * 64 + lane;
     f32x4 b4[KS / 4];
-    if (mode != 1) {
 #pragma unroll
-      for (int j = 0; j < KS / 4; ++j) b4[j] = bp[(long long)j * 64];
-    } else {
-#pragma unroll
-      for (int j = 0; j < KS / 4; ++j) b4[j] = load_agent_x4(bp + (long long)j * 64);
-#pragma unroll
-      for (int j = 0; j < KS / 4; ++j) asm volatile("s_waitcnt vmcnt(0)" : "+v"(b4[j])::"memory");
-    }
+    for (int j = 0; j < KS / 4; ++j) b4[j] = bp[(long long)j * 64];
 #pragma unroll
     for (int j = 0; j < KS / 4; ++j) {
       const float bv[4] = {b4[j][0], b4[j][1], b4[j][2], b4[j][3]};
@@ -225,7 +204,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
                                                                 float* __restrict__ yT,            // (H, T, BP)
                                                                 float* __restrict__ save_g,        // (4H, T, BP) or null
                                                                 float* __restrict__ save_c,        // (H, T, BP) or null
-                                                                int slot, int T, int H, int BP, int mode) {
+                                                                int slot, int T, int H, int BP) {
   constexpr int NC = NCB * 16;
   __shared__ float red[16][32][NC + 1];
   __shared__ unsigned s_base;
@@ -257,8 +236,8 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
   for (int t = 0; t < T; ++t) {
     float gate[4] = {pre_v[0], pre_v[1], pre_v[2], pre_v[3]};
     if (t > 0) {
-      wait_flags(sync->flags, 0, nwg, base + (unsigned)t, mode);  // every workgroup has published h_{t-1}
-      wave_product<KS, NCB>(a4, hfrag + (mode == 2 ? t - 1 : (t - 1) & 1) * hbuf, wave, lane, red, mode);
+      wait_flags(sync->flags, 0, nwg, base + (unsigned)t);  // every workgroup has published h_{t-1}
+      wave_product<KS, NCB>(a4, hfrag + (t - 1) * hbuf, wave, lane, red);
       __syncthreads();
       if (gate_thread) {
 #pragma unroll
@@ -278,7 +257,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
       const float c_new = __fadd_rn(__fmul_rn(fg, c_reg), __fmul_rn(ig, gg));
       c_reg = c_new;
       const float hv = __fmul_rn(og, tanhf(c_new));
-      if (t + 1 < T) store_agent(hfrag + (mode == 2 ? t : t & 1) * hbuf + hpos, hv);   // first: its write-through is the critical path
+      if (t + 1 < T) store_agent(hfrag + t * hbuf + hpos, hv);   // first: its write-through is the critical path
       const long long o = (long long)unit * rs + (long long)t * BP + col;
       yT[o] = hv;
       if (save_g != nullptr) {
@@ -290,7 +269,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
       }
     }
     if (t + 1 < T) {
-      publish_flag(sync->flags + ub, base + (unsigned)t + 1u, 8 * NC, mode);
+      publish_flag(sync->flags + ub, base + (unsigned)t + 1u);
       if (gate_thread) {      // next step's gate pre-activations arrive while the flags are polled
 #pragma unroll
         for (int q = 0; q < 4; ++q) pre_v[q] = pre[(long long)(q * H + unit) * rs + (long long)(t + 1) * BP + col];
@@ -312,7 +291,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
 //   state     h_t crosses the device ALREADY split, in B-fragment order: hs[t][plane][k/16][lane] 16-byte pieces, lane =
 //             32*((k%16)/8) + column, piece = 8 consecutive k.  The 8 units of a workgroup are exactly one piece per column:
 //             per plane it writes 32 lanes x 16 B = 512 contiguous bytes = four whole 128-byte lines of a FRESH region per
-//             step that nobody else writes (exchange mode 2 above; the only mode of this kernel), by write-through stores.
+//             step that nobody else writes (the exchange above), by write-through stores.
 //             Consumers read their 3*NK pieces per lane with plain 16-byte loads through a 4-step register window.
 typedef __bf16 ls_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float ls_f32x16 __attribute__((ext_vector_type(16)));
@@ -414,7 +393,7 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
   for (int t = 0; t < T; ++t) {
     float gate[4] = {pre_v[0], pre_v[1], pre_v[2], pre_v[3]};
     if (t > 0) {
-      wait_flags(sync->flags, 0, nwg, base + (unsigned)t, 2);   // every workgroup has published h_{t-1}
+      wait_flags(sync->flags, 0, nwg, base + (unsigned)t);   // every workgroup has published h_{t-1}
       {
         // The pieces of step s are requested WIN steps ahead.  hipcc sinks plain loads down to their first use (one memory round
         // trip per step), so the loads and their waits are explicit: in-order return, s_waitcnt vmcnt(n) with n = the loads issued
@@ -486,7 +465,7 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
     }
     if (gate_thread) yT[(long long)unit * rs + (long long)t * BP + col] = hv;
     if (t + 1 < T) {
-      publish_flag(sync->flags + ub, base + (unsigned)t + 1u, 128, 2);
+      publish_flag(sync->flags + ub, base + (unsigned)t + 1u);
       if (gate_thread) {      // next step's gate pre-activations arrive while the flags are polled
 #pragma unroll
         for (int q = 0; q < 4; ++q) pre_v[q] = pre[(long long)(q * H + unit) * rs + (long long)(t + 1) * BP + col];
@@ -509,7 +488,7 @@ __global__ __launch_bounds__(1024) void lstm_bwd_persist_kernel(const float* __r
                                                                 float* __restrict__ dgates,        // (4H, T, BP) out
                                                                 float* partial,                    // (4, H, NC)
                                                                 float* dgfrag,                     // T x 4 x H*NC, fragment order
-                                                                int slot, int T, int H, int BP, int mode) {
+                                                                int slot, int T, int H, int BP) {
   constexpr int NC = NCB * 16;
   __shared__ float red[16][32][NC + 1];
   __shared__ unsigned s_base;
@@ -549,8 +528,8 @@ __global__ __launch_bounds__(1024) void lstm_bwd_persist_kernel(const float* __r
       dh = dyT[o];
     }
     if (n > 0) {
-      wait_flags(sync->flags2, 0, nwg, base + (unsigned)n, mode);   // dgates_{t+1} of every unit is published
-      wave_product<KS, NCB>(a4, dgfrag + (mode == 2 ? n - 1 : (n - 1) & 1) * 4 * hbuf + q * hbuf, wave, lane, red, mode);
+      wait_flags(sync->flags2, 0, nwg, base + (unsigned)n);   // dgates_{t+1} of every unit is published
+      wave_product<KS, NCB>(a4, dgfrag + (n - 1) * 4 * hbuf + q * hbuf, wave, lane, red);
       __syncthreads();
       for (int e = tid; e < 32 * NC; e += 1024) {
         const int row = e / NC, c = e - row * NC;
@@ -559,8 +538,8 @@ __global__ __launch_bounds__(1024) void lstm_bwd_persist_kernel(const float* __r
         for (int w = 0; w < 16; ++w) s += red[w][row][c];
         store_agent(partial + (long long)q * hbuf + (long long)(ub * 32 + row) * NC + c, s);
       }
-      publish_flag(sync->flags + wg, base + (unsigned)n, 1024, mode);
-      wait_flags(sync->flags, ub * 4, 4, base + (unsigned)n, mode);   // the four quarter sums of this unit block
+      publish_flag(sync->flags + wg, base + (unsigned)n);
+      wait_flags(sync->flags, ub * 4, 4, base + (unsigned)n);   // the four quarter sums of this unit block
       if (gate_thread) {
         const float* pp = partial + (long long)unit * NC + col;
         dh += ((load_agent(pp) + load_agent(pp + hbuf)) + (load_agent(pp + 2 * hbuf) + load_agent(pp + 3 * hbuf)));
@@ -578,12 +557,12 @@ __global__ __launch_bounds__(1024) void lstm_bwd_persist_kernel(const float* __r
       dg[3] = d_o * og * (1.f - og);
       if (n + 1 < T) {      // first: their write-through is the critical path
 #pragma unroll
-        for (int g = 0; g < 4; ++g) store_agent(dgfrag + (mode == 2 ? n : n & 1) * 4 * hbuf + g * hbuf + hpos, dg[g]);
+        for (int g = 0; g < 4; ++g) store_agent(dgfrag + n * 4 * hbuf + g * hbuf + hpos, dg[g]);
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) dgates[(long long)g * H * rs + o] = dg[g];
     }
-    if (n + 1 < T) publish_flag(sync->flags2 + wg, base + (unsigned)n + 1u, 8 * NC, mode);
+    if (n + 1 < T) publish_flag(sync->flags2 + wg, base + (unsigned)n + 1u);
   }
   leave_launch(sync, base, (unsigned)T, (unsigned)nwg);
 }
@@ -742,16 +721,6 @@ __global__ void mask_flags_if_kernel(float* flags, int n, const float* poison) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) flags[i] = 0.f;
 }
 
-// FAC_LSTM_EXCHANGE = fence (mode 0) | sc1 (mode 1) | fresh (mode 2, default)
-static int exchange_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("FAC_LSTM_EXCHANGE");
-    mode = e == nullptr ? 2 : (e[0] == 'f' && e[1] == 'e') ? 0 : e[0] == 's' ? 1 : 2;
-  }
-  return mode;
-}
-
 static bool persist_shape_ok(int H, int B) {
   if (H <= 0 || H % 256 != 0 || B <= 0 || B > 32) return false;
   const int ks = H / 64;
@@ -766,8 +735,8 @@ static bool persist_split_shape_ok(int H, int B) {
   return wgs <= LSTM_MAX_WG && wgs <= device_cus();
 }
 
-using FwdKern = void (*)(const float*, const float*, float*, float*, float*, float*, int, int, int, int, int);
-using BwdKern = void (*)(const float*, const float*, const float*, const float*, float*, float*, float*, int, int, int, int, int);
+using FwdKern = void (*)(const float*, const float*, float*, float*, float*, float*, int, int, int, int);
+using BwdKern = void (*)(const float*, const float*, const float*, const float*, float*, float*, float*, int, int, int, int);
 using SplitKern = void (*)(const float*, const ls_bf16x8*, ls_bf16x8*, float*, int, int, int, int);
 
 static FwdKern fwd_kernel_for(int H, int B) {
@@ -921,8 +890,7 @@ extern "C" int fac_lstm_layer_fwd_persist(const float* pre, const float* whh16, 
   {
     ResidentLaunch order((hipStream_t)stream);
     arm_timeout_word((hipStream_t)stream);
-    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(1024), 0, (hipStream_t)stream, pre, whh16, hfrag, yT, gates_save, c_save, slot, T, H, BP,
-                       exchange_mode());
+    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(1024), 0, (hipStream_t)stream, pre, whh16, hfrag, yT, gates_save, c_save, slot, T, H, BP);
     rc = check_launch("lstm_layer_fwd_persist");
   }
   return rc;
@@ -949,8 +917,7 @@ extern "C" int fac_lstm_layer_bwd_persist(const float* dyT, const float* whh16t,
   {
     ResidentLaunch order((hipStream_t)stream);
     arm_timeout_word((hipStream_t)stream);
-    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(1024), 0, (hipStream_t)stream, dyT, whh16t, gates, cs, dgates, partial, dgfrag, slot, T, H, BP,
-                       exchange_mode());
+    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(1024), 0, (hipStream_t)stream, dyT, whh16t, gates, cs, dgates, partial, dgfrag, slot, T, H, BP);
     rc = check_launch("lstm_layer_bwd_persist");
   }
   return rc;

@@ -7,7 +7,6 @@ Reference counterparts: dac/model/encodec.py (SConv1d :192-228, SConvTranspose1d
 SLSTM :272-288, NormConv1d :125-139), dac/nn/layers.py (Snake1d :27-33, WNConv1d :9-10).
 """
 import math
-import os
 
 import torch
 from torch import nn
@@ -111,9 +110,8 @@ class _Norm(nn.Module):
 
 
 # Short clips through the split GEMM kernel as one flattened signal (SConv1d._run_flat, SConvTranspose1d.run): inference only.
-FLAT_SHORT_CLIPS = os.environ.get("FAC_FLAT_SHORT", "1") != "0"
-PW_TAILS_TO_384 = os.environ.get("FAC_PW_TAILS_384", "1") != "0"
-FLAT_STRIDE1 = os.environ.get("FAC_FLAT_STRIDE1", "1") != "0"      # wide stride-1 k = 7 convs on short clips (SConv1d._run_flat_stride1)
+FLAT_SHORT_CLIPS = True
+FLAT_STRIDE1 = True      # wide stride-1 k = 7 convs on short clips (SConv1d._run_flat_stride1)
 
 
 class SConv1d(nn.Module):
@@ -141,7 +139,7 @@ class SConv1d(nn.Module):
             split = w.packed_split()
         elif (self.kernel_size == 1 and self.stride == 1 and alpha_in is None
               and ops.gemm_split_ok(w.c_out, w.c_in, 1, x.shape[0] * x.shape[-1])
-              and not (PW_TAILS_TO_384 and w.c_in == w.c_out and w.c_in in (256, 384) and x.shape[0] * x.shape[-1] >= 65536)):
+              and not (w.c_in == w.c_out and w.c_in in (256, 384) and x.shape[0] * x.shape[-1] >= 65536)):
             # (the C = 256 / 384 ResidualUnit tails stay on the streaming k = 1 kernel: -0.7 ms per B = 32 forward, round 4)
             split = w.packed_split()          # 1x1 with many channels: split-bf16 GEMM (conv1d_gemm_split.hip)
         elif (self.stride == 2 and alpha_in is None and alpha_out is None and res is None and act == ops.ACT_NONE and self.dilation == 1

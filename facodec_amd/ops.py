@@ -25,23 +25,19 @@ def cin_pad(c):
 # torch.cuda.current_stream() builds a Stream object through five layers of Python (7 us per call, 11 000 calls = 40 ms of host time
 # per train step: tools/tune/host_profile.py, round 6); the raw handle is one C call.  Same value: the current stream of the
 # current device, side-stream contexts included.
-_SLOW_STREAM = os.environ.get("FAC_SLOW_STREAM") == "1"           # A/B switch: torch.cuda.current_stream() as in rounds 1-5
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _GET_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
 
 
 def _raw_stream(device_index=None):
     """The current HIP stream of the (current) device as an integer handle."""
-    if _RAW_STREAM is not None and _GET_DEVICE is not None and not _SLOW_STREAM:
+    if _RAW_STREAM is not None and _GET_DEVICE is not None:
         return _RAW_STREAM(_GET_DEVICE() if device_index is None else device_index)
     return torch.cuda.current_stream(device_index).cuda_stream
 
 
 def _stream():
     return C.c_void_p(_raw_stream())
-
-
-_SYNC_H2D = os.environ.get("FAC_SYNC_H2D") == "1"        # A/B switch: the blocking copies of rounds 1-5
 
 
 def h2d(t, device, dtype=None):
@@ -54,7 +50,7 @@ def h2d(t, device, dtype=None):
         return t if dtype is None or t.dtype == dtype else t.to(dtype)
     if dtype is not None and t.dtype != dtype:
         t = t.to(dtype)
-    if torch.device(device).type != "cuda" or _SYNC_H2D:
+    if torch.device(device).type != "cuda":
         return t.to(device)
     staged = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
     staged.copy_(t)
@@ -123,8 +119,8 @@ def pack_convtr_weight(v, g, stride, out=None):
 
 # All-phases-per-workgroup launch of the causal ConvTranspose1d (fac_conv_desc.row_phases): contiguous stores through the
 # LDS epilogue instead of `stride` interleaved strided streams (2.9x the algorithmic HBM traffic).  Needs the 256-column
-# tile, so it takes over from CONVTR_ROWS_MIN_T input columns; FAC_CONVTR_ROWS=0 keeps the polyphase launch everywhere.
-CONVTR_ROWS = os.environ.get("FAC_CONVTR_ROWS", "0") != "0"
+# tile, so it takes over from CONVTR_ROWS_MIN_T input columns; CONVTR_ROWS = False keeps the polyphase launch everywhere.
+CONVTR_ROWS = False
 CONVTR_ROWS_MIN_T = 512
 
 
@@ -155,7 +151,7 @@ def pack_convtr_weight_rows(v, g, stride, out=None):
 
 def convtr_split_ok(c_in, c_out, stride, batch, t_in, causal=True, alpha_in=None):
     """All-phases ConvTranspose1d on the split-bf16 GEMM kernel (conv1d_gemm_split.hip, K = 2): mirrors conv_gsplit_ok."""
-    return (BF16_SPLIT and GEMM_SPLIT and causal and alpha_in is None and 2 <= stride <= 16 and c_in >= 64
+    return (BF16_SPLIT and causal and alpha_in is None and 2 <= stride <= 16 and c_in >= 64
             and t_in >= 256 and batch * t_in >= 1024 and c_out * stride >= 64)
 
 
@@ -258,8 +254,8 @@ class flop_scale:
         _FLOP_SCALE = self.prev
 
 # k = 7 convs on the bf16 matrix pipe with fp32-grade operand splitting (conv1d_bsplit.hip).  Results have
-# fp32-MFMA-grade error; FAC_BF16_SPLIT=0 keeps every conv on the fp32 MFMA kernel.
-BF16_SPLIT = os.environ.get("FAC_BF16_SPLIT", "1") != "0"
+# fp32-MFMA-grade error; BF16_SPLIT = False keeps every conv on the fp32 MFMA kernel.
+BF16_SPLIT = True
 
 
 def set_conv_profile(p):
@@ -402,15 +398,14 @@ def _launch_conv(d, what):
     _PROFILE.records.append((buf.value.decode(), flops, e0, e1))
 
 
-# 1- / 2-tap convs as split-bf16 GEMMs (conv1d_gemm_split.hip): policy of who packs the GEMM layout.  FAC_GEMM_SPLIT=0 off.
-GEMM_SPLIT = os.environ.get("FAC_GEMM_SPLIT", "1") != "0"
-GEMM_SPLIT_MIN_CIN = int(os.environ.get("FAC_GEMM_SPLIT_MIN_CIN", "256"))
+# 1- / 2-tap convs as split-bf16 GEMMs (conv1d_gemm_split.hip): policy of who packs the GEMM layout.
+GEMM_SPLIT_MIN_CIN = 256
 
 
 def gemm_split_ok(c_out, c_in, k, n_cols, t_out=None):
     """1- / 2-tap stride-1 conv worth the bf16 pipe: many input channels (below ~256 the k = 1 layers are HBM-bound and the
     streaming kernel conv1d_pw.hip is the right tool), at least half a row tile, enough columns."""
-    if not (BF16_SPLIT and GEMM_SPLIT and k in (1, 2)):
+    if not (BF16_SPLIT and k in (1, 2)):
         return False
     if c_in < GEMM_SPLIT_MIN_CIN or c_out < 64 or n_cols < 1024:
         return False
@@ -420,7 +415,7 @@ def gemm_split_ok(c_out, c_in, k, n_cols, t_out=None):
 def gemm_split_strided_ok(c_out, c_in, k, stride, batch, t_out):
     """Strided conv with stride < k <= 2 * stride (the encoder's k = 2 s downsampling convs, the period discriminators' k = 5
     stride-3 convs) as a 2-tap split GEMM over the `stride` phase sub-signals: mirrors conv_gsplit_ok."""
-    return (BF16_SPLIT and GEMM_SPLIT and 1 < stride <= 16 and stride < k <= 2 * stride and c_in >= 32
+    return (BF16_SPLIT and 1 < stride <= 16 and stride < k <= 2 * stride and c_in >= 32
             and c_out >= 64 and t_out >= 256 and batch * t_out >= 1024)
 
 
@@ -460,14 +455,13 @@ def pack_gemm_weight_split_t(w, out=None):
     return out
 
 
-BSPLIT2 = os.environ.get("FAC_BSPLIT2", "1") != "0"
 
 
 def split2_ok(c_out, k, k1, stride, n_cols):
     """Few-output-channel 9- / 3-tap conv (plain or two-level, taps per level k1) for conv1d_bsplit2.hip: mirrors
     conv_bsplit2_ok."""
     kv = k1 if 0 < k1 < k else k
-    return (BF16_SPLIT and BSPLIT2 and 8 <= c_out <= 32 and ((kv == 9 and stride in (1, 2)) or (kv == 3 and stride == 1))
+    return (BF16_SPLIT and 8 <= c_out <= 32 and ((kv == 9 and stride in (1, 2)) or (kv == 3 and stride == 1))
             and n_cols >= 4096)
 
 
@@ -572,7 +566,7 @@ def to_p8(x, alpha=None):
 # pays for the pass when the input is small next to the GEMM -- the LSTM input projections, the transposed convs with many output
 # rows per input sample, the last two strided convs of the encoder (threshold sweep 150 / 300 / 450 / 700 on one box: 56.3 / 56.0 /
 # 55.5 / 56.0 ms per forward).  0 disables.
-P8_PREPASS_MIN_FLOP_PER_BYTE = float(os.environ.get("FAC_P8_PREPASS", "450"))
+P8_PREPASS_MIN_FLOP_PER_BYTE = 450.0
 
 
 def p8_prepass(x, flop_per_in_byte):
@@ -648,9 +642,9 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
     return (out, y2) if alpha_y2 is not None else out
 
 
-# Streaming hops: the WaveNet's elementwise launches folded into the reduction kernels of its convs (FAC_STREAM_FOLD=0: separate
+# Streaming hops: the WaveNet's elementwise launches folded into the reduction kernels of its convs (STREAM_FOLD = False: separate
 # launches, the round-5 hop; bit-identical either way -- tests/test_gpu_parity.py::test_streaming_folded_epilogues_are_bit_identical)
-STREAM_FOLD = os.environ.get("FAC_STREAM_FOLD", "1") != "0"
+STREAM_FOLD = True
 SKINNY_MAX_COLS = 640
 
 
@@ -715,7 +709,7 @@ def conv_transpose1d(x, w_packed, c_out, stride, bias=None, alpha_in=None, out=N
 # the same trick for the TRAINING launches (round 6).  Per-clip column tiles of that kernel would be half empty at the 160-frame
 # latent rate, so those launches (the encoder's last downsampling conv, the decoder's first ConvTranspose1d, and their data
 # gradients) fell to the fp32 128 x 160 tile at 38 - 63 TFLOP/s (profiles/r06_train_layers_serial.log: 3.9 ms per step).
-FLAT_TRAIN = os.environ.get("FAC_FLAT_TRAIN", "1") != "0"
+FLAT_TRAIN = True
 # k = 1 ResidualUnit tails at C = 64 .. 384 on the bf16 pipe inside the streaming kernel (conv1d_pw_split.hip); 0: fp32 MFMAs (rounds 2-5)
 PW_SPLIT = os.environ.get("FAC_PW_SPLIT", "1") != "0"
 
@@ -727,7 +721,7 @@ def pw_split_tail_ok(c_in, c_out, cols):
 
 
 # stride-2 layers with few channels on the streaming kernel with taps (conv1d_pw_split.hip, conv1d_pwt_kernel); follows PW_SPLIT
-PW_TAPS = os.environ.get("FAC_PW_TAPS", "1") != "0"
+PW_TAPS = True
 
 
 def pw_taps_ok(c_in, c_out, k, stride, transposed, batch, t_out):
@@ -818,8 +812,8 @@ def pack_lstm_whh(w_hh, out=None):
     return out
 
 
-LSTM_PERSIST = os.environ.get("FAC_LSTM_PERSIST", "1") != "0"
-LSTM_PERSIST_MAX_BATCH = int(os.environ.get("FAC_LSTM_PERSIST_MAX_BATCH", "16"))
+LSTM_PERSIST = True
+LSTM_PERSIST_MAX_BATCH = 16
 
 
 _LSTM_ARMED = set()
@@ -865,8 +859,8 @@ def lstm_persist_ok(H, batch):
             and bool(_lib.load().fac_lstm_persist_stream_ok(_stream())))
 
 
-LSTM_PERSIST_SPLIT = os.environ.get("FAC_LSTM_PERSIST_SPLIT", "1") != "0"
-LSTM_PERSIST_SPLIT_MIN_BATCH = int(os.environ.get("FAC_LSTM_PERSIST_SPLIT_MIN_BATCH", "17"))
+LSTM_PERSIST_SPLIT = True
+LSTM_PERSIST_SPLIT_MIN_BATCH = 17
 
 
 LSTM_PERSIST_SPLIT_MAX_SCRATCH = int(float(os.environ.get("FAC_LSTM_PERSIST_SPLIT_MAX_SCRATCH_GB", "1")) * 2 ** 30)
@@ -875,7 +869,7 @@ LSTM_PERSIST_SPLIT_MAX_SCRATCH = int(float(os.environ.get("FAC_LSTM_PERSIST_SPLI
 def lstm_persist_split_ok(H, batch, T=None):
     """True when an inference layer runs on the resident kernel with bf16 x 3 operands (lstm_persist.hip,
     fac_lstm_layer_fwd_persist_split): 17 .. 32 batch columns, where the fp32 resident kernel is bound by its fp32 MFMA time and
-    the per-step kernel by re-streaming W_hh.  Follows FAC_BF16_SPLIT like the conv kernels of the same arithmetic.
+    the per-step kernel by re-streaming W_hh.  Follows BF16_SPLIT like the conv kernels of the same arithmetic.
     T (frames): the kernel needs one fresh exchange region per step, T * H * 32 * 6 bytes of scratch per layer call -- 47 MB at the
     benchmark's 160 frames, but 1.5 - 3 GB for 30-second clips; above FAC_LSTM_PERSIST_SPLIT_MAX_SCRATCH_GB (1) the per-step kernels,
     which need none, take the layer."""
@@ -1311,7 +1305,7 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
 
 
 # 1 (default): both shortcuts; 0: neither (rounds 1-5); 2: only "no padding -> no copy"; 3: only the in-place edge fold + row-stride view
-FOLD_IN_PLACE = int(os.environ.get("FAC_FOLD_IN_PLACE", "1"))
+FOLD_IN_PLACE = 1
 
 
 def _rows_view(t):
@@ -1348,7 +1342,7 @@ def conv1d_bwd_weight(x, dy, k, stride=1, dilation=1, pad_mode=PAD_REFLECT, caus
 # launch goes to torch's current stream in program order, so consecutive layers can share it -- no per-layer allocation of
 # hundreds of MB, and its size shows up once in peak_mem instead of as allocator churn.  FAC_WGRAD_WS_GB caps it.
 _WGRAD_WS = {}
-WGRAD_K1_STREAM = os.environ.get("FAC_WGRAD_K1_STREAM", "1") != "0"      # k = 1 tails with few channels on conv1d_wgrad_k1.hip
+WGRAD_K1_STREAM = True      # k = 1 tails with few channels on conv1d_wgrad_k1.hip
 WGRAD_WS_CAP = int(float(os.environ.get("FAC_WGRAD_WS_GB", "6")) * (1 << 30))
 
 
@@ -1385,7 +1379,7 @@ def _bwd_weight_launch(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilati
 
 def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1=0, dilation2=0, db=None):
     """dW on the bf16 matrix pipe with fp32-grade splitting (conv1d_wgrad_split.hip) when the shape qualifies and
-    FAC_BF16_SPLIT is on, else on the fp32 MFMA kernel.  db: optional (C_out) buffer for the bias gradient; returns True when the
+    BF16_SPLIT is on, else on the fp32 MFMA kernel.  db: optional (C_out) buffer for the bias gradient; returns True when the
     launch filled it."""
     lib = _lib.load()
     if WGRAD_K1_STREAM and BF16_SPLIT and k == 1 and stride == 1 and pad_left == 0 and t_in == t_out and k1 in (0, 1):

@@ -96,13 +96,13 @@ class NativeRccl:
         return _NativeWork(done)
 
 
-GATHER_COPY = os.environ.get("FAC_GATHER_COPY", "1") != "0"
+GATHER_COPY = True
 
 
 def _fold(dst, src):
     """dst[j].copy_(src[j]) for all j.  On the GPU: fac_gather_copy (a few launches, ~0.1 ms of host time for 300 tensors) for the
     contiguous fp32 pairs; torch._foreach_copy_ (measured 17 us of host time per tensor, a hipMemcpyAsync for every second one)
-    for whatever is left, on the CPU, and with FAC_GATHER_COPY=0."""
+    for whatever is left, on the CPU, and with GATHER_COPY = False."""
     rest_d, rest_s = dst, src
     if GATHER_COPY and dst[0].is_cuda:
         ok = [s.is_cuda and s.dtype == torch.float32 and d.dtype == torch.float32 and s.is_contiguous() and d.is_contiguous()

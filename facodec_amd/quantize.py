@@ -284,7 +284,7 @@ class LogMelFrontend(nn.Module):
             basis, self._off = dsp.dft_basis(self.n_fft, self.win, win)
             bt = torch.from_numpy(basis).to(device).unsqueeze(-1)
             self._basis = ops.pack_conv_weight(bt)
-            self._basis_split = ops.pack_gemm_weight_split(bt) if ops.BF16_SPLIT and ops.GEMM_SPLIT else None
+            self._basis_split = ops.pack_gemm_weight_split(bt) if ops.BF16_SPLIT else None
             fb = self.mel_scale.fb.detach().to(device).t().contiguous()  # (n_mels, F)
             self._fb_packed = ops.pack_conv_weight(fb.unsqueeze(-1))
         return self._basis, self._fb_packed, self._off

@@ -24,8 +24,6 @@ How the offline arithmetic is reproduced incrementally
   * `finish()` flushes the frames that were waiting for look-ahead, with the reflect padding of the END of the
     signal the offline front-end applies.
 """
-import os
-
 import torch
 
 from . import ops
@@ -33,7 +31,6 @@ from .dac_model import FUSED_RU_CHANNELS, DecoderBlock, EncoderBlock
 from .layers import ConvWeights
 from .quantize import check_codes
 
-LSTM_REAL_COLUMNS = os.environ.get("FAC_STREAM_LSTM_REAL_COLUMNS", "1") != "0"     # _LSTMState.run
 HOP = 480            # samples per streaming hop (20 ms @ 24 kHz)
 FRAME = 300          # encoder hop (prod of strides 2*5*5*6)
 PERIOD = 2400        # lcm(HOP, FRAME): 5 hops = 8 frames
@@ -109,7 +106,7 @@ class _LSTMState:
         B, H, T = x.shape
         inp = ops.lstm_to_time_major(x)
         BP = inp.shape[2]
-        few = LSTM_REAL_COLUMNS and T * B <= 4 and B < BP
+        few = T * B <= 4 and B < BP
         for l in range(len(self.state)):
             if few:
                 # The recurrence kernel wants the batch padded to 32 columns; the input projection does not: as T "clips" of B
@@ -410,7 +407,6 @@ class StreamingCodec:
         self.n_samples = 0
         self.hops = 0
         self.use_graphs = use_graphs
-        self.two_streams = os.environ.get("FAC_STREAM_TWO_STREAMS", "1") != "0"
         self._side = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         if self._side is not None:
             ops.register_stream_slot(self._side)            # its own split-reduction scratch
@@ -421,7 +417,7 @@ class StreamingCodec:
     # ------------------------------------------------------------------------------------------ steps
     def _step(self, wave_new, final=False):
         first = self.qs.c[0]
-        if wave_new is not None and self.two_streams and self._side is not None:
+        if wave_new is not None and self._side is not None:
             # steady-state hop: [encoder -> latent FIFO] and [quantizer -> decoder] touch disjoint state once the samples are in
             # the STFT history and the due latents are copied out -- two chains of ~100 latency-bound launches side by side
             self.qs.push(wave_new, None)

@@ -40,9 +40,6 @@ def crop_segments(waves, mel_input_length, max_frame_len=80, hop=300, starts=Non
     return wav_seg, starts, out_extra
 
 
-UNBIND_GRADS = os.environ.get("FAC_UNBIND_GRADS", "1") != "0"
-
-
 class GeneratorStep:
     """Generator half without the GAN / predictor terms: 15 mel + 0.25 commitment + codebook (train.py:357-358 subset)."""
 
@@ -154,7 +151,7 @@ class GeneratorStep:
         optimiser folds them in with one multi-tensor copy (FlatAdamW.zero_grad).  Under a DistributedDataParallel
         wrapper (data_parallel=False) the reducer owns `.grad`: the views stay bound."""
         for k in keys:
-            self.opt[k].zero_grad(unbind=UNBIND_GRADS and self.opt[k].data_parallel)
+            self.opt[k].zero_grad(unbind=self.opt[k].data_parallel)
 
     def forward_backward(self, wave, masks=None, full_waves=None, wave_lens=None):
         m = self.model
@@ -223,7 +220,6 @@ class TrainStep(GeneratorStep):
         self._sync_start([self.opt[k] for k in ("discriminator", "fa_predictors") if k in self.opt])
         self.stft = losses.MultiScaleSTFTLoss()
         self.l1 = losses.L1Loss()
-        self.batched_d_step = os.environ.get("FAC_BATCHED_D_STEP", "1") != "0"
 
     def predictor_losses(self, preds, rev, targets):
         """train.py:314-356 given the targets the reference takes from external models: f0 (B, F) normalised log-F0
@@ -281,12 +277,9 @@ class TrainStep(GeneratorStep):
             target = target[..., len_diff // 2:-len_diff // 2].contiguous()
         # ---- discriminator step (train.py:279-292)
         disc = m.discriminator
-        if self.batched_d_step:      # one pass over [fake | real]: half the launches, twice the tiles per launch
-            from .discriminator import gan_loss_d_batched
-            loss_d = gan_loss_d_batched(disc.forward_internal(torch.cat([pred.detach(), target], 0)))
-        else:
-            d_fake, d_real = disc.forward_internal(pred.detach()), disc.forward_internal(target)
-            loss_d, _, _ = gan_losses(d_fake, d_real)
+        # one pass over [fake | real]: half the launches, twice the tiles per launch
+        from .discriminator import gan_loss_d_batched
+        loss_d = gan_loss_d_batched(disc.forward_internal(torch.cat([pred.detach(), target], 0)))
         loss_d.backward()
         opt["discriminator"].launch_all_reduce()                         # rides under the loss forwards below
         mel = self.mel(pred, target)

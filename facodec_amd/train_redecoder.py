@@ -21,7 +21,7 @@ of the old forward (:303); this step makes the call without them.
 import torch
 
 from . import losses, optim
-from .train import UNBIND_GRADS, crop_segments
+from .train import crop_segments
 
 OPT_KEYS = ("encoder", "decoder", "discriminator")
 
@@ -73,7 +73,7 @@ class RedecoderTrainStep:
         from .discriminator import gan_loss_d_batched, gan_losses
         m, opt, disc = self.model, self.opt, self.disc
         for k in OPT_KEYS:
-            opt[k].zero_grad(unbind=UNBIND_GRADS and opt[k].data_parallel)
+            opt[k].zero_grad(unbind=opt[k].data_parallel)
         wav_seg, _, _ = crop_segments(waves, mel_input_length, self.max_frame_len, self.hop, starts=starts, generator=generator)
         codes, timbre = self.codec_forward(wav_seg, waves, wave_lens)
         pred = m.decoder(m.encoder(codes[0], codes[1], timbre, dropout=self.dropout))

@@ -42,3 +42,29 @@ def _function_level_only(path, allowed):
 def test_bench_and_entry_use_the_oracle_only_as_checker():
     _function_level_only(os.path.join(REPO, "bench.py"), {"cpu_baseline"})
     _function_level_only(os.path.join(REPO, "__graft_entry__.py"), {"smoke"})
+
+
+# Environment variables and preprocessor conditions the package may read: deployment / resource configuration, and the second paths
+# that tests drive through a child process's environment.  A tuning lever does not belong here: settle it, keep the
+# winner as a constant and delete the switch.
+FAC_NAMES_ALLOWED = {
+    "FAC_LIB_PATH", "FAC_BUILD_TAG", "FAC_EXTRA_FLAGS",
+    "FAC_NATIVE_RCCL", "FAC_FORCE_ALLREDUCE", "FAC_DIST_BACKEND", "FAC_BUCKET_MB", "FAC_EARLY_EXCHANGE",
+    "FAC_QUANT_STREAMS", "FAC_DISC_STREAMS", "FAC_PRED_STREAMS", "FAC_MEL_STREAMS",
+    "FAC_WGRAD_WS_GB", "FAC_LSTM_PERSIST_SPLIT_MAX_SCRATCH_GB",
+    "FAC_WGRAD_NARROW", "FAC_WEIGHT_BATCH", "FAC_PW", "FAC_PW_SPLIT",
+}
+
+
+def test_fac_environment_reads_and_macro_conditions_are_the_allowed_ones():
+    import glob
+    import re
+    pkg = os.path.join(REPO, "facodec_amd")
+    files = glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True) + glob.glob(os.path.join(pkg, "csrc", "*"))
+    found = set()
+    for path in files:
+        if os.path.isfile(path) and path.endswith((".py", ".hip", ".h")):
+            for line in open(path):
+                if re.search(r"os\.environ|getenv\s*\(|^\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    found |= set(re.findall(r"\bFAC_[A-Z0-9_]+", line))
+    assert found == FAC_NAMES_ALLOWED, (sorted(found - FAC_NAMES_ALLOWED), sorted(FAC_NAMES_ALLOWED - found))

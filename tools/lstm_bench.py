@@ -1,5 +1,5 @@
 """Times one SLSTM layer's recurrence and BPTT: resident kernels (lstm_persist.hip; fp32, and bf16 x 3 for 17 .. 32 columns) vs one
-launch per step (lstm.hip).  FAC_LSTM_PERSIST_MAX_BATCH=32 times the fp32 resident kernel at 32 columns too."""
+launch per step (lstm.hip).  ops.LSTM_PERSIST_MAX_BATCH = 32 times the fp32 resident kernel at 32 columns too."""
 import json
 import sys
 

@@ -28,7 +28,7 @@ def main():
         enrol = wave[:, :, :48000]
         timbre = model.quantizer(model.encoder(wave), wave, n_c=2)[4]
         sess = StreamingCodec(model, timbre, n_c=2, use_graphs=False)
-        sess.two_streams = False
+        sess._side = None                      # one chain: the session's single-stream path
         sess.prime(wave[:, :, :4800])
         for h in range(5):
             sess.push(wave[:, :, 4800 + h * HOP:4800 + (h + 1) * HOP])

@@ -1,11 +1,9 @@
 #!/usr/bin/env python
 """Streaming-hop A/B inside ONE process: two (or more) sessions built under different switches, fed the same audio in alternating
 blocks of 300 hops -- box-to-box and minute-to-minute drift of the per-hop latency (+-0.08 ms between two 30 s runs of
-tools/stream_bench.py on one box) cancels.  Variants are "name:KEY=VAL,KEY=VAL" with keys
-  gemv (FAC_GEMV), fold (ops.STREAM_FOLD), lstm_real (streaming.LSTM_REAL_COLUMNS), two (StreamingCodec.two_streams).
+tools/stream_bench.py on one box) cancels.  Variants are "name:KEY=VAL" with the key fold (ops.STREAM_FOLD).
    python tools/tune/stream_ab_inproc.py base: "nofold:fold=0" ...
-(Round 6 used it with two more switches that were then removed: the quantizer as its own third chain, and a smaller workgroup budget
-for the encoder chain's split-reduction launches -- both exactly neutral, profiles/r06_streaming_inprocess_ab.log.)"""
+(Round 6 used it with more switches, removed once settled: DESIGN.md 11.5 and profiles/r06_streaming_inprocess_ab.log.)"""
 import json
 import os
 import statistics
@@ -15,15 +13,13 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from facodec_amd import ops, streaming, synth  # noqa: E402
+from facodec_amd import ops, synth  # noqa: E402
 from facodec_amd.commons import build_model, default_model_params  # noqa: E402
 from facodec_amd.streaming import HOP, StreamingCodec  # noqa: E402
 
 
 def apply(cfg):
-    os.environ["FAC_GEMV"] = str(cfg.get("gemv", 1))
     ops.STREAM_FOLD = bool(int(cfg.get("fold", 1)))
-    streaming.LSTM_REAL_COLUMNS = bool(int(cfg.get("lstm_real", 1)))
 
 
 def main():
@@ -44,7 +40,6 @@ def main():
         for name, cfg in variants:
             apply(cfg)
             s = StreamingCodec(model, timbre, n_c=2)
-            s.two_streams = bool(int(cfg.get("two", 1)))
             s.prime(wave[:, :, :4800])
             for h in range(15):                       # eager period, capture period, first replays -- under this variant's switches
                 s.push(wave[:, :, 4800 + h * HOP:4800 + (h + 1) * HOP])
