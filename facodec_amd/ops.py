@@ -377,25 +377,32 @@ def _conv_workspace(device):
     return ws
 
 
+def conv_variant(d):
+    """(id, name) of the kernel fac_conv1d_fwd launches for descriptor `d` (fac_conv1d_variant: the same planner, no launch);
+    id < 0 with an empty name where fac_conv1d_fwd would reject `d`."""
+    buf = C.create_string_buffer(96)
+    return _lib.load().fac_conv1d_variant(C.byref(d), buf, 96), buf.value.decode()
+
+
 def _launch_conv(d, what):
     lib = _lib.load()
     ws = _conv_workspace(_cuda_device(_GET_DEVICE() if _GET_DEVICE is not None else torch.cuda.current_device()))
     d.ws, d.ws_bytes = ws.data_ptr(), CONV_WS_BYTES
+    if _FLOPS is not None or _PROFILE is not None:
+        flops = 2.0 * d.B * d.n_phase * max(1, d.row_phases) * d.C_out * d.T_out * d.C_in * d.K
+        if d.w_k1:
+            flops += 2.0 * d.B * d.C_out * d.T_out * d.C_out   # fused 1x1 conv
     if _FLOPS is not None:
-        _FLOPS.add(_FLOP_KEY, 2.0 * d.B * d.n_phase * max(1, d.row_phases) * d.C_out * d.T_out * d.C_in * d.K + (2.0 * d.B * d.C_out * d.T_out * d.C_out if d.w_k1 else 0.0))
+        _FLOPS.add(_FLOP_KEY, flops)
     if _PROFILE is None:
         _lib.check(lib.fac_conv1d_fwd(C.byref(d), _stream()), what)
         return
-    buf = C.create_string_buffer(64)
-    lib.fac_conv1d_variant(C.byref(d), buf, 64)
+    name = conv_variant(d)[1][:63]      # the profile's keys have always been the first 63 bytes of the name
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     _lib.check(lib.fac_conv1d_fwd(C.byref(d), _stream()), what)
     e1.record()
-    flops = 2.0 * d.B * d.n_phase * max(1, d.row_phases) * d.C_out * d.T_out * d.C_in * d.K
-    if d.w_k1:
-        flops += 2.0 * d.B * d.C_out * d.T_out * d.C_out   # fused 1x1 conv
-    _PROFILE.records.append((buf.value.decode(), flops, e0, e1))
+    _PROFILE.records.append((name, flops, e0, e1))
 
 
 # 1- / 2-tap convs as split-bf16 GEMMs (conv1d_gemm_split.hip): policy of who packs the GEMM layout.

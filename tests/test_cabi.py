@@ -89,15 +89,14 @@ def _desc(B, c_in, c_out, T_in, T_out, K, stride=1, dil=1, pad_left=0, n_phase=1
     return d
 
 
+def variant(d):
+    buf = ctypes.create_string_buffer(96)
+    return _lib.load().fac_conv1d_variant(ctypes.byref(d), buf, 96), buf.value.decode()
+
+
 def test_kernel_selection_for_the_benchmark_shapes():
     """Which kernel fac_conv1d_fwd takes for the layer shapes of configs[1] (B = 32 x 2 s) and for their small-batch
-    counterparts -- host logic only (fac_conv1d_variant reads the descriptor, nothing is launched)."""
-    lib = _lib.load()
-
-    def variant(d):
-        buf = ctypes.create_string_buffer(96)
-        return lib.fac_conv1d_variant(ctypes.byref(d), buf, 96), buf.value.decode()
-
+    counterparts -- host logic only: fac_conv1d_variant runs the planner fac_conv1d_fwd launches from and stops before the launch."""
     B = 32
     # k = 7 ResidualUnit convs with pre-split weights: the split-bf16 kernel, for every channel count of the codec
     for c, t in ((64, 48000), (96, 48000), (128, 24000), (192, 24000), (384, 4800), (768, 960)):
@@ -121,3 +120,50 @@ def test_kernel_selection_for_the_benchmark_shapes():
     # transposed conv (polyphase, n_phase = stride) stays on the fp32 tiles
     vid, name = variant(_desc(B, 384, 192, 4800, 4800, 2, pad_left=1, n_phase=5, y2=True))
     assert vid in (3, 4), name
+
+
+def test_kernel_selection_is_the_launch_path():
+    """fac_conv1d_variant answers from fac_conv1d_fwd's own validation and predicate order: the launches on which a separately
+    kept naming chain once disagreed with the launch, the errors, and every kernel the benchmark shapes above do not reach."""
+    lib = _lib.load()
+    fp32_w = ctypes.c_void_p(0x20000)
+    # the K = 3 / 5 / 7 split kernel is asked before the C_out <= 2 kernels and does not look at C_out
+    vid, name = variant(_desc(32, 96, 1, 48000, 48000, 7, pad_left=6, split=True))
+    assert vid == 11 and name == "conv1d_bsplit_kernel<7> 64x256 (bf16x3 split, fp32-grade)", name
+    # ... and refuses a channel stride its 32-bit offsets cannot hold: split-only weights are then an error, fp32 weights a tile
+    d = _desc(32, 64, 64, 48000, 48000, 7, pad_left=6, split=True)
+    d.x_cs = 1 << 30
+    assert variant(d)[0] == -1 and b"no fp32 weights were given" in lib.fac_last_error()
+    d.w = fp32_w
+    assert variant(d) == (2, "conv1d_mfma_kernel<2,1,1,4,K> 64x128")
+    # what fac_conv1d_fwd rejects is rejected here, same code and message
+    d = _desc(32, 64, 64, 48000, 48000, 7, pad_left=6)
+    d.C_out_pad = 100
+    assert variant(d)[0] == -1 and b"C_out_pad must be a multiple of 32" in lib.fac_last_error()
+    assert lib.fac_conv1d_fwd(ctypes.byref(d), None) == -1 and b"C_out_pad must be a multiple of 32" in lib.fac_last_error()
+    # the gated epilogue exists in the split-reduction kernel only
+    d = _desc(1, 512, 1024, 30, 30, 5, pad_left=4)
+    d.act, d.y_bs = 4, 512 * 30                                                  # FAC_ACT_GATE
+    assert variant(d) == (10, "conv1d_skinny_kernel (split reduction, <=640 columns)")
+    d = _desc(32, 512, 1024, 960, 960, 5, pad_left=4)
+    d.act, d.y_bs = 4, 512 * 960
+    assert variant(d)[0] == -1 and b"few-column launches" in lib.fac_last_error()
+    # split-bf16 GEMM: k = 1, and a strided conv with stride < K <= 2 * stride as two taps
+    vid, name = variant(_desc(8, 512, 512, 960, 960, 1, split=True))
+    assert vid == 15 and name == "conv1d_gemm_split_kernel<1> 128x128 (bf16x3 split GEMM, fp32-grade)", name
+    vid, name = variant(_desc(16, 128, 256, 5760, 960, 12, stride=6, pad_left=6, split=True))
+    assert vid == 15 and name == "conv1d_gemm_split_kernel<2> 128x128 (bf16x3 split GEMM, fp32-grade)", name
+    # few output channels, (3, 9) taps over a row-concatenated signal of pitch 32
+    d = _desc(1, 6, 32, 6464, 6464, 27, pad_left=36, split=True)
+    d.K1, d.dilation2 = 9, 32
+    vid, name = variant(d)
+    assert vid == 16 and name == "conv1d_bsplit2_kernel<9,1> 32x512 (bf16x3 split, fp32-grade)", name
+    # streaming kernels on the bf16 pipe (pw_split): k = 1 tail, k = 4 stride-2 conv
+    d = _desc(64, 96, 96, 4101, 4101, 1, res=True, y2=True)
+    d.pw_split = 1
+    vid, name = variant(d)
+    assert vid == 17 and name.startswith("conv1d_pws_kernel "), name
+    d = _desc(32, 64, 128, 8203, 4102, 4, stride=2, pad_left=2, y2=True)
+    d.pw_split, d.pad_mode = 1, 1
+    vid, name = variant(d)
+    assert vid == 18 and name.startswith("conv1d_pwt_kernel<4 taps> "), name

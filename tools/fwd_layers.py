@@ -28,15 +28,13 @@ def main():
     orig = ops._launch_conv
 
     def spy(d, what):
-        buf = ops.C.create_string_buffer(96)
-        ops._lib.load().fac_conv1d_variant(ops.C.byref(d), buf, 96)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         orig(d, what)
         e1.record()
         recs.append((dict(B=d.B, ci=d.C_in, co=d.C_out, T=d.T_out, K=d.K, s=d.stride, dil=d.dilation, ph=d.n_phase,
                           ain=bool(d.alpha_in), aout=bool(d.alpha_out), res=bool(d.res), y2=bool(d.y2), split=bool(d.w_split),
-                          fused=bool(d.w_k1)), buf.value.decode()[:44], 2.0 * d.B * d.n_phase * d.C_out * d.T_out * d.C_in * d.K, e0, e1))
+                          fused=bool(d.w_k1)), ops.conv_variant(d)[1][:44], 2.0 * d.B * d.n_phase * d.C_out * d.T_out * d.C_in * d.K, e0, e1))
 
     ops._launch_conv = spy
     step()

@@ -28,13 +28,11 @@ def main():
     orig = ops._launch_conv
 
     def spy(d, what):
-        buf = ops.C.create_string_buffer(96)
-        ops._lib.load().fac_conv1d_variant(ops.C.byref(d), buf, 96)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         orig(d, what)
         e1.record()
-        key = (d.B, d.C_in, d.C_out, d.T_out, d.K, d.K1, d.stride, d.dilation, d.dilation2, d.n_phase, d.row_phases, buf.value.decode()[:44])
+        key = (d.B, d.C_in, d.C_out, d.T_out, d.K, d.K1, d.stride, d.dilation, d.dilation2, d.n_phase, d.row_phases, ops.conv_variant(d)[1][:44])
         recs.append((key, 2.0 * d.B * d.n_phase * max(1, d.row_phases) * d.C_out * d.T_out * d.C_in * d.K, e0, e1))
 
     ops._launch_conv = spy
