@@ -20,16 +20,6 @@ from torch.autograd import Function
 from . import ops
 
 
-def _split_ok(c_out, c_in, k, stride, x):
-    if k == 1 and stride == 1:          # 1x1 with many channels: split-bf16 GEMM (conv1d_gemm_split.hip)
-        return ops.gemm_split_ok(c_out, c_in, 1, x.shape[0] * x.shape[-1]) and not ops.pw_split_tail_ok(c_in, c_out, x.shape[0] * x.shape[-1])
-    if k in (3, 5):                     # WaveNet / style-encoder k = 5, encoder output conv k = 3: enough channels only
-        return (ops.BF16_SPLIT and stride == 1 and c_in % 16 == 0 and c_in >= 64 and c_out % 16 == 0 and c_out > 32
-                and x.shape[0] * x.shape[-1] > 640)
-    return (ops.BF16_SPLIT and k == 7 and stride == 1 and c_in % 16 == 0 and c_out % 16 == 0 and c_out > 2
-            and x.shape[0] * x.shape[-1] > 640)
-
-
 def _wn(w):
     """(v, g) of a ConvWeights holder (g None for a plain weight)."""
     return (w.weight_v, w.weight_g) if w.weight_norm else (w.weight, None)
@@ -41,34 +31,21 @@ class _Conv(Function):
         k, stride, dilation, pad_mode, causal, act = cfg
         vd, gd = v.detach(), (g.detach() if g is not None else None)
         sc = ops.wn_scale(vd, gd) if gd is not None else None          # g / ||v||: once per forward, re-used by the backward
-        if (stride == 2 and dilation == 1 and act == ops.ACT_NONE
-                and ops.pw_taps_ok(v.shape[1], v.shape[0], k, 2, False, x.shape[0], -(-x.shape[-1] // 2))):
-            wp, ws = ops.pack_conv_weight(vd, gd, scale=sc), None        # few channels: the streaming kernel with taps takes the fp32 pack
-        elif stride > 1 and dilation == 1 and ops.gemm_split_strided_ok(v.shape[0], v.shape[1], k, stride, x.shape[0], -(-x.shape[-1] // stride)):
-            wp, ws = None, ops.pack_gemm_weight_split(vd, gd, in_stride=stride, scale=sc)     # downsampling conv on the split GEMM kernel
-        elif _split_ok(v.shape[0], v.shape[1], k, stride, x):       # k = 7 / k = 1 convs: fp32-grade split on the bf16 pipe
-            wp, ws = None, ops.pack_conv_weight_split(vd, gd, scale=sc)
-        else:
-            wp, ws = ops.pack_conv_weight(vd, gd, scale=sc), None
+        B, _, T = x.shape
+        plan = ops.plan_conv(v.shape[0], v.shape[1], k, stride, dilation, B, T, -(-T // stride), plain=act == ops.ACT_NONE,
+                             causal_reflect=causal and pad_mode == ops.PAD_REFLECT, flat_train="reflect")
+        wp, ws = ops.pack_conv_for(plan.layout, vd, gd, stride, scale=sc)
         ctx.scale = sc
         xin = x.detach()
-        n_out = -(-x.shape[-1] // stride)
-        if (stride > 1 and dilation == 1 and causal and pad_mode == ops.PAD_REFLECT and act == ops.ACT_NONE and x.shape[-1] % stride == 0
-                and x.shape[-1] > stride and ops.flat_strided_ok(v.shape[0], v.shape[1], k, stride, x.shape[0], n_out)):
+        bd = bias.detach() if bias is not None else None
+        if plan.form == ops.FLAT_STRIDED:
             # short clips (the 160-frame latent rate): every clip reflect-padded on the left by k - s = s samples (the causal padding
             # of dac/model/encodec.py:212-222; T % s == 0: no right padding), all of them as one signal on the split GEMM kernel
-            y = ops.conv1d_flat_strided(torch.nn.functional.pad(xin, (stride, 0), mode="reflect"),
-                                        ops.pack_gemm_weight_split(vd, gd, in_stride=stride, scale=sc), v.shape[0], k, stride,
-                                        bias=bias.detach() if bias is not None else None)
-            ctx.cfg = cfg
-            ctx.save_for_backward(x, v, g, bias, None)
-            return y
-        if ws is not None and stride > 1 and dilation == 1:
-            # split GEMM over the phase sub-signals: plane inputs where the pass pays for itself (ops.p8_prepass; round 6: the training
-            # launches take the same pre-pass as the inference ones -- same bf16 operands in the same order, same bits)
-            xin = ops.p8_prepass(xin, 2.0 * v.shape[0] * k / (4.0 * stride))
-        y = ops.conv1d(xin, wp, v.shape[0], k, bias=bias.detach() if bias is not None else None,
-                       stride=stride, dilation=dilation, pad_mode=pad_mode, causal=causal, act=act, w_split=ws)
+            y = ops.conv1d_flat(torch.nn.functional.pad(xin, (stride, 0), mode="reflect"), ws, v.shape[0], k, stride, T // stride,
+                                bias=bd, p8=plan.p8)
+        else:                            # (split GEMM over the phase sub-signals: plane inputs where the pass pays, ops.p8_prepass)
+            y = ops.conv1d(ops.p8_prepass(xin, plan.p8), wp, v.shape[0], k, bias=bd, stride=stride, dilation=dilation,
+                           pad_mode=pad_mode, causal=causal, act=act, w_split=ws)
         ctx.cfg = cfg
         ctx.save_for_backward(x, v, g, bias, y if act == ops.ACT_TANH else None)
         return y
@@ -101,24 +78,19 @@ class _ConvTr(Function):
         vd, gd = v.detach(), (g.detach() if g is not None else None)
         ctx.stride, ctx.causal = stride, causal
         ctx.save_for_backward(x, v, g, bias)
-        if not causal:
-            # non-causal (the redecoder's decoder): the launch of SConvTranspose1d.run in eval mode -- polyphase layout, trim by the
-            # kernel's phase_shift -- so train and eval forwards agree
-            wt = ops.convtr_weight_for(vd, gd, stride, x.shape[-1], causal=False, batch=x.shape[0])
-            return ops.conv_transpose1d(x.detach(), wt, v.shape[1], stride, bias=bias.detach() if bias is not None else None, causal=False)
-        if ops.flat_convtr_ok(v.shape[0], v.shape[1], stride, x.shape[0], x.shape[-1] + 1):
+        # (non-causal, the redecoder's decoder: the launch of SConvTranspose1d.run in eval mode -- polyphase layout, trim by the
+        # kernel's phase_shift -- so train and eval forwards agree)
+        B, _, T = x.shape
+        bd = bias.detach() if bias is not None else None
+        plan = ops.plan_convtr(v.shape[0], v.shape[1], stride, B, T, causal=causal, flat_train_cols=T + 1)
+        wt = ops.pack_convtr_for(plan.layout, vd, gd, stride)
+        if plan.layout == ops.TR_FLAT:
             # short clips: a zero column in front of every clip (the x[t - 1] of its first frame), one flattened signal; the s output
             # samples of that column are dropped
-            xz = torch.nn.functional.pad(x.detach(), (1, 0))
-            return ops.conv_transpose1d_flat(xz, vd, gd, stride, bias=bias.detach() if bias is not None else None)[:, :, stride:].contiguous()
-        wt = ops.convtr_weight_for(vd, gd, stride, x.shape[-1], batch=x.shape[0])
-        xin = x.detach()
-        if isinstance(wt, tuple):                     # all-phases launch on the split GEMM kernel: 2 s C_out MACs per input sample
-            xin = ops.p8_prepass(xin, 2.0 * v.shape[1] * 2 * stride / 4.0)
-        y = ops.conv_transpose1d(xin, wt, v.shape[1], stride, bias=bias.detach() if bias is not None else None)
-        ctx.stride = stride
-        ctx.save_for_backward(x, v, g, bias)
-        return y
+            return ops.conv_transpose1d_flat(torch.nn.functional.pad(x.detach(), (1, 0)), wt, v.shape[1], stride, trim=stride, bias=bd,
+                                             p8=plan.p8)
+        xin = ops.p8_prepass(x.detach(), plan.p8)     # all-phases launch on the split GEMM kernel: 2 s C_out MACs per input sample
+        return ops.conv_transpose1d(xin, wt, v.shape[1], stride, bias=bd, causal=causal)
 
     @staticmethod
     def backward(ctx, dy):
@@ -186,16 +158,11 @@ class _ResUnit(Function):
         xd, xad = x.detach(), xa.detach()
         v7d, g7d, v1d, g1d = v7.detach(), g7.detach(), v1.detach(), g1.detach()
         s7, s1 = ops.wn_scale(v7d, g7d), ops.wn_scale(v1d, g1d)      # once per forward, re-used by the backward
-        if _split_ok(c, v7.shape[1], 7, 1, xad):
-            wp, ws = None, ops.pack_conv_weight_split(v7d, g7d, scale=s7)
-        else:
-            wp, ws = ops.pack_conv_weight(v7d, g7d, scale=s7), None
+        B, _, T = xad.shape
+        wp, ws = ops.pack_conv_for(ops.plan_conv(c, v7.shape[1], 7, 1, dilation, B, T, T).layout, v7d, g7d, scale=s7)
         h, ha = ops.conv1d(xad, wp, c, 7, bias=b7.detach(), dilation=dilation, pad_mode=pad_mode, causal=causal,
                            alpha_y2=a2.detach().reshape(-1), w_split=ws)
-        if _split_ok(c, c, 1, 1, ha):
-            wp1, ws1 = None, ops.pack_conv_weight_split(v1d, g1d, scale=s1)
-        else:
-            wp1, ws1 = ops.pack_conv_weight(v1d, g1d, scale=s1), None
+        wp1, ws1 = ops.pack_conv_for(ops.plan_conv(c, c, 1, 1, 1, B, ha.shape[-1], ha.shape[-1]).layout, v1d, g1d, scale=s1)
         y, ya = ops.conv1d(ha, wp1, c, 1, bias=b1.detach(), pad_mode=pad_mode, causal=causal, res=xd,
                            alpha_y2=a_next.detach().reshape(-1), w_split=ws1)
         ctx.cfg = cfg
@@ -269,13 +236,11 @@ class _LSTM(Function):
         for l in range(L):
             w_ih, w_hh, b_ih, b_hh = (p.detach() for p in params[4 * l: 4 * l + 4])
             with ops.flop_scale(B / BP):
-                use_split = ops.gemm_split_ok(4 * H, H, 1, T * BP)
-                sig = inp.view(1, H, T * BP)
-                if use_split:
-                    sig = ops.p8_prepass(sig, 2.0 * 4 * H / 4.0)
-                pre = ops.conv1d(sig, None if use_split else ops.pack_conv_weight(w_ih), 4 * H, 1,
+                plan = ops.plan_gemm(4 * H, H, T * BP)
+                sig = ops.p8_prepass(inp.view(1, H, T * BP), plan.p8)
+                pre = ops.conv1d(sig, ops.pack_conv_weight(w_ih) if plan.layout == ops.W_FP32 else None, 4 * H, 1,
                                  bias=ops.add(b_ih, b_hh), pad_left=0, t_out=T * BP, pad_mode=ops.PAD_ZERO,
-                                 w_split=ops.pack_gemm_weight_split(w_ih) if use_split else None)
+                                 w_split=ops.pack_gemm_weight_split(w_ih) if plan.layout == ops.W_GEMM else None)
                 gates = torch.empty(4 * H, T, BP, device=x.device)
                 cs = torch.empty(H, T, BP, device=x.device)
                 if ops.lstm_persist_ok(H, B):      # whole layer in one launch, W_hh resident in registers
@@ -319,7 +284,7 @@ class _LSTM(Function):
             db = ops.bias_grad(dg_flat)
             grads[4 * l + 2], grads[4 * l + 3] = db, db.clone()
             # gradient w.r.t. this layer's input sequence: W_ih^T dgates, one GEMM over every (t, b)
-            if ops.gemm_split_ok(H, 4 * H, 1, T * BP):
+            if ops.plan_gemm(H, 4 * H, T * BP).layout == ops.W_GEMM:
                 d_out = ops.conv1d(dg_flat, None, H, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=T * BP,
                                    w_split=ops.pack_gemm_weight_split_t(w_ih)).view(H, T, BP)
             else:

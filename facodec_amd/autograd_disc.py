@@ -14,9 +14,10 @@ def _call(name, *args):
 _p = ops._ptr
 
 
-def _split_ok(k, stride, c_in, c_out, ncol):
-    """k = 5 / 7 stride-1 convs with enough channels and columns: fp32-grade split on the bf16 pipe."""
-    return ops.BF16_SPLIT and k in (5, 7) and stride == 1 and c_in % 16 == 0 and c_out % 16 == 0 and c_out > 2 and ncol > 640
+def _plan(c_out, c_in, k, stride, batch, t_in, t_out, k1):
+    """The discriminators' conv rule: k = 5 / 7 split taps without a channel floor, split2 stacks, no 1x1 GEMM, no streaming taps."""
+    return ops.plan_conv(c_out, c_in, k, stride, 1, batch, t_in, t_out, k1=k1, split_k=(5, 7), floor_k=(), pw_taps=False,
+                         split2=True)
 
 
 class PlainConv(Function):
@@ -32,18 +33,11 @@ class PlainConv(Function):
         t_out = (t_in + 2 * pad - max_off - 1) // stride + 1
         vd, gd = v.detach().contiguous(), (g.detach().contiguous() if g is not None else None)
         sc = ops.wn_scale(vd, gd) if gd is not None else None           # once per forward, re-used by the backward
-        if ops.split2_ok(v.shape[0], k, k1, stride, B * t_out):
-            wp, ws = None, ops.pack_conv_weight_split2(vd, gd, k1, scale=sc)      # 32-channel (3, 9) / (3, 3) stacks: conv1d_bsplit2.hip
-        elif not k1 and stride > 1 and ops.gemm_split_strided_ok(v.shape[0], c_in, k, stride, B, t_out):
-            wp, ws = None, ops.pack_gemm_weight_split(vd, gd, in_stride=stride, scale=sc)     # (5, 1) stride-3 convs: split GEMM over 3 phases
-        elif not k1 and _split_ok(k, stride, c_in, v.shape[0], B * t_out):
-            wp, ws = None, ops.pack_conv_weight_split(vd, gd, scale=sc)
-        else:
-            wp, ws = ops.pack_conv_weight(vd, gd, scale=sc), None
+        # 32-channel (3, 9) / (3, 3) stacks: conv1d_bsplit2.hip; (5, 1) stride-3 convs: split GEMM over 3 phases; k = 5 / 7: split taps
+        plan = _plan(v.shape[0], c_in, k, stride, B, t_in, t_out, k1)
+        wp, ws = ops.pack_conv_for(plan.layout, vd, gd, stride, k1, scale=sc)
         ctx.scale = sc
-        xin = x.detach()
-        if ws is not None and not k1 and stride > 1 and ops.gemm_split_strided_ok(v.shape[0], c_in, k, stride, B, t_out):
-            xin = ops.p8_prepass(xin, 2.0 * v.shape[0] * k / (4.0 * stride))      # (5, 1) stride-3 convs on the split GEMM kernel
+        xin = ops.p8_prepass(x.detach(), plan.p8)       # (5, 1) stride-3 convs on the split GEMM kernel
         y = ops.conv1d(xin, wp, v.shape[0], k, bias=bias.detach() if bias is not None else None,
                        stride=stride, pad_left=pad, pad_mode=ops.PAD_ZERO, t_out=t_out, w_split=ws, k1=k1, dilation2=dil2)
         ctx.cfg = (k, stride, pad, t_in, t_out, k1, dil2, max_off)
@@ -66,9 +60,9 @@ class PlainConv(Function):
                 # polyphase transposed conv (no zero-inserted columns: 1.2x the useful flops for k = 5, s = 3 instead of 3x)
                 v6 = torch.cat([vd, vd.new_zeros(c_out, c_in, 2 * stride - k)], dim=2) if k < 2 * stride else vd
                 dy_ext = torch.cat([dy, dy.new_zeros(B, c_out, 1)], dim=2)
-                wt = ops.convtr_weight_for(v6, gd, stride, dy_ext.shape[-1], batch=B)
-                if isinstance(wt, tuple):
-                    dy_ext = ops.p8_prepass(dy_ext, 2.0 * c_in * 2 * stride / 4.0)
+                tplan = ops.plan_convtr(c_out, c_in, stride, B, dy_ext.shape[-1])
+                wt = ops.pack_convtr_for(tplan.layout, v6, gd, stride)
+                dy_ext = ops.p8_prepass(dy_ext, tplan.p8)
                 with ops.flop_scale(k / (2.0 * stride)):      # the zero taps that pad k to 2 * stride are not algorithmic work
                     dxp = ops.conv_transpose1d(dy_ext, wt, c_in, stride)
                 if dxp.shape[-1] < pad + t_in:
@@ -87,18 +81,12 @@ class PlainConv(Function):
                     tp, shift = t_in, pl
                 else:                     # (not reached by the model's layers: padding larger than the taps' span)
                     tp, shift = up.shape[-1] + max_off, max_off
-                if ops.split2_ok(c_in, k, k1, 1, B * tp):
-                    ws = ops.pack_conv_weight_split2(ops.flipped_weight(vd, gd, ctx.scale), None, k1)
-                    with ops.flop_scale(1.0 / stride):
-                        dxp = ops.conv1d(up, None, c_in, k, pad_left=shift, pad_mode=ops.PAD_ZERO, t_out=tp, w_split=ws,
-                                         k1=k1, dilation2=dil2)
-                elif not k1 and _split_ok(k, 1, c_out, c_in, B * tp):
-                    ws = ops.pack_conv_weight_split(ops.flipped_weight(vd, gd, ctx.scale))
-                    dxp = ops.conv1d(up, None, c_in, k, pad_left=shift, pad_mode=ops.PAD_ZERO, t_out=tp, w_split=ws)
-                else:
-                    with ops.flop_scale(1.0 / stride):        # zero-inserted columns (stride > 1) are not algorithmic work
-                        dxp = ops.conv1d(up, ops.pack_conv_weight_bwd(vd, gd, ctx.scale), c_in, k, pad_left=shift, pad_mode=ops.PAD_ZERO, t_out=tp,
-                                         k1=k1, dilation2=dil2)
+                layout = _plan(c_in, c_out, k, 1, B, up.shape[-1], tp, k1).layout      # the forward rule with the channels swapped
+                wp, ws = ((ops.pack_conv_weight_bwd(vd, gd, ctx.scale), None) if layout == ops.W_FP32
+                          else ops.pack_conv_for(layout, ops.flipped_weight(vd, gd, ctx.scale), None, k1=k1))
+                # zero-inserted columns (stride > 1) are not algorithmic work (the split-taps launch has always counted them)
+                with ops.flop_scale(1.0 if layout == ops.W_TAPS else 1.0 / stride):
+                    dxp = ops.conv1d(up, wp, c_in, k, pad_left=shift, pad_mode=ops.PAD_ZERO, t_out=tp, w_split=ws, k1=k1, dilation2=dil2)
                 if pl >= 0:
                     dx = dxp
                 else:

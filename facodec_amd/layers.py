@@ -44,54 +44,37 @@ class ConvWeights(nn.Module):
         self._rows_split = None
         self.freeze_packed = False
 
+    def _vg(self):
+        return (self.weight_v.detach(), self.weight_g.detach()) if self.weight_norm else (self.weight.detach(), None)
+
+    def _cached(self, slot, pack, *a, **kw):
+        """The packed copy kept in `slot`: repacked into the same buffer on every call unless `freeze_packed`."""
+        cur = getattr(self, slot)
+        if cur is None or not self.freeze_packed:
+            cur = pack(*self._vg(), *a, out=cur[0] if isinstance(cur, tuple) else cur, **kw)
+            setattr(self, slot, cur)
+        return cur
+
     def packed(self):
-        if self._packed is not None and self.freeze_packed:
-            return self._packed
-        v = self.weight_v if self.weight_norm else self.weight
-        g = self.weight_g if self.weight_norm else None
         if self.transposed:
-            self._packed = ops.pack_convtr_weight(v.detach(), g.detach() if g is not None else None, self.stride,
-                                                  out=self._packed)
-        else:
-            self._packed = ops.pack_conv_weight(v.detach(), g.detach() if g is not None else None, out=self._packed)
-        return self._packed
+            return self._cached("_packed", ops.pack_convtr_weight, self.stride)
+        return self._cached("_packed", ops.pack_conv_weight)
 
     def packed_rows(self):
         """ConvTranspose1d weights for the all-phases launch (ops.pack_convtr_weight_rows)."""
-        if self._rows is not None and self.freeze_packed:
-            return self._rows
-        v = self.weight_v if self.weight_norm else self.weight
-        g = self.weight_g if self.weight_norm else None
-        self._rows = ops.pack_convtr_weight_rows(v.detach(), g.detach() if g is not None else None, self.stride, out=self._rows)
-        return self._rows
+        return self._cached("_rows", ops.pack_convtr_weight_rows, self.stride)
 
     def packed_rows_split(self):
         """ConvTranspose1d weights for the all-phases launch on the split-bf16 GEMM kernel: (buffer, rows)."""
-        if self._rows_split is not None and self.freeze_packed:
-            return self._rows_split
-        v = self.weight_v if self.weight_norm else self.weight
-        g = self.weight_g if self.weight_norm else None
-        prev = self._rows_split[0] if self._rows_split is not None else None
-        self._rows_split = ops.pack_convtr_weight_rows_split(v.detach(), g.detach() if g is not None else None, self.stride, out=prev)
-        return self._rows_split
+        return self._cached("_rows_split", ops.pack_convtr_weight_rows_split, self.stride)
 
     def packed_split_strided(self, stride):
         """Split GEMM weights of a strided conv (stride < k <= 2 * stride), ops.pack_gemm_weight_split(in_stride=stride)."""
-        if self._split is not None and self.freeze_packed:
-            return self._split
-        v = self.weight_v if self.weight_norm else self.weight
-        g = self.weight_g if self.weight_norm else None
-        self._split = ops.pack_gemm_weight_split(v.detach(), g.detach() if g is not None else None, out=self._split, in_stride=stride)
-        return self._split
+        return self._cached("_split", ops.pack_gemm_weight_split, in_stride=stride)
 
     def packed_split(self):
         """The same weights as three exact bf16 planes (ops.pack_conv_weight_split) for the k = 7 convs."""
-        if self._split is not None and self.freeze_packed:
-            return self._split
-        v = self.weight_v if self.weight_norm else self.weight
-        g = self.weight_g if self.weight_norm else None
-        self._split = ops.pack_conv_weight_split(v.detach(), g.detach() if g is not None else None, out=self._split)
-        return self._split
+        return self._cached("_split", ops.pack_conv_weight_split)
 
     def _apply(self, fn, *a, **kw):
         self._packed = None  # device / dtype moves invalidate the packed copies
@@ -109,9 +92,9 @@ class _Norm(nn.Module):
         setattr(self, name, weights)
 
 
-# Short clips through the split GEMM kernel as one flattened signal (SConv1d._run_flat, SConvTranspose1d.run): inference only.
+# Short clips through the split GEMM kernel as one flattened signal (ops.conv1d_flat / conv_transpose1d_flat): inference only.
 FLAT_SHORT_CLIPS = True
-FLAT_STRIDE1 = True      # wide stride-1 k = 7 convs on short clips (SConv1d._run_flat_stride1)
+FLAT_STRIDE1 = True      # wide stride-1 k = 7 convs on short clips too
 
 
 class SConv1d(nn.Module):
@@ -130,94 +113,32 @@ class SConv1d(nn.Module):
     def w(self):
         return self.conv.conv
 
+    def plan(self, B, T, alpha_in=False, plain=True, res=False):
+        """The inference forward's variant of the conv rule (convplan.plan_conv) for B clips of T columns."""
+        return ops.plan_conv(self.w.c_out, self.w.c_in, self.kernel_size, self.stride, self.dilation, B, T, -(-T // self.stride),
+                             alpha_in=alpha_in, plain=plain, res=res, causal_reflect=self.causal and self.pad_mode == ops.PAD_REFLECT,
+                             grad=torch.is_grad_enabled(), c_out_mult16=False, tail="always", flat_infer=FLAT_SHORT_CLIPS,
+                             flat_stride1=FLAT_STRIDE1)
+
     def run(self, x, alpha_in=None, alpha_out=None, res=None, act=ops.ACT_NONE, alpha_y2=None, want_y=True):
         """alpha_y2: additionally emit snake(y, alpha_y2) for the next Snake->conv (returns (y, y2))."""
-        w = self.w
-        split = None
-        if (ops.BF16_SPLIT and self.kernel_size in (3, 5, 7) and self.stride == 1 and alpha_in is None and w.c_in % 16 == 0
-                and w.c_out > 2 and x.shape[0] * x.shape[-1] > 640 and (self.kernel_size == 7 or (w.c_in >= 64 and w.c_out > 32))):
-            split = w.packed_split()
-        elif (self.kernel_size == 1 and self.stride == 1 and alpha_in is None
-              and ops.gemm_split_ok(w.c_out, w.c_in, 1, x.shape[0] * x.shape[-1])
-              and not (w.c_in == w.c_out and w.c_in in (256, 384) and x.shape[0] * x.shape[-1] >= 65536)):
-            # (the C = 256 / 384 ResidualUnit tails stay on the streaming k = 1 kernel: -0.7 ms per B = 32 forward, round 4)
-            split = w.packed_split()          # 1x1 with many channels: split-bf16 GEMM (conv1d_gemm_split.hip)
-        elif (self.stride == 2 and alpha_in is None and alpha_out is None and res is None and act == ops.ACT_NONE and self.dilation == 1
-              and isinstance(x, torch.Tensor)
-              and ops.pw_taps_ok(w.c_in, w.c_out, self.kernel_size, 2, False, x.shape[0], -(-x.shape[-1] // 2))):
-            pass                              # few channels: the streaming kernel with taps takes the fp32 pack (fac_conv_desc.pw_split)
-        elif (self.stride > 1 and alpha_in is None and self.dilation == 1
-              and ops.gemm_split_strided_ok(w.c_out, w.c_in, self.kernel_size, self.stride, x.shape[0], -(-x.shape[-1] // self.stride))):
-            split = w.packed_split_strided(self.stride)     # downsampling conv: 2 taps over `stride` phase sub-signals
-        elif (FLAT_SHORT_CLIPS and self.stride > 1 and alpha_in is None and res is None and self.dilation == 1 and self.causal
-              and self.pad_mode == ops.PAD_REFLECT and self.kernel_size == 2 * self.stride and x.shape[-1] % self.stride == 0
-              and x.shape[-1] > self.stride and not torch.is_grad_enabled()
-              and ops.gemm_split_strided_ok(w.c_out, w.c_in, self.kernel_size, self.stride, 1,
-                                            x.shape[0] * (x.shape[-1] // self.stride + 1) - 1)):
-            return self._run_flat(x, alpha_out, act, alpha_y2, want_y)
-        if (FLAT_SHORT_CLIPS and FLAT_STRIDE1 and split is not None and self.stride == 1 and self.kernel_size == 7 and res is None
-                and self.causal and self.pad_mode == ops.PAD_REFLECT and not torch.is_grad_enabled() and isinstance(x, torch.Tensor)
-                and x.shape[0] >= 4 and (self.kernel_size - 1) * self.dilation < x.shape[-1] <= 224 and w.c_in * w.c_out >= 1 << 20):
-            return self._run_flat_stride1(x, alpha_out, act, alpha_y2, want_y, split)
-        if split is not None and self.stride > 1:      # split GEMM over the phase sub-signals: P8 input where it pays (ops.p8_prepass)
-            x = ops.p8_prepass(x, 2.0 * w.c_out * self.kernel_size / (4.0 * self.stride))
-        return ops.conv1d(x, w.packed() if split is None else None, w.c_out, self.kernel_size, bias=w.bias,
-                          stride=self.stride, dilation=self.dilation, pad_mode=self.pad_mode, alpha_in=alpha_in,
+        w, k, s_ = self.w, self.kernel_size, self.stride
+        B, _, T = x.shape       # (x is an fp32 tensor: no caller hands a P8 to a module, so the old chains' isinstance guards are gone)
+        plan = self.plan(B, T, alpha_in is not None, alpha_out is None and res is None and act == ops.ACT_NONE, res is not None)
+        split = (w.packed_split_strided(s_) if plan.layout == ops.W_GEMM_STRIDED
+                 else w.packed_split() if plan.layout in (ops.W_TAPS, ops.W_GEMM) else None)
+        if plan.form != ops.PER_CLIP:
+            # every clip reflect-padded on the left (the causal padding of dac/model/encodec.py:212-222, materialised: data movement
+            # only; strided: T % s == 0, so there is no right padding) and all of them laid out as ONE signal
+            P = (k - 1) * self.dilation + 1 - s_
+            return ops.conv1d_flat(torch.nn.functional.pad(x, (P, 0), mode="reflect"), split, w.c_out, k, s_, T // s_,
+                                   dilation=self.dilation, bias=w.bias, p8=plan.p8, alpha_out=alpha_out, act=act, alpha_y2=alpha_y2,
+                                   want_y=want_y)
+        x = ops.p8_prepass(x, plan.p8)      # split GEMM over the phase sub-signals: P8 input where it pays
+        return ops.conv1d(x, w.packed() if split is None else None, w.c_out, k, bias=w.bias,
+                          stride=s_, dilation=self.dilation, pad_mode=self.pad_mode, alpha_in=alpha_in,
                           alpha_out=alpha_out, res=res, act=act, causal=self.causal, alpha_y2=alpha_y2, want_y=want_y,
                           w_split=split)
-
-    def _run_flat(self, x, alpha_out, act, alpha_y2, want_y):
-        """Short clips (the 160-frame latent rate): per-clip column tiles would be half empty, so the split GEMM kernel refuses them
-        and the launch fell to the fp32 tile at ~72 TFLOP/s.  No new kernel is needed: every clip is reflect-padded on the left
-        by k - s = s samples (the causal padding of dac/model/encodec.py:212-222; T % s == 0, so there is no right padding) and
-        the padded clips are laid one after another as ONE signal of B (T / s + 1) s samples; the same strided conv without
-        padding then computes every real output exactly (output t of clip b is column b (T / s + 1) + t) plus one junk column
-        per clip where the window straddles two clips, which is dropped on the way back to (B, C, T / s)."""
-        w, s_ = self.w, self.stride
-        B, c_in, T = x.shape
-        n = T // s_
-        xp = torch.nn.functional.pad(x, (s_, 0), mode="reflect")                    # data movement only
-        xf = xp.permute(1, 0, 2).reshape(1, c_in, B * (n + 1) * s_)
-        t_out = B * (n + 1) - 1
-        xf = ops.p8_prepass(xf, 2.0 * w.c_out * self.kernel_size / (4.0 * s_))
-        got = ops.conv1d(xf, None, w.c_out, self.kernel_size, bias=w.bias, stride=s_, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=t_out,
-                         alpha_out=alpha_out, act=act, alpha_y2=alpha_y2, want_y=want_y, w_split=w.packed_split_strided(s_))
-
-        def back(y):
-            if y is None:
-                return None
-            full = torch.empty(w.c_out, B * (n + 1), device=y.device, dtype=y.dtype)
-            full[:, :t_out] = y[0]
-            return full.reshape(w.c_out, B, n + 1)[:, :, :n].permute(1, 0, 2).contiguous()
-
-        return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
-
-    def _run_flat_stride1(self, x, alpha_out, act, alpha_y2, want_y, split):
-        """The stride-1 counterpart of `_run_flat` (round 5) for the decoder's input conv 1024 -> 1536 k 7 at the 160-frame latent
-        rate, which fills 160 of the 256 columns of the split kernel's time tile.  Every clip is reflect-padded on the left by
-        P = (k - 1) d (the causal padding of dac/model/encodec.py:212-222, materialised: data movement only) and the padded clips are
-        laid one after another as ONE signal of B (T + P) samples; the same conv WITHOUT padding computes output t of clip b at column
-        b (T + P) + t -- the same products in the same order as the per-clip launch, so the same bits -- plus P junk columns per
-        clip where the window straddles two clips, dropped on the way back.  Measured at B = 32: 0.756 -> 0.517 ms (149 -> 226
-        TFLOP/s-eq).  The k = 3 / k = 5 layers at the same rate gain nothing (0.269 -> 0.261, 0.059 -> 0.055 ms: few taps per staged
-        column, they are bound by staging, not by tile columns) and stay on the per-clip launch."""
-        w = self.w
-        B, c_in, T = x.shape
-        P = (self.kernel_size - 1) * self.dilation
-        xp = torch.nn.functional.pad(x, (P, 0), mode="reflect")
-        xf = xp.permute(1, 0, 2).reshape(1, c_in, B * (T + P))
-        t_out = B * (T + P) - P
-        got = ops.conv1d(xf, None, w.c_out, self.kernel_size, bias=w.bias, stride=1, dilation=self.dilation, pad_left=0,
-                         pad_mode=ops.PAD_ZERO, t_out=t_out, alpha_out=alpha_out, act=act, alpha_y2=alpha_y2, want_y=want_y, w_split=split)
-
-        def back(y):
-            if y is None:
-                return None
-            full = torch.empty(w.c_out, B * (T + P), device=y.device, dtype=y.dtype)
-            full[:, :t_out] = y[0]
-            return full.reshape(w.c_out, B, T + P)[:, :, :T].permute(1, 0, 2).contiguous()
-
-        return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
 
     def forward(self, x):
         return self.run(x)
@@ -238,30 +159,22 @@ class SConvTranspose1d(nn.Module):
     def w(self):
         return self.convtr.convtr
 
+    def plan(self, B, T, alpha_in=False):
+        return ops.plan_convtr(self.w.c_in, self.w.c_out, self.stride, B, T, causal=self.causal, alpha_in=alpha_in,
+                               grad=torch.is_grad_enabled(), flat_infer=FLAT_SHORT_CLIPS)
+
     def run(self, x, alpha_in=None, alpha_y2=None):
         w = self.w
-        if (self.causal and alpha_in is None and isinstance(x, torch.Tensor)
-                and ops.pw_taps_ok(w.c_in, w.c_out, 2 * self.stride, self.stride, True, x.shape[0], x.shape[-1])):
-            wp = w.packed_rows()              # stride 2, few channels: the streaming kernel with taps (conv1d_pw_split.hip)
-        elif ops.convtr_split_ok(w.c_in, w.c_out, self.stride, x.shape[0], x.shape[-1], self.causal, alpha_in):
-            wp = w.packed_rows_split()
-            x = ops.p8_prepass(x, 2.0 * w.c_out * 2 * self.stride / 4.0)      # all output phases as GEMM rows: 2 s C_out MACs per input sample
-        elif (FLAT_SHORT_CLIPS and not torch.is_grad_enabled() and x.shape[-1] < 256
-              and ops.convtr_split_ok(w.c_in, w.c_out, self.stride, 1, x.shape[0] * (x.shape[-1] + 1), self.causal, alpha_in)):
-            # short clips: ONE signal of B (T + 1) columns with a zero column in front of every clip (the x[t - 1] of its first
-            # frame); the s output samples of that column are dropped on the way back (see SConv1d._run_flat)
-            B, c_in, T = x.shape
-            xf = torch.cat([torch.zeros(B, c_in, 1, device=x.device, dtype=x.dtype), x], -1).permute(1, 0, 2).reshape(1, c_in, B * (T + 1))
-            xf = ops.p8_prepass(xf, 2.0 * w.c_out * 2 * self.stride / 4.0)
-            got = ops.conv_transpose1d(xf, w.packed_rows_split(), w.c_out, self.stride, bias=w.bias, alpha_y2=alpha_y2, causal=True)
-
-            def back(y):
-                return y.reshape(w.c_out, B, (T + 1) * self.stride)[:, :, self.stride:].permute(1, 0, 2).contiguous()
-
-            return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
-        else:
-            wp = w.packed_rows() if ops.convtr_rows_ok(x.shape[-1], self.stride, self.causal) else w.packed()
-        return ops.conv_transpose1d(x, wp, w.c_out, self.stride, bias=w.bias, alpha_in=alpha_in,
+        B, c_in, T = x.shape
+        plan = self.plan(B, T, alpha_in is not None)
+        if plan.layout == ops.TR_FLAT:
+            # short clips: ONE signal of B (T + 1) columns with a zero column in front of every clip (the x[t - 1] of its first frame)
+            xz = torch.cat([torch.zeros(B, c_in, 1, device=x.device, dtype=x.dtype), x], -1)
+            return ops.conv_transpose1d_flat(xz, w.packed_rows_split(), w.c_out, self.stride, trim=self.stride, bias=w.bias,
+                                             alpha_y2=alpha_y2, p8=plan.p8)
+        wp = (w.packed_rows_split() if plan.layout == ops.TR_ROWS_SPLIT
+              else w.packed() if plan.layout == ops.TR_POLYPHASE else w.packed_rows())
+        return ops.conv_transpose1d(ops.p8_prepass(x, plan.p8), wp, w.c_out, self.stride, bias=w.bias, alpha_in=alpha_in,
                                     alpha_y2=alpha_y2, causal=self.causal)
 
     def forward(self, x):
@@ -313,17 +226,16 @@ class SLSTM(nn.Module):
         for l in range(self.num_layers):
             p = self.lstm
             w_raw = getattr(p, f"weight_ih_l{l}").detach()
-            use_split = ops.gemm_split_ok(4 * H, H, 1, inp.shape[1] * inp.shape[2])
-            w_ih = None if use_split else ops.pack_conv_weight(w_raw)
-            w_ih_split = ops.pack_gemm_weight_split(w_raw) if use_split else None
+            plan = ops.plan_gemm(4 * H, H, inp.shape[1] * inp.shape[2])
+            w_ih = ops.pack_conv_weight(w_raw) if plan.layout == ops.W_FP32 else None
+            w_ih_split = ops.pack_gemm_weight_split(w_raw) if plan.layout == ops.W_GEMM else None
             bias = ops.add(getattr(p, f"bias_ih_l{l}").detach(), getattr(p, f"bias_hh_l{l}").detach())
             w_hh = getattr(p, f"weight_hh_l{l}").detach()
             persist = ops.lstm_persist_ok(H, B)
             T_, BP = inp.shape[1], inp.shape[2]
             # one GEMM over every (t, b): the channel-major buffer is a (1, H, T*BP) "signal"
             sig = inp.view(1, H, T_ * BP)
-            if use_split:
-                sig = ops.p8_prepass(sig, 2.0 * 4 * H / 4.0)
+            sig = ops.p8_prepass(sig, plan.p8)
             with ops.flop_scale(B / BP):
                 pre = ops.conv1d(sig, w_ih, 4 * H, 1, bias=bias, pad_left=0, t_out=T_ * BP,
                                  pad_mode=ops.PAD_ZERO, w_split=w_ih_split)

@@ -55,7 +55,7 @@ class _SpectralScale:
         """frames (N, win, n_frames) -> (N, 2F, n_frames) [Re | Im]: the windowed-DFT GEMM."""
         two_f = 2 * self.F
         with ops.flop_key("dft"):
-            if ops.gemm_split_ok(two_f, self.win, 1, frames.shape[0] * n_frames):
+            if ops.plan_gemm(two_f, self.win, frames.shape[0] * n_frames).layout == ops.W_GEMM:
                 if self._basis_split is None:
                     self._basis_split = ops.pack_gemm_weight_split(self.basis_t)
                 return ops.conv1d(frames, None, two_f, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n_frames, w_split=self._basis_split)
@@ -64,7 +64,7 @@ class _SpectralScale:
     def dft_adjoint(self, dspec, n_frames):
         """dspec (N, 2F, n_frames) -> gradient of the frames (N, win, n_frames): the transposed GEMM."""
         with ops.flop_key("dft"):
-            if ops.gemm_split_ok(self.win, 2 * self.F, 1, dspec.shape[0] * n_frames):
+            if ops.plan_gemm(self.win, 2 * self.F, dspec.shape[0] * n_frames).layout == ops.W_GEMM:
                 if self._basis_split_t is None:
                     self._basis_split_t = ops.pack_gemm_weight_split_t(self.basis_t)
                 return ops.conv1d(dspec, None, self.win, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n_frames, w_split=self._basis_split_t)

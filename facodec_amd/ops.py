@@ -10,6 +10,8 @@ import torch
 
 from . import _lib
 from .wprep import prepared
+# the layout / launch-form policy, its predicates and the layout names live in convplan.py; re-exported for call sites, tests and tools
+from .convplan import *  # noqa: F401,F403
 from ._lib import ConvDesc, VqDesc, VqDecodeDesc, PAD_REFLECT, PAD_ZERO, ACT_NONE, ACT_TANH, ACT_MISH, ACT_LOG_MEL, ACT_GATE, ACT_WN_RES_SKIP  # noqa: F401
 
 
@@ -129,10 +131,6 @@ def convtr_rows_pad(c_out, stride):
     return -(-c_out // cpt) * 128
 
 
-def convtr_rows_ok(t_in, stride, causal=True):
-    return CONVTR_ROWS and causal and 2 <= stride <= 16 and t_in >= CONVTR_ROWS_MIN_T
-
-
 @prepared
 def pack_convtr_weight_rows(v, g, stride, out=None):
     """ConvTranspose1d (C_in, C_out, 2*stride) -> (cin_pad(C_in), 2, rows) with rows = (channel, phase) pairs in 128-row
@@ -147,22 +145,6 @@ def pack_convtr_weight_rows(v, g, stride, out=None):
     _lib.check(_lib.load().fac_pack_convtr_w_rows(_ptr(v), _ptr(scale), _ptr(out), c_in, c_out, stride, _stream()),
                "fac_pack_convtr_w_rows")
     return out
-
-
-def convtr_split_ok(c_in, c_out, stride, batch, t_in, causal=True, alpha_in=None):
-    """All-phases ConvTranspose1d on the split-bf16 GEMM kernel (conv1d_gemm_split.hip, K = 2): mirrors conv_gsplit_ok."""
-    return (BF16_SPLIT and causal and alpha_in is None and 2 <= stride <= 16 and c_in >= 64
-            and t_in >= 256 and batch * t_in >= 1024 and c_out * stride >= 64)
-
-
-def convtr_weight_for(v, g, stride, t_in, causal=True, batch=1, alpha_in=None):
-    """The packed weights conv_transpose1d wants for an input of `batch` clips of t_in columns: (split GEMM buffer, rows) for the
-    bf16-pipe launch, the fp32 rows layout (opt-in) or the polyphase layout."""
-    if causal and alpha_in is None and pw_taps_ok(v.shape[0], v.shape[1], 2 * stride, stride, True, batch, t_in):
-        return pack_convtr_weight_rows(v, g, stride)          # stride 2, few channels: the streaming kernel with taps
-    if convtr_split_ok(v.shape[0], v.shape[1], stride, batch, t_in, causal, alpha_in):
-        return pack_convtr_weight_rows_split(v, g, stride)
-    return pack_convtr_weight_rows(v, g, stride) if convtr_rows_ok(t_in, stride, causal) else pack_convtr_weight(v, g, stride)
 
 
 # --------------------------------------------------------------------------------- conv (K1-K4)
@@ -405,25 +387,7 @@ def _launch_conv(d, what):
     _PROFILE.records.append((name, flops, e0, e1))
 
 
-# 1- / 2-tap convs as split-bf16 GEMMs (conv1d_gemm_split.hip): policy of who packs the GEMM layout.
-GEMM_SPLIT_MIN_CIN = 256
-
-
-def gemm_split_ok(c_out, c_in, k, n_cols, t_out=None):
-    """1- / 2-tap stride-1 conv worth the bf16 pipe: many input channels (below ~256 the k = 1 layers are HBM-bound and the
-    streaming kernel conv1d_pw.hip is the right tool), at least half a row tile, enough columns."""
-    if not (BF16_SPLIT and k in (1, 2)):
-        return False
-    if c_in < GEMM_SPLIT_MIN_CIN or c_out < 64 or n_cols < 1024:
-        return False
-    return k == 1 or (t_out is not None and t_out >= 256)
-
-
-def gemm_split_strided_ok(c_out, c_in, k, stride, batch, t_out):
-    """Strided conv with stride < k <= 2 * stride (the encoder's k = 2 s downsampling convs, the period discriminators' k = 5
-    stride-3 convs) as a 2-tap split GEMM over the `stride` phase sub-signals: mirrors conv_gsplit_ok."""
-    return (BF16_SPLIT and 1 < stride <= 16 and stride < k <= 2 * stride and c_in >= 32
-            and c_out >= 64 and t_out >= 256 and batch * t_out >= 1024)
+GEMM_SPLIT_MIN_CIN = 256     # 1- / 2-tap convs as split-bf16 GEMMs (conv1d_gemm_split.hip): fewest input channels (convplan.gemm_split_ok)
 
 
 @prepared
@@ -460,16 +424,6 @@ def pack_gemm_weight_split_t(w, out=None):
     _lib.check(lib.fac_pack_gemm_w_split(_ptr(w), 1, c_in, 1, None, out.data_ptr(), c_in, c_out, 1, 1, _stream()),
                "fac_pack_gemm_w_split(transposed)")
     return out
-
-
-
-
-def split2_ok(c_out, k, k1, stride, n_cols):
-    """Few-output-channel 9- / 3-tap conv (plain or two-level, taps per level k1) for conv1d_bsplit2.hip: mirrors
-    conv_bsplit2_ok."""
-    kv = k1 if 0 < k1 < k else k
-    return (BF16_SPLIT and 8 <= c_out <= 32 and ((kv == 9 and stride in (1, 2)) or (kv == 3 and stride == 1))
-            and n_cols >= 4096)
 
 
 @prepared
@@ -577,8 +531,9 @@ P8_PREPASS_MIN_FLOP_PER_BYTE = 450.0
 
 
 def p8_prepass(x, flop_per_in_byte):
-    """x (B, C, T) fp32 -> P8 when the policy above says the pass pays for itself (inference only: no autograd node), else x."""
-    if (P8_PREPASS_MIN_FLOP_PER_BYTE <= 0 or flop_per_in_byte < P8_PREPASS_MIN_FLOP_PER_BYTE or not BF16_SPLIT or isinstance(x, P8)
+    """x (B, C, T) fp32 -> P8 when the policy above says the pass pays for itself (inference only: no autograd node), else x.
+    flop_per_in_byte: a plan's `p8` figure (None: the plan's launch takes fp32 input)."""
+    if (flop_per_in_byte is None or P8_PREPASS_MIN_FLOP_PER_BYTE <= 0 or flop_per_in_byte < P8_PREPASS_MIN_FLOP_PER_BYTE or not BF16_SPLIT or isinstance(x, P8)
             or torch.is_grad_enabled() or not x.is_cuda or x.shape[1] % 8 != 0 or x.shape[0] * (x.shape[1] // 8) * x.shape[2] * 16 >= (1 << 32)):
         return x
     return to_p8(x)
@@ -712,76 +667,74 @@ def conv_transpose1d(x, w_packed, c_out, stride, bias=None, alpha_in=None, out=N
     return (out, y2) if alpha_y2 is not None else out
 
 
-# Short clips on the split GEMM kernel as ONE flattened signal (layers.SConv1d._run_flat / SConvTranspose1d.run, round 4, inference):
-# the same trick for the TRAINING launches (round 6).  Per-clip column tiles of that kernel would be half empty at the 160-frame
-# latent rate, so those launches (the encoder's last downsampling conv, the decoder's first ConvTranspose1d, and their data
-# gradients) fell to the fp32 128 x 160 tile at 38 - 63 TFLOP/s (profiles/r06_train_layers_serial.log: 3.9 ms per step).
+# Short clips on the split GEMM kernel as ONE flattened signal (conv1d_flat / conv_transpose1d_flat; round 4, inference) for the
+# TRAINING launches too (round 6): per-clip column tiles would be half empty at the 160-frame latent rate, so the encoder's last strided
+# conv, the decoder's first ConvTranspose1d and their data gradients fell to the fp32 128 x 160 tile (r06_train_layers_serial.log: 3.9 ms).
 FLAT_TRAIN = True
 # k = 1 ResidualUnit tails at C = 64 .. 384 on the bf16 pipe inside the streaming kernel (conv1d_pw_split.hip); 0: fp32 MFMAs (rounds 2-5)
 PW_SPLIT = os.environ.get("FAC_PW_SPLIT", "1") != "0"
-
-
-def pw_split_tail_ok(c_in, c_out, cols):
-    """C = 256 / 384 ResidualUnit tails (and their data gradients) of the TRAINING step on the streaming bf16-plane kernel instead
-    of the split GEMM kernel (round 6: 0.29 -> 0.2 ms per launch at 16 x 4800 columns)."""
-    return BF16_SPLIT and PW_SPLIT and c_in == c_out and c_in in (256, 384) and cols >= 65536
-
-
 # stride-2 layers with few channels on the streaming kernel with taps (conv1d_pw_split.hip, conv1d_pwt_kernel); follows PW_SPLIT
 PW_TAPS = True
 
 
-def pw_taps_ok(c_in, c_out, k, stride, transposed, batch, t_out):
-    """Mirror of conv_pwt_ok: the causal ConvTranspose1d with stride 2 (all output phases as rows, fp32 weights of
-    pack_convtr_weight_rows) or a k = 4 stride-2 conv (fp32 weights of pack_conv_weight) whose C_in * taps <= 384 virtual channels
-    fit the LDS as bf16 planes for 64 output rows; t_out = output columns per clip at the INPUT rate (transposed) / output rate."""
-    if not (BF16_SPLIT and PW_SPLIT and PW_TAPS and stride == 2):
-        return False
-    taps, rows = (2, 2 * c_out) if transposed else (4, c_out)
-    if k != 4 or (c_in * taps) % 64 or c_in * taps > 384 or rows % 64:
-        return False
-    return batch * ((t_out + 31) // 32) >= 2 * (256 // (rows // 64)) * 12
+def pack_conv_for(layout, v, g, stride=1, k1=0, scale=None):
+    """(fp32 pack, split buffer), one of them None: the weights in the layout a ConvPlan names."""
+    if layout in (W_FP32, W_FP32_PW_TAPS):
+        return pack_conv_weight(v, g, scale=scale), None
+    if layout == W_GEMM_STRIDED:
+        return None, pack_gemm_weight_split(v, g, in_stride=stride, scale=scale)
+    if layout == W_SPLIT2:
+        return None, pack_conv_weight_split2(v, g, k1, scale=scale)
+    return None, pack_conv_weight_split(v, g, scale=scale)          # W_TAPS / W_GEMM: fp32-grade split on the bf16 pipe
 
 
-def flat_strided_ok(c_out, c_in, k, s, batch, n_out):
-    """A k = 2 s strided conv over `batch` clips of n_out outputs each, too short for per-clip tiles but long enough as one signal."""
-    return (FLAT_TRAIN and k == 2 * s and s > 1 and n_out < 256 and not gemm_split_strided_ok(c_out, c_in, k, s, batch, n_out)
-            and gemm_split_strided_ok(c_out, c_in, k, s, 1, batch * (n_out + 1) - 1))
+def pack_convtr_for(layout, v, g, stride):
+    """The weights conv_transpose1d wants in the layout a ConvTrPlan names ((split GEMM buffer, rows) for the bf16-pipe launches)."""
+    if layout in (TR_ROWS_SPLIT, TR_FLAT):
+        return pack_convtr_weight_rows_split(v, g, stride)
+    return pack_convtr_weight(v, g, stride) if layout == TR_POLYPHASE else pack_convtr_weight_rows(v, g, stride)
 
 
-def conv1d_flat_strided(xp, w_split, c_out, k, s, bias=None):
-    """xp (B, C_in, (n + 1) s): every clip already carries its s columns of padding (reflected on the left for the causal forward
-    conv, zeros on the right for the data gradient of a transposed conv).  The clips are laid one after another as ONE signal and
-    the strided conv runs WITHOUT padding: output column b (n + 1) + t is output t of clip b (same products, same order as the
-    per-clip launch), plus one junk column per clip where the window straddles two clips, dropped on the way back -> (B, C_out, n)."""
+def convtr_weight_for(v, g, stride, t_in, causal=True, batch=1, alpha_in=None):
+    """The packed weights of the per-clip launch for an input of `batch` clips of t_in columns."""
+    return pack_convtr_for(plan_convtr(v.shape[0], v.shape[1], stride, batch, t_in, causal=causal, alpha_in=alpha_in is not None).layout,
+                           v, g, stride)
+
+
+def conv1d_flat(xp, w_split, c_out, k, s, n, dilation=1, bias=None, p8=None, alpha_out=None, act=ACT_NONE, alpha_y2=None, want_y=True):
+    """Short clips as ONE signal.  xp (B, C_in, L): every clip already padded to length L -- reflected on the left by k - s = s
+    samples (causal strided conv, L = (n + 1) s) or by (k - 1) d samples (causal stride-1 conv, L = n + (k - 1) d), or zeros
+    around the dy of a transposed conv.  The clips are laid one after another and the conv runs WITHOUT padding at stride s:
+    with pitch = L // s output columns per clip, column b pitch + t is output t of clip b -- the same products in the same order as
+    the per-clip launch, so the same bits -- and the pitch - n columns where the window straddles two clips are dropped on the way
+    back -> (B, C_out, n); t_out = B pitch - (pitch - n).  p8: the plan's figure for ops.p8_prepass.  Returns what conv1d returns."""
     B, c_in, L = xp.shape
-    n = L // s - 1
-    xf = xp.permute(1, 0, 2).reshape(1, c_in, B * L)
-    t_out = B * (n + 1) - 1
-    xf = p8_prepass(xf, 2.0 * c_out * k / (4.0 * s))
-    y = conv1d(xf, None, c_out, k, bias=bias, stride=s, pad_left=0, pad_mode=PAD_ZERO, t_out=t_out, w_split=w_split)
-    full = torch.empty(c_out, B * (n + 1), device=y.device, dtype=y.dtype)
-    full[:, :t_out] = y[0]
-    return full.reshape(c_out, B, n + 1)[:, :, :n].permute(1, 0, 2).contiguous()
+    pitch = L // s
+    xf = p8_prepass(xp.permute(1, 0, 2).reshape(1, c_in, B * L), p8)                # data movement only
+    t_out = B * pitch - (pitch - n)
+    got = conv1d(xf, None, c_out, k, bias=bias, stride=s, dilation=dilation, pad_left=0, pad_mode=PAD_ZERO, t_out=t_out,
+                 alpha_out=alpha_out, act=act, alpha_y2=alpha_y2, want_y=want_y, w_split=w_split)
+
+    def back(y):
+        if y is None:
+            return None
+        full = torch.empty(c_out, B * pitch, device=y.device, dtype=y.dtype)
+        full[:, :t_out] = y[0]
+        return full.reshape(c_out, B, pitch)[:, :, :n].permute(1, 0, 2).contiguous()
+
+    return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
 
 
-def flat_convtr_ok(c_in, c_out, s, batch, t_cols):
-    """An all-phases ConvTranspose1d launch over `batch` clips of t_cols input columns each (incl. their zero column), short clips."""
-    return (FLAT_TRAIN and t_cols < 256 and not convtr_split_ok(c_in, c_out, s, batch, t_cols)
-            and convtr_split_ok(c_in, c_out, s, 1, batch * t_cols))
-
-
-def conv_transpose1d_flat(xz, v, g, s, bias=None):
-    """xz (B, C_in, T'): clips that already hold their zero column (in FRONT for the forward transposed conv: the x[t - 1] of a
-    clip's first frame; at the END for the data gradient of a strided conv, where it is the next clip's x[t - 1] as well).  One
-    signal of B T' columns through the all-phases split-GEMM launch -> (B, C_out, T' s): per clip exactly the per-clip launch's
-    output (y[t s + p] = W[p] x[t] + W[p + s] x[t - 1])."""
+def conv_transpose1d_flat(xz, w_rows_split, c_out, s, trim=0, bias=None, alpha_y2=None, p8=None):
+    """xz (B, C_in, T'): clips that already hold their zero column -- in FRONT for the forward transposed conv (the x[t - 1] of a
+    clip's first frame; trim = s drops that column's s output samples), at the END for the data gradient of a strided conv (where
+    it is the next clip's x[t - 1] as well; nothing to trim).  One signal of B T' columns through the all-phases split-GEMM launch
+    -> (B, C_out, T' s - trim): per clip exactly the per-clip launch's output (y[t s + p] = W[p] x[t] + W[p + s] x[t - 1])."""
     B, c_in, T1 = xz.shape
-    c_out = v.shape[1]
-    xf = xz.permute(1, 0, 2).reshape(1, c_in, B * T1)
-    xf = p8_prepass(xf, 2.0 * c_out * 2 * s / 4.0)
-    y = conv_transpose1d(xf, pack_convtr_weight_rows_split(v, g, s), c_out, s, bias=bias, causal=True)
-    return y.reshape(c_out, B, T1 * s).permute(1, 0, 2).contiguous()
+    xf = p8_prepass(xz.permute(1, 0, 2).reshape(1, c_in, B * T1), p8)
+    got = conv_transpose1d(xf, w_rows_split, c_out, s, bias=bias, alpha_y2=alpha_y2, causal=True)
+    back = lambda y: y.reshape(c_out, B, T1 * s)[:, :, trim:].permute(1, 0, 2).contiguous()   # noqa: E731
+    return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
 
 
 def snake(x, alpha, out=None):
@@ -1278,26 +1231,29 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
     pad_left = padding_total if causal else padding_total - padding_total // 2
     pad_right = (padding_total - pad_left) + extra
     tp = pad_left + t_in + pad_right
-    if (stride == 1 and BF16_SPLIT and c_in % 16 == 0 and c_out % 16 == 0 and B * tp > 640
-            and (k == 7 or (k in (3, 5) and c_out >= 64 and c_in > 32))):
-        # the flipped / transposed conv on the bf16 pipe too: materialise w = g v/||v||, swap channels, flip taps
-        wt = flipped_weight(v, g, scale)                                   # (C_in, C_out, K) = weights of the bwd conv
-        dxpad = conv1d(dy, None, c_in, k, dilation=dilation, pad_left=(k - 1) * dilation, pad_mode=PAD_ZERO, t_out=tp,
-                       w_split=pack_conv_weight_split(wt))
-    elif stride == 1 and k == 1 and gemm_split_ok(c_in, c_out, 1, B * tp) and not pw_split_tail_ok(c_in, c_out, B * tp):
-        w = rows_fma(v, scale) if g is not None else v                    # 1x1: the transposed GEMM on the bf16 pipe
-        dxpad = conv1d(dy, None, c_in, 1, pad_left=0, pad_mode=PAD_ZERO, t_out=tp, w_split=pack_gemm_weight_split_t(w))
-    elif stride == 1:
-        dxpad = conv1d(dy, pack_conv_weight_bwd(v, g, scale), c_in, k, dilation=dilation, pad_left=(k - 1) * dilation,
-                       pad_mode=PAD_ZERO, t_out=tp)
+    if stride == 1:
+        layout = plan_conv(c_in, c_out, k, 1, dilation, B, t_out, tp).layout       # the forward plan of the conv with the channels swapped
+        if layout == W_TAPS:
+            # the flipped / transposed conv on the bf16 pipe too: materialise w = g v/||v||, swap channels, flip taps
+            wt = flipped_weight(v, g, scale)                                   # (C_in, C_out, K) = weights of the bwd conv
+            dxpad = conv1d(dy, None, c_in, k, dilation=dilation, pad_left=(k - 1) * dilation, pad_mode=PAD_ZERO, t_out=tp,
+                           w_split=pack_conv_weight_split(wt))
+        elif layout == W_GEMM:
+            w = rows_fma(v, scale) if g is not None else v                    # 1x1: the transposed GEMM on the bf16 pipe
+            dxpad = conv1d(dy, None, c_in, 1, pad_left=0, pad_mode=PAD_ZERO, t_out=tp, w_split=pack_gemm_weight_split_t(w))
+        else:
+            dxpad = conv1d(dy, pack_conv_weight_bwd(v, g, scale), c_in, k, dilation=dilation, pad_left=(k - 1) * dilation,
+                           pad_mode=PAD_ZERO, t_out=tp)
     else:
         if k != 2 * stride or dilation != 1:
             raise NotImplementedError("strided bwd_data is built for the model's k = 2*stride convs")
         dy_ext = torch.cat([dy, torch.zeros(B, c_out, 1, device=dy.device)], dim=2)
-        if flat_convtr_ok(c_out, c_in, stride, B, t_out + 1):      # short clips: one flattened signal (the trailing zero column of a
-            dxpad = conv_transpose1d_flat(dy_ext, v, g, stride)    # clip is the x[t - 1] of the next clip's first frame)
+        plan = plan_convtr(c_out, c_in, stride, B, t_out + 1, flat_train_cols=t_out + 1)
+        wt = pack_convtr_for(plan.layout, v, g, stride)
+        if plan.layout == TR_FLAT:       # short clips: one flattened signal (the trailing zero column of a clip is the x[t - 1] of
+            dxpad = conv_transpose1d_flat(dy_ext, wt, c_in, stride, p8=plan.p8)      # the next clip's first frame)
         else:
-            dxpad = conv_transpose1d(dy_ext, convtr_weight_for(v, g, stride, dy_ext.shape[-1], batch=B), c_in, stride)
+            dxpad = conv_transpose1d(dy_ext, wt, c_in, stride)
         assert dxpad.shape[-1] == tp, (dxpad.shape, tp)
     if tp == t_in and FOLD_IN_PLACE in (1, 2):
         return dxpad                                  # no padding (the 1x1 convs): the padded gradient IS the gradient
@@ -1494,18 +1450,14 @@ def conv_transpose1d_bwd(x, dy, v, g, stride, causal=True):
     c_out, k = v.shape[1], v.shape[2]
     assert k == 2 * stride and dy.shape == (B, c_out, t_in * stride)
     shift = 0 if causal else stride - stride // 2
-    if pw_taps_ok(c_out, c_in, k, stride, False, B, t_in):         # stride 2, few channels: the streaming kernel with taps (fp32 pack)
-        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in)
-    elif gemm_split_strided_ok(c_in, c_out, k, stride, B, t_in):   # the strided conv of dy on the split GEMM kernel
-        dx = conv1d(dy, None, c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in,
-                    w_split=pack_gemm_weight_split(v, g, in_stride=stride))
-    elif flat_strided_ok(c_in, c_out, k, stride, B, t_in):
+    plan = plan_conv(c_in, c_out, k, stride, 1, B, t_in * stride, t_in, flat_train="zero")     # the strided forward conv of dy
+    wp, ws = pack_conv_for(plan.layout, v, g, stride)
+    if plan.form == FLAT_STRIDED:
         # short clips: every clip gets its s columns of zeros (shift in front, s - shift behind) and the clips run as one flattened
         # signal -- the kernel cannot offset inside the concatenation, so this is the one path that pads with a copy (as causal)
-        dx = conv1d_flat_strided(torch.nn.functional.pad(dy, (shift, stride - shift)), pack_gemm_weight_split(v, g, in_stride=stride),
-                                 c_in, k, stride)
+        dx = conv1d_flat(torch.nn.functional.pad(dy, (shift, stride - shift)), ws, c_in, k, stride, t_in, p8=plan.p8)
     else:
-        dx = conv1d(dy, pack_conv_weight(v, g), c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in)
+        dx = conv1d(dy, wp, c_in, k, stride=stride, pad_left=shift, pad_mode=PAD_ZERO, t_out=t_in, w_split=ws)
     dw = torch.empty(c_in, c_out, k, device=x.device, dtype=torch.float32)
     _bwd_weight_launch(dy, x, dw, B, c_out, t_in * stride, c_in, t_in, k, stride, 1, shift, PAD_ZERO)
     return dx, dw

@@ -199,16 +199,19 @@ class _PlainConv(nn.Module):
         self.bias = nn.Parameter(_uniform_(torch.empty(c_out), b))
         self.c_in, self.c_out, self.k = c_in, c_out, k
 
+    def plan(self, B, T):
+        """This class's variant of the conv rule (convplan.plan_conv): no C_out % 16, the channel floor at k = 7 too, no tail rule."""
+        return ops.plan_conv(self.c_out, self.c_in, self.k, 1, 1, B, T, T, c_out_mult16=False, floor_k=(3, 5, 7), tail=None)
+
     def run(self, x, pad=0, **kw):
-        if self.k == 1 and pad == 0 and ops.gemm_split_ok(self.c_out, self.c_in, 1, x.shape[0] * x.shape[-1]):
-            return ops.conv1d(x, None, self.c_out, 1, bias=self.bias.detach(), pad_left=0, pad_mode=ops.PAD_ZERO, t_out=x.shape[-1],
-                              w_split=ops.pack_gemm_weight_split(self.weight.detach()), **kw)      # 1x1, many channels: bf16 pipe
-        if (ops.BF16_SPLIT and self.k in (3, 5, 7) and self.c_in % 16 == 0 and self.c_in >= 64 and self.c_out > 32
-                and x.shape[0] * x.shape[-1] > 640):      # k = 5 convs of the style encoder: split-bf16 kernel (conv1d_bsplit.hip)
-            return ops.conv1d(x, None, self.c_out, self.k, bias=self.bias.detach(), pad_left=pad, pad_mode=ops.PAD_ZERO,
-                              t_out=x.shape[-1], w_split=ops.pack_conv_weight_split(self.weight.detach()), **kw)
-        return ops.conv1d(x, ops.pack_conv_weight(self.weight.detach()), self.c_out, self.k, bias=self.bias.detach(),
-                          pad_left=pad, pad_mode=ops.PAD_ZERO, t_out=x.shape[-1], **kw)
+        """`same` convs: pad = (k - 1) / 2 (the 1x1 convs are never padded)."""
+        layout, w = self.plan(x.shape[0], x.shape[-1]).layout, self.weight.detach()
+        if layout == ops.W_GEMM:                # 1x1, many channels: bf16 pipe
+            ws = ops.pack_gemm_weight_split(w)
+        else:                                   # k = 5 convs of the style encoder: split-bf16 kernel (conv1d_bsplit.hip)
+            ws = ops.pack_conv_weight_split(w) if layout == ops.W_TAPS else None
+        return ops.conv1d(x, ops.pack_conv_weight(w) if ws is None else None, self.c_out, self.k, bias=self.bias.detach(),
+                          pad_left=pad, pad_mode=ops.PAD_ZERO, t_out=x.shape[-1], w_split=ws, **kw)
 
 
 class _Conv1dGLU(nn.Module):
@@ -309,7 +312,7 @@ class LogMelFrontend(nn.Module):
         F_ = self.n_fft // 2 + 1
         frames = ops.stft_frames(w, self.win, n_frames, self.hop, self.n_fft // 2, off)
         with ops.flop_key("dft"):
-            if self._basis_split is not None and ops.gemm_split_ok(2 * F_, self.win, 1, B * n_frames):
+            if self._basis_split is not None and ops.plan_gemm(2 * F_, self.win, B * n_frames).layout == ops.W_GEMM:
                 spec = ops.conv1d(frames, None, 2 * F_, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n_frames, w_split=self._basis_split)
             else:
                 spec = ops.conv1d(frames, basis, 2 * F_, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n_frames)

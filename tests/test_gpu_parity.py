@@ -801,7 +801,7 @@ def test_split_gemm_takes_p8_input_bit_identically(ops, cuda, kind, B, ci, co, T
 def test_short_clips_run_flattened_on_the_split_gemm(O, cuda, monkeypatch):
     """The 160-frame layers (encoder's last downsampling conv 512 -> 1024 k 12 s 6, decoder's first ConvTranspose1d 1536 -> 768 s 6)
     at B = 32: too short for per-clip column tiles, so they run as ONE flattened signal on the split GEMM kernel
-    (SConv1d._run_flat / SConvTranspose1d.run).  Same results as the oracle and as the per-clip launch (FAC_FLAT_SHORT=0 path)."""
+    (ops.conv1d_flat / ops.conv_transpose1d_flat).  Same results as the oracle and as the per-clip launch (FAC_FLAT_SHORT=0 path)."""
     from facodec_amd import layers, ops
     B, T = 32, 960
     conv = layers.SConv1d(64, 128, 12, stride=6, causal=True, norm="weight_norm")
@@ -837,9 +837,9 @@ def test_short_clips_run_flattened_on_the_split_gemm(O, cuda, monkeypatch):
 @pytest.mark.parametrize("c_in,c_out,d,T,a2", [(1024, 1536, 1, 160, False), (1024, 1024, 3, 100, True)])
 def test_short_clips_run_flattened_stride1_bit_identically(c_in, c_out, d, T, a2, O, cuda, monkeypatch):
     """The decoder's input conv (1024 -> 1536, k = 7) at the latent rate -- 160 frames fill 160 of the split kernel's 256 tile columns --
-    runs as ONE flattened signal of reflect-padded clips (SConv1d._run_flat_stride1): the same products in the same order as the
+    runs as ONE flattened signal of reflect-padded clips (ops.conv1d_flat): the same products in the same order as the
     per-clip launch, so the outputs are the same bits; both within the op tolerance of the oracle."""
-    from facodec_amd import layers
+    from facodec_amd import layers, ops
     B = 8
     conv = layers.SConv1d(c_in, c_out, 7, dilation=d, causal=True, norm="weight_norm")
     sd = synth.load_synthetic(conv, seed=41)
@@ -847,8 +847,8 @@ def test_short_clips_run_flattened_stride1_bit_identically(c_in, c_out, d, T, a2
     x = torch.randn(B, c_in, T, generator=_g(42)).to(cuda)
     alpha2 = (1 + 0.2 * torch.rand(c_out, generator=_g(43))).to(cuda) if a2 else None
     calls = []
-    orig = layers.SConv1d._run_flat_stride1
-    monkeypatch.setattr(layers.SConv1d, "_run_flat_stride1", lambda self, *a: (calls.append(1), orig(self, *a))[1])
+    orig = ops.conv1d_flat
+    monkeypatch.setattr(ops, "conv1d_flat", lambda *a, **kw: (calls.append(1), orig(*a, **kw))[1])
     with torch.no_grad():
         got = conv.run(x, alpha_y2=alpha2)
     assert len(calls) == 1
@@ -1587,7 +1587,7 @@ def test_in_place_reflect_fold_is_bit_identical_to_the_unpadding_copy(cuda):
 
 def test_short_clip_training_convs_run_flattened(cuda):
     """Round 6: at the 160-frame latent rate the training launches of the encoder's last strided conv and the decoder's first
-    ConvTranspose1d (forward AND data gradient) run as ONE flattened signal on the split GEMM kernel (ops.conv1d_flat_strided /
+    ConvTranspose1d (forward AND data gradient) run as ONE flattened signal on the split GEMM kernel (ops.conv1d_flat /
     conv_transpose1d_flat) instead of per clip on the fp32 128 x 160 tile.  Same mathematical products: outputs and gradients
     within 1e-5 of the per-clip path (FAC_FLAT_TRAIN=0), and the flattened launch is the one that runs."""
     from facodec_amd import autograd as A
