@@ -31,7 +31,7 @@ class ConvDesc(C.Structure):
         ("w_batched", C.c_int32), ("w_bs", _i64), ("ws", _p), ("ws_bytes", _i64), ("w_split", _p),
         ("K1", C.c_int32), ("dilation2", C.c_int32), ("row_phases", C.c_int32),
         ("x_p8", _p), ("x_p8_plane_bytes", _i64), ("y2_p8", _p), ("y2_p8_plane_bytes", _i64),
-        ("pw_split", C.c_int32),
+        ("pw_split", C.c_int32), ("split_rows", C.c_int32),
     ]
 
 
@@ -69,6 +69,8 @@ SIGNATURES = {
     "fac_gemm_w_split_bytes": (_i64, [_i, _i, _i, _i]),
     "fac_pack_gemm_w_split": (_i, [_p, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _p]),
     "fac_pack_conv_w_split": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "fac_conv_w_split_rows_bytes": (_i64, [_i, _i, _i, _i]),
+    "fac_pack_conv_w_split_rows": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_flip_transpose_w": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_prep_begin": (_i, []),
     "fac_prep_set_phase": (_i, [_i]),

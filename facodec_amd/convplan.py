@@ -6,7 +6,7 @@ holds the two against each other).  The switches (BF16_SPLIT, PW_SPLIT, PW_TAPS,
 attributes of `ops`, where tests and tools set them; they are read at call time."""
 from collections import namedtuple
 
-__all__ = ["ConvPlan", "ConvTrPlan", "plan_conv", "plan_convtr", "plan_gemm", "gemm_split_ok", "gemm_split_strided_ok", "split2_ok",
+__all__ = ["ConvPlan", "ConvTrPlan", "plan_conv", "plan_convtr", "plan_gemm", "tile_rows", "gemm_split_ok", "gemm_split_strided_ok", "split2_ok",
            "pw_taps_ok", "pw_split_tail_ok", "convtr_split_ok", "convtr_rows_ok", "flat_strided_ok", "flat_convtr_ok", "W_FP32", "W_TAPS",
            "W_GEMM", "W_GEMM_STRIDED", "W_SPLIT2", "W_FP32_PW_TAPS", "PER_CLIP", "FLAT_STRIDED", "FLAT_STRIDE1", "TR_POLYPHASE", "TR_ROWS",
            "TR_ROWS_SPLIT", "TR_ROWS_PW_TAPS", "TR_FLAT"]          # what `ops` re-exports
@@ -99,12 +99,25 @@ def flat_convtr_ok(c_in, c_out, s, batch, t_cols):
             and convtr_split_ok(c_in, c_out, s, 1, batch * t_cols))
 
 
+def tile_rows(c_out, c_in, k, grad=False):
+    """Output rows per tile of a W_TAPS launch, which is also the co-tile size its weights are packed for (ops.pack_conv_weight_split
+    `rows`, fac_conv_desc.split_rows): 96 -- the 96 x 256 form of the k = 7 split kernel (conv1d_bsplit96.hip) -- for the output
+    channel counts listed in ops.BS_ROWS96 (a module attribute: the A/B sets it to ()), else 64.  grad=True is what the training sites (autograd.py, the
+    data gradients of ops.py) ask with: they keep the 64-row form, the training step was not part of the A/B that wired the channel
+    counts.  The inference modules (layers.SConv1d) ask without it whether or not autograd is recording, so that a forward gives the
+    same bits either way.  The figure refines a ConvPlan whose
+    layout is W_TAPS; it is not a field of the tuple, whose three fields tests/golden/conv_plan_table.json records."""
+    sw = _sw()
+    return 96 if (sw.BF16_SPLIT and not grad and k == 7 and c_out in sw.BS_ROWS96 and c_in % 8 == 0) else 64
+
+
 # ------------------------------------------------------------------------------------------ planners
 def plan_conv(c_out, c_in, k, stride, dilation, batch, t_in, t_out, *, k1=0, alpha_in=False, plain=True, res=False,
               causal_reflect=False, grad=True, c_out_mult16=True, split_k=(1, 3, 5, 7), floor_k=(3, 5), tail="pw_split",
               pw_taps=True, split2=False, flat_infer=False, flat_stride1=False, flat_train=None):
     """Plan of one forward-conv launch: `batch` clips of t_in columns -> t_out columns each.  The data gradient of a stride-1 conv
     is this function with the channels swapped (ops.conv1d_bwd_data), the dx of a transposed conv a strided forward conv.
+    A W_TAPS plan is completed by tile_rows(c_out, c_in, k, grad): the co-tile size of the pack and of the launch.
     Facts of the launch: k1 (taps per level of a two-level conv, 0: plain), alpha_in (a Snake fused on the input), plain (epilogue
     without res / act / alpha_out), res, causal_reflect (causal layer with reflect padding), grad (autograd is recording).
     The sites' rules grew apart; every difference found is kept as a named argument (defaults: the training rule):

@@ -25,6 +25,7 @@ enum ConvKernel : int {
   CK_BSPLIT2 = 16,   // split-bf16 kernel for few output channels, 9 / 3 taps
   CK_PWS = 17,       // streaming k = 1 kernel on the bf16 pipe (pw_split)
   CK_PWT = 18,       // streaming kernel with taps on the bf16 pipe (pw_split, stride 2)
+  CK_BSPLIT96 = 19,  // split-bf16 kernel, K = 7, 96-row tile (split_rows = 96)
 };
 
 // Tile selection: M tile by output channels, narrow-N tile for short sequences (LSTM batches).
@@ -111,7 +112,8 @@ static int conv_plan(const fac_conv_desc* d, ConvArgs& a, ConvKernel& k) {
   if (d->x_p8 || d->y2_p8) {      // P8 operands exist only in the kernels listed at fac_conv_desc.x_p8: no silent fp32 detour
     const bool gs = d->w_split && (d->K <= 2 || (d->stride > 1 && d->K <= 2 * d->stride)) && conv_gsplit_ok(a) &&
                     !conv_skinny_ok(a, d->ws, d->ws_bytes) && d->C_in % 8 == 0 && d->x_p8_plane_bytes < (1ll << 32);
-    const bool ok = !d->y2_p8 && (gs || (d->w_split && !conv_two_level(a) && conv_bsplit_p8_ok(a) && !conv_cin1_ok(a)));
+    const bool ok = !d->y2_p8 && (gs || (d->w_split && !conv_two_level(a) && (d->split_rows == 96 ? conv_bsplit96_p8_ok(a) : conv_bsplit_p8_ok(a)) &&
+                                       !conv_cin1_ok(a)));
     FAC_REQUIRE(ok, "conv1d: P8 operands given but the launch does not run on a kernel that takes them (K=%d stride=%d C_in=%d columns=%lld)",
                 d->K, d->stride, d->C_in, (long long)d->B * d->T_out);
   }
@@ -147,6 +149,16 @@ static int conv_plan(const fac_conv_desc* d, ConvArgs& a, ConvKernel& k) {
     return FAC_OK;
   }
   const bool two_level = conv_two_level(a);
+  FAC_REQUIRE(d->split_rows == 0 || d->split_rows == 64 || d->split_rows == 96, "conv1d: split_rows must be 0, 64 or 96");
+  // weights packed for the 96-row tile fit no other kernel: the launch runs on it or fails
+  if (d->split_rows == 96) {
+    FAC_REQUIRE(d->w_split && !two_level && conv_bsplit96_ok(a) && !conv_cin1_ok(a),
+                "conv1d: split_rows = 96 needs a stride-1 k = 7 launch with C_out %% 96 == 0, C_in %% 8 == 0 and more than 640 columns "
+                "(K=%d stride=%d C_in=%d C_out=%d columns=%lld)", d->K, d->stride, d->C_in, d->C_out, (long long)d->B * d->T_out);
+    a.w = reinterpret_cast<const float*>(d->w_split);
+    k = CK_BSPLIT96;
+    return FAC_OK;
+  }
   // K = 3 / 5 / 7 split kernel first (its shapes exclude the few-column launches the split-reduction kernel takes)
   if (d->w_split && !two_level && conv_bsplit_ok(a) && !conv_cin1_ok(a)) {
     a.w = reinterpret_cast<const float*>(d->w_split);
@@ -195,6 +207,7 @@ extern "C" int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream) {
     case CK_BSPLIT2: return conv_dispatch_bsplit2(a, s);
     case CK_PWS: return conv_dispatch_pws(a, s);
     case CK_PWT: return conv_dispatch_pwt(a, s);
+    case CK_BSPLIT96: return conv_dispatch_bsplit96(a, s);
   }
   return FAC_ERR_ARG;   // not reached: conv_plan sets one of the above
 }
@@ -231,6 +244,7 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
     case CK_BSPLIT2: snprintf(name, name_len, "conv1d_bsplit2_kernel<%d,%d> 32x512 (bf16x3 split, fp32-grade)", a.KV, a.stride); break;
     case CK_PWS: snprintf(name, name_len, "conv1d_pws_kernel (k=1 streaming, W planes in LDS, bf16x3 split, fp32-grade)"); break;
     case CK_PWT: snprintf(name, name_len, "conv1d_pwt_kernel<%d taps> (streaming, W planes in LDS, bf16x3 split, fp32-grade)", a.K); break;
+    case CK_BSPLIT96: snprintf(name, name_len, "conv1d_bsplit_kernel<%d> 96x256 (bf16x3 split, fp32-grade)", a.K); break;
   }
   return k;
 }

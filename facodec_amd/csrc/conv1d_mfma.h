@@ -718,6 +718,10 @@ int conv_dispatch_gsplit(ConvArgs& a, hipStream_t s);
 bool conv_bsplit_ok(const ConvArgs& a);
 bool conv_bsplit_p8_ok(const ConvArgs& a);   // ... and the launch takes a P8 input (wide shape: C_in >= 64, C_in % 16 == 0)
 int conv_dispatch_bsplit(ConvArgs& a, hipStream_t s);
+// the 96-row form of the k = 7 split kernel (conv1d_bsplit96.hip; weights of fac_pack_conv_w_split_rows(rows = 96))
+bool conv_bsplit96_ok(const ConvArgs& a);
+bool conv_bsplit96_p8_ok(const ConvArgs& a);
+int conv_dispatch_bsplit96(ConvArgs& a, hipStream_t s);
 bool conv_pws_ok(const ConvArgs& a);
 int conv_dispatch_pws(ConvArgs& a, hipStream_t s);
 bool conv_pwt_ok(const ConvArgs& a);        // streaming kernel with taps: stride-2 ConvTranspose1d (all phases) / k = 4 stride-2 conv, few channels

@@ -72,9 +72,9 @@ class ConvWeights(nn.Module):
         """Split GEMM weights of a strided conv (stride < k <= 2 * stride), ops.pack_gemm_weight_split(in_stride=stride)."""
         return self._cached("_split", ops.pack_gemm_weight_split, in_stride=stride)
 
-    def packed_split(self):
-        """The same weights as three exact bf16 planes (ops.pack_conv_weight_split) for the k = 7 convs."""
-        return self._cached("_split", ops.pack_conv_weight_split)
+    def packed_split(self, rows=64):
+        """The same weights as three exact bf16 planes (ops.pack_conv_weight_split) for the k = 7 convs, in co tiles of `rows`."""
+        return self._cached("_split", ops.pack_conv_weight_split, rows=rows)
 
     def _apply(self, fn, *a, **kw):
         self._packed = None  # device / dtype moves invalidate the packed copies
@@ -126,7 +126,8 @@ class SConv1d(nn.Module):
         B, _, T = x.shape       # (x is an fp32 tensor: no caller hands a P8 to a module, so the old chains' isinstance guards are gone)
         plan = self.plan(B, T, alpha_in is not None, alpha_out is None and res is None and act == ops.ACT_NONE, res is not None)
         split = (w.packed_split_strided(s_) if plan.layout == ops.W_GEMM_STRIDED
-                 else w.packed_split() if plan.layout in (ops.W_TAPS, ops.W_GEMM) else None)
+                 else w.packed_split(ops.tile_rows(w.c_out, w.c_in, k)) if plan.layout == ops.W_TAPS
+                 else w.packed_split() if plan.layout == ops.W_GEMM else None)
         if plan.form != ops.PER_CLIP:
             # every clip reflect-padded on the left (the causal padding of dac/model/encodec.py:212-222, materialised: data movement
             # only; strided: T % s == 0, so there is no right padding) and all of them laid out as ONE signal

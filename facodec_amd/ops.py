@@ -238,6 +238,9 @@ class flop_scale:
 # k = 7 convs on the bf16 matrix pipe with fp32-grade operand splitting (conv1d_bsplit.hip).  Results have
 # fp32-MFMA-grade error; BF16_SPLIT = False keeps every conv on the fp32 MFMA kernel.
 BF16_SPLIT = True
+# Output channel counts whose k = 7 inference convs run the 96 x 256 form of the split kernel (conv1d_bsplit96.hip), read by
+# convplan.tile_rows at call time.  Wired per channel count on a same-box A/B; () puts every layer on the 64 x 256 form.
+BS_ROWS96 = (96,)
 
 
 def set_conv_profile(p):
@@ -459,9 +462,10 @@ def pack_convtr_weight_rows_split(v, g, stride, out=None):
 
 
 @prepared
-def pack_conv_weight_split(v, g=None, out=None, scale=None):
-    """(C_out, C_in, K) [weight-normed with g] -> split-bf16 layout of fac_pack_conv_w_split (K = 5 / 7; uint8 buffer) or of
-    fac_pack_gemm_w_split (K = 1 / 2)."""
+def pack_conv_weight_split(v, g=None, out=None, scale=None, rows=None):
+    """(C_out, C_in, K) [weight-normed with g] -> split-bf16 layout of fac_pack_conv_w_split_rows (K = 3 / 5 / 7; uint8 buffer) or of
+    fac_pack_gemm_w_split (K = 1 / 2).  rows: co-tile size, 64 or (K = 7) 96; None: what convplan.tile_rows names for an inference
+    launch.  The buffer carries the figure as `.split_rows`, which conv1d hands to the launch with it."""
     v = _dev(v, "weight")
     c_out, c_in, k = v.shape
     if k <= 2:
@@ -469,11 +473,16 @@ def pack_conv_weight_split(v, g=None, out=None, scale=None):
     lib = _lib.load()
     if scale is None and g is not None:
         scale = wn_scale(v, g)
-    nbytes = lib.fac_conv_w_split_bytes(c_out, c_in, k)
-    if out is None:
+    if rows is None:
+        rows = tile_rows(c_out, c_in, k)
+    nbytes = lib.fac_conv_w_split_rows_bytes(c_out, c_in, k, rows)
+    if nbytes < 0:
+        raise _lib.FacodecHipError("pack_conv_weight_split: no %d-row tile for k = %d" % (rows, k))
+    if out is None or out.numel() != nbytes:         # (a buffer packed for the other tile: the switch was flipped in between)
         out = torch.empty(nbytes, device=v.device, dtype=torch.uint8)
-    _lib.check(lib.fac_pack_conv_w_split(_ptr(v), _ptr(scale), out.data_ptr(), c_out, c_in, k, _stream()),
-               "fac_pack_conv_w_split")
+    _lib.check(lib.fac_pack_conv_w_split_rows(_ptr(v), _ptr(scale), out.data_ptr(), c_out, c_in, k, rows, _stream()),
+               "fac_pack_conv_w_split_rows")
+    out.split_rows = rows
     return out
 
 
@@ -589,6 +598,7 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
     d.w_k1 = w_k1.data_ptr() if w_k1 is not None else None
     d.bias_k1 = bias_k1.data_ptr() if bias_k1 is not None else None
     d.w_split = w_split.data_ptr() if w_split is not None else None
+    d.split_rows = getattr(w_split, "split_rows", 0)         # co-tile size the buffer was packed for (pack_conv_weight_split)
     d.x_bs, d.x_cs = (x.stride(0), x.stride(1)) if x_p8 is None else (c_in * t_in, t_in)
     d.y_bs, d.y_cs = c_y * t_out, t_out
     if out is not None and (out.stride(0), out.stride(1)) != (d.y_bs, d.y_cs) and out.shape[0] * out.shape[1] > 1:
@@ -685,7 +695,7 @@ def pack_conv_for(layout, v, g, stride=1, k1=0, scale=None):
         return None, pack_gemm_weight_split(v, g, in_stride=stride, scale=scale)
     if layout == W_SPLIT2:
         return None, pack_conv_weight_split2(v, g, k1, scale=scale)
-    return None, pack_conv_weight_split(v, g, scale=scale)          # W_TAPS / W_GEMM: fp32-grade split on the bf16 pipe
+    return None, pack_conv_weight_split(v, g, scale=scale, rows=64)          # W_TAPS / W_GEMM (training sites: tile_rows(grad=True))
 
 
 def pack_convtr_for(layout, v, g, stride):
@@ -1237,7 +1247,7 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
             # the flipped / transposed conv on the bf16 pipe too: materialise w = g v/||v||, swap channels, flip taps
             wt = flipped_weight(v, g, scale)                                   # (C_in, C_out, K) = weights of the bwd conv
             dxpad = conv1d(dy, None, c_in, k, dilation=dilation, pad_left=(k - 1) * dilation, pad_mode=PAD_ZERO, t_out=tp,
-                           w_split=pack_conv_weight_split(wt))
+                           w_split=pack_conv_weight_split(wt, rows=64))
         elif layout == W_GEMM:
             w = rows_fma(v, scale) if g is not None else v                    # 1x1: the transposed GEMM on the bf16 pipe
             dxpad = conv1d(dy, None, c_in, 1, pad_left=0, pad_mode=PAD_ZERO, t_out=tp, w_split=pack_gemm_weight_split_t(w))

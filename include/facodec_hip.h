@@ -180,6 +180,10 @@ typedef struct fac_conv_desc {
    * = 2), and with `w` of fac_pack_conv_w the k = 4 stride-2 conv, each with C_in * taps <= 384 (conv1d_pw_split.hip).  Needs only
    * `w`; ignored elsewhere.  The host side sets it wherever it hands `w_split` to the other layers. */
   int32_t pw_split;
+  /* Optional (0 = 64): output rows per tile the split weights `w_split` of a K = 7 stride-1 launch were packed for
+   * (fac_pack_conv_w_split_rows).  96 selects the 96-row form of the split kernel (conv1d_bsplit96.hip: C_out % 96 == 0, C_in % 8 ==
+   * 0); such weights fit no other kernel, so a launch outside its shapes is an error. */
+  int32_t split_rows;
 } fac_conv_desc;
 
 int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream);
@@ -190,6 +194,10 @@ int fac_to_p8(const float* x, const float* alpha, void* out, int B, int C, int T
  * hi + mid + lo == w exactly, laid out per (64-channel tile, 16-input-channel stage) for LDS-DMA.
  * `out` must hold fac_conv_w_split_bytes(C_out, C_in, K) bytes. */
 int64_t fac_conv_w_split_bytes(int C_out, int C_in, int K);
+/* The same for tiles of `rows` output channels: 64 (what the two functions above/below use) or, K = 7 only, 96 -- co tiles of 96
+ * channels, stages of 8 input channels x 4 tap pairs (fac_conv_desc.split_rows = 96).  _bytes returns -1 for any other (K, rows). */
+int64_t fac_conv_w_split_rows_bytes(int C_out, int C_in, int K, int rows);
+int fac_pack_conv_w_split_rows(const float* v, const float* scale, void* out, int C_out, int C_in, int K, int rows, fac_stream_t stream);
 int fac_pack_conv_w_split(const float* v, const float* scale, void* out, int C_out, int C_in, int K,
                           fac_stream_t stream);
 /* Split weights of the few-output-channel 9- / 3-tap convs (conv1d_bsplit2.hip: C_out <= 32, K1 = 9 stride 1 / 2 or K1 = 3 stride
