@@ -184,6 +184,10 @@ SIGNATURES = {
     "fac_masked_mean": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_layernorm_c_affine": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_stft_frames": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fac_stft_frames_ragged": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fac_mask_tail": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "fac_mask_tail_i64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "fac_frame_mask": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_spec_power": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_reduce_pair": (_i, [_p, _p, _p, _p, _i64, _i, _f, _f, _i, _p]),
     "fac_aa_snakebeta_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

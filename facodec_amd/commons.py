@@ -113,6 +113,164 @@ def decode_codes(model, codes, timbre):
     return model.decoder(model.quantizer.decode_input(codes, timbre))
 
 
+# ------------------------------------------------------------------------------------ clips of different lengths
+# Sample budget of one padded batch (clips x longest clip): the benchmark's 32 clips x 2 s, the batch every kernel is tuned on.
+MAX_BATCH_SAMPLES = 32 * 48000
+
+
+def plan_groups(lengths, max_batch_samples=MAX_BATCH_SAMPLES):
+    """Groups clips into padded batches: -> list of index lists.  The clips are sorted by length (ascending, ties in the caller's
+    order) and cut into runs of neighbours; a run grows while count x longest clip (what the padded batch holds) stays within
+    the budget, so a long clip is batched with clips of its own size and never pads the short ones up to itself.  A single
+    clip longer than the budget is a group of its own."""
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    groups, cur = [], []
+    for i in order:
+        if cur and (len(cur) + 1) * lengths[i] > max_batch_samples:
+            groups.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def padding_share(lengths, groups):
+    """Fraction of the padded batches' samples that is padding."""
+    padded = sum(len(g) * max(lengths[i] for i in g) for g in groups)
+    return 1.0 - sum(lengths) / padded if padded else 0.0
+
+
+def _reflect_convs(model):
+    """-> [(name, reflect pad in columns, samples per column or None, columns per frame or None)] of every reflect-padded conv of
+    encoder, quantizer and decoder, walking each module tree in execution order; raises NotImplementedError for a non-causal
+    conv (a right-padded batch gives every clip its own result only if nothing looks to the right)."""
+    from .layers import SConv1d, SConvTranspose1d
+    from . import ops
+    found = []
+    for key in ("encoder", "quantizer", "decoder"):
+        rate = 1                                   # encoder: samples per column; decoder: columns per frame; quantizer: frame rate
+        for name, m in model[key].named_modules():
+            if isinstance(m, (SConv1d, SConvTranspose1d)) and not m.causal:
+                raise NotImplementedError(f"{key}.{name} is not causal: batches of clips with different lengths need the causal "
+                                          "configuration (right padding must not reach back into a clip)")
+            if isinstance(m, SConvTranspose1d):
+                rate *= m.stride
+            elif isinstance(m, SConv1d):
+                pad = (m.kernel_size - 1) * m.dilation + 1 - m.stride
+                if m.pad_mode == ops.PAD_REFLECT and pad > 0:
+                    found.append((f"{key}.{name}", pad, rate if key == "encoder" else None,
+                                  rate if key == "decoder" else 1 if key == "quantizer" else None))
+                if key == "encoder":
+                    rate *= m.stride
+    return found
+
+
+def min_clip_samples(model):
+    """Shortest clip the clip-list calls take: every reflect padding of the path needs a signal longer than the pad (as
+    StreamingDecoder._min_prime derives it for the decoder's first chunk) -- the log-mel front-end's n_fft / 2 samples, a causal
+    conv of the encoder `pad` columns of its own rate, a conv of the quantizer or decoder pad // (columns per frame) + 1 whole
+    frames.  Below it the single-clip calls fail or fall back to a zero extension that depends on the clip's length, which a
+    padded batch cannot reproduce.  (The shipped configuration: 3000 samples = 10 frames, the decoder's k = 7 convs of dilation 9
+    at 6 columns per frame.)"""
+    hop = model.quantizer.hop_length
+    need = model.quantizer.to_mel.n_fft // 2 + 1
+    for _, pad, per_col, per_frame in _reflect_convs(model):
+        need = max(need, pad * per_col + 1 if per_col is not None else hop * (pad // per_frame + 1))
+    return need
+
+
+def _need_gpu(tensors, what):
+    from ._lib import FacodecHipError
+    for t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be tensors (got {type(t)})")
+        if not t.is_cuda:
+            raise FacodecHipError(f"{what} must live on the GPU (got {t.device}); there is no CPU path")
+
+
+def _clip_lengths(model, tensors, what, per_item=1):
+    _need_gpu(tensors, what)
+    lengths = [int(t.shape[-1]) * per_item for t in tensors]
+    need = min_clip_samples(model)
+    hop = model.quantizer.hop_length
+    for i, n in enumerate(lengths):
+        if n < need:
+            raise ValueError(f"clip {i} has {n} samples; the shortest clip this path takes has {need} samples "
+                             f"({-(-need // hop)} frames: the longest reflect padding of encoder, log-mel front-end and decoder)")
+    return lengths
+
+
+@torch.no_grad()
+def encode_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
+    """Clips of different lengths -> codes and timbre per clip, in the caller's order:
+
+        clips = encode_clips(model, [wave_0 (T_0,), wave_1 (1, T_1), ...])         # GPU tensors, float32, 24 kHz
+        clips[i] == dict(codes=[p (1, T_i // 300), c (n_c, T_i // 300), r (3, T_i // 300)] int64, timbre=(1024,))
+
+    every entry what the single-clip calls `model.encoder(w)`, `model.quantizer(z, w, n_c, return_codes=True)` give on that clip
+    alone.  The clips are sorted by length and grouped into zero-padded batches under a sample budget (plan_groups); each group
+    is one encoder pass and one FAquantizer.forward_ragged.  The reference's `collate` output (zero-padded `waves` (B, T) and
+    `wave_lens`) maps onto it as `[waves[b, :wave_lens[b]] for b in range(B)]`."""
+    waves = list(waves)
+    if not waves:
+        return []
+    for w in waves:
+        if isinstance(w, torch.Tensor) and not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = _clip_lengths(model, waves, "clips")
+    from . import ops
+    dev, hop = waves[0].device, model.quantizer.hop_length
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True).unsqueeze(1)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), dev)
+        z = model.encoder(batch)
+        _, codes, timbre, _ = model.quantizer.forward_ragged(z, batch, lens, n_c=n_c)
+        for j, i in enumerate(group):
+            out[i] = dict(codes=[c[j, :, :lengths[i] // hop] for c in codes], timbre=timbre[j])
+    return out
+
+
+@torch.no_grad()
+def decode_clips(model, codes_list, timbres, max_batch_samples=MAX_BATCH_SAMPLES):
+    """Codes of clips of different lengths -> list of waves (1, 300 F_i), in the caller's order.  codes_list[i] =
+    [p (n_p, F_i), c (n_c, F_i), r (n_r, F_i)] int64 as encode_clips returns them (the same row counts for every clip);
+    timbres[i] (1024,): the clip's own or another clip's / speaker's (timbre swap, as in decode_codes).  Per group of
+    plan_groups the codes are padded with code 0 and decoded by one fac_vq_decode launch and one decoder pass (causal: the
+    padding cannot reach back into a clip); every wave is cropped to its clip."""
+    codes_list = [list(c) for c in codes_list]
+    if not codes_list:
+        return []
+    timbres = list(timbres)
+    if len(timbres) != len(codes_list):
+        raise ValueError(f"{len(codes_list)} clips but {len(timbres)} timbres")
+    for c in codes_list:
+        if len(c) != 3 or any(not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != c[0].shape[1] for x in c):
+            raise ValueError("every clip's codes must be [codes_p (n_p, F), codes_c (n_c, F), codes_r (n_r, F)]")
+        if [x.shape[0] for x in c] != [x.shape[0] for x in codes_list[0]]:
+            raise ValueError("the clips disagree on the quantizer counts (n_p, n_c, n_r)")
+    hop = model.quantizer.hop_length
+    lengths = _clip_lengths(model, [c[0] for c in codes_list], "codes", per_item=hop)
+    _need_gpu(timbres, "timbres")
+    out = [None] * len(codes_list)
+    for group in plan_groups(lengths, max_batch_samples):
+        codes = [torch.nn.utils.rnn.pad_sequence([codes_list[i][s].t() for i in group], batch_first=True).transpose(1, 2).contiguous()
+                 for s in range(3)]
+        timbre = torch.stack([timbres[i].reshape(-1) for i in group])
+        wave = decode_codes(model, codes, timbre)
+        for j, i in enumerate(group):
+            out[i] = wave[j, :, :lengths[i]]
+    return out
+
+
+@torch.no_grad()
+def reconstruct_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
+    """encode_clips then decode_clips with every clip's own timbre: list of waves (1, 300 (T_i // 300))."""
+    clips = encode_clips(model, waves, n_c=n_c, max_batch_samples=max_batch_samples)
+    return decode_clips(model, [c["codes"] for c in clips], [c["timbre"] for c in clips], max_batch_samples=max_batch_samples)
+
+
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):
     """modules/commons.py:446-471: {'net': {key: state_dict}, ...}; strips DDP's 'module.' prefix."""
     state = torch.load(path, map_location="cpu")

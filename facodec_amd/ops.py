@@ -1156,6 +1156,50 @@ def stft_frames(wave, n_win, n_frames, hop, pad, n_off):
     return frames
 
 
+# --------------------------------------------------------------------------------- batches of clips with different lengths
+def _lens(lens, B):
+    """lens (B,) int32 on the device (every row's length in samples); never copied to the host."""
+    if not isinstance(lens, torch.Tensor) or not lens.is_cuda:
+        raise _lib.FacodecHipError(f"lens must live on the GPU (got {getattr(lens, 'device', type(lens))}); there is no CPU path")
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,):
+        raise _lib.FacodecHipError(f"lens must be int32 ({B},), got {lens.dtype} {tuple(lens.shape)}")
+    return lens if lens.is_contiguous() else lens.contiguous()
+
+
+def stft_frames_ragged(wave, lens, n_win, n_frames, hop, pad, n_off):
+    """stft_frames on a right-padded batch: row b is framed as wave[b, :lens[b]] (its own end reflection, lens[b] // hop
+    frames, bit-equal to stft_frames of that slice), the frame columns behind are zeros."""
+    wave = _dev(wave, "wave")
+    B, T = wave.shape
+    frames = torch.empty(B, n_win, n_frames, device=wave.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_stft_frames_ragged(_ptr(wave), _ptr(_lens(lens, B)), _ptr(frames), B, T, n_win, n_frames, hop, pad,
+                                                  n_off, _stream()), "fac_stft_frames_ragged")
+    return frames
+
+
+def mask_tail_(x, lens, unit):
+    """x (B, C, T) fp32 or int64, contiguous: x[b, :, t] = 0 for t >= lens[b] // unit, in place."""
+    if not x.is_cuda:
+        raise _lib.FacodecHipError(f"tensor must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dim() != 3 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.int64):
+        raise _lib.FacodecHipError(f"mask_tail_: a contiguous (B, C, T) float32 / int64 tensor, got {x.dtype} {tuple(x.shape)}")
+    B, c, T = x.shape
+    lib = _lib.load()
+    fn, name = (lib.fac_mask_tail, "fac_mask_tail") if x.dtype == torch.float32 else (lib.fac_mask_tail_i64, "fac_mask_tail_i64")
+    _lib.check(fn(_ptr(x), _ptr(_lens(lens, B)), B, c, T, unit, _stream()), name)
+    return x
+
+
+def frame_mask(lens, n_frames, unit):
+    """-> (mask (B, n_frames) float 0 / 1 with mask[b, f] = f < lens[b] // unit, frame_lens (B,) int32 = min(lens // unit, n_frames))."""
+    B = lens.shape[0]
+    lens = _lens(lens, B)
+    mask = torch.empty(B, n_frames, device=lens.device, dtype=torch.float32)
+    n_valid = torch.empty(B, device=lens.device, dtype=torch.int32)
+    _lib.check(_lib.load().fac_frame_mask(_ptr(lens), _ptr(mask), _ptr(n_valid), B, n_frames, unit, _stream()), "fac_frame_mask")
+    return mask, n_valid
+
+
 def spec_power(spec, power):
     B, f2, nf = spec.shape
     out = torch.empty(B, f2 // 2, nf, device=spec.device, dtype=torch.float32)

@@ -263,6 +263,25 @@ class StyleEncoder(nn.Module):
         x = self.fc.run(x)
         return ops.masked_mean(x, mask)
 
+    def forward_ragged(self, x, lens, mask, unit):
+        """Per-clip-exact mode for a right-padded batch: x (B, in_dim, T), lens (B,) int32 sample counts on the device, row b
+        has lens[b] // unit frames, mask (B, T) = ops.frame_mask(lens, T, unit) -> (B, out_dim), every row what `forward(x[b:b+1,
+        :, :n_b])` gives.  Unlike the `mask=` path above (the reference's: only the first k = 5 GLU conv sees a zeroed tail, the
+        second one reads what the first wrote past the clip's end), the tail is zeroed in front of EACH conv, which is the zero
+        padding that conv has on the clip alone; keys past the end are masked out of the attention and the mean runs over the
+        clip's own frames."""
+        x = self.spectral["0"].run(x, act=ops.ACT_MISH)
+        x = self.spectral["3"].run(x, act=ops.ACT_MISH)
+        for glu in self.temporal:
+            ops.mask_tail_(x, lens, unit)
+            a = glu.conv1.run(x, pad=2)
+            x = ops.glu_residual(a, x)
+        ops.mask_tail_(x, lens, unit)
+        x = self.slf_attn(x, mask, res=x)
+        x = self.fc.run(x)
+        ops.mask_tail_(x, lens, unit)                # fac_masked_mean sums every column and divides by the mask's sum
+        return ops.masked_mean(x, mask)
+
 
 # ------------------------------------------------------------------------------------ front-end
 class LogMelFrontend(nn.Module):
@@ -306,11 +325,22 @@ class LogMelFrontend(nn.Module):
         """wave (B, 1, T) or (B, T) -> normalised log-mel (B, n_mels, T // hop) (the quantizer's crop,
         modules/quantize.py:242) or, with all_frames, all 1 + T // hop centred frames (meldataset.py:45)."""
         w = wave.reshape(wave.shape[0], wave.shape[-1])
-        B, T = w.shape
-        n_frames = T // self.hop + (1 if all_frames else 0)
-        basis, fbp, off = self._consts(w.device)
+        n_frames = w.shape[1] // self.hop + (1 if all_frames else 0)
+        off = self._consts(w.device)[2]
+        return self._from_frames(ops.stft_frames(w, self.win, n_frames, self.hop, self.n_fft // 2, off))
+
+    def forward_ragged(self, wave, lens):
+        """Right-padded batch: wave (B, 1, T) or (B, T), lens (B,) int32 sample counts on the device -> (B, n_mels, T // hop); row
+        b's first lens[b] // hop frames are `forward(wave[b:b+1, ..., :lens[b]])` (the frames reflect at the clip's own end), the
+        columns behind them are the log-mel of silence."""
+        w = wave.reshape(wave.shape[0], wave.shape[-1])
+        off = self._consts(w.device)[2]
+        return self._from_frames(ops.stft_frames_ragged(w, lens, self.win, w.shape[1] // self.hop, self.hop, self.n_fft // 2, off))
+
+    def _from_frames(self, frames):
+        B, _, n_frames = frames.shape
+        basis, fbp, _ = self._consts(frames.device)
         F_ = self.n_fft // 2 + 1
-        frames = ops.stft_frames(w, self.win, n_frames, self.hop, self.n_fft // 2, off)
         with ops.flop_key("dft"):
             if self._basis_split is not None and ops.plan_gemm(2 * F_, self.win, B * n_frames).layout == ops.W_GEMM:
                 spec = ops.conv1d(frames, None, 2 * F_, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n_frames, w_split=self._basis_split)
@@ -519,6 +549,41 @@ class FAquantizer(nn.Module):
         return outs, quantized, commitment, codebook, timbre
 
     forward_v2 = forward
+
+    @cached_forward
+    def forward_ragged(self, x, waves, lens, n_c=2):
+        """Eval forward of a right-padded batch of clips with different lengths: x (B, D, F) the encoder's latent of waves
+        (B, 1, T), lens (B,) int32 sample counts on the device (never read back) -> (outs (B, D, n), [codes_p, codes_c, codes_r],
+        timbre (B, D), frame_lens (B,) int32 = lens // hop), n = T // hop.  Row b's first frame_lens[b] frames and its timbre are
+        what `forward(x[b:b+1, :, :n_b], waves[b:b+1, :, :lens[b]], n_c, return_codes=True)` gives: the log-mel frames reflect at
+        the clip's own end, the timbre encoder runs in its per-clip-exact mode (StyleEncoder.forward_ragged), everything else is
+        causal or per-frame (the caller checks the configuration: commons.encode_clips).  outs and codes behind a clip's last
+        frame are zeros.  The lengths are validated where they originate, on the host (commons.min_clip_samples)."""
+        if self.training:
+            raise RuntimeError("FAquantizer.forward_ragged is an eval-mode forward (call .eval() first); training batches are equal-length crops")
+        hop = self.hop_length
+        mel = self.to_mel.forward_ragged(waves, lens)         # (B, 80, n) computed once
+        n = min(mel.shape[-1], x.shape[2])
+        if x.shape[2] != n:
+            x = x[:, :, :n].contiguous()
+        mask, frame_lens = ops.frame_mask(lens, mel.shape[-1], hop)
+
+        def prosody_chain():                                  # as in `forward`
+            f0 = ops.conv1d(mel[:, :20], self.melspec_linear.w.packed(), 256, 1, bias=self.melspec_linear.w.bias,
+                            pad_left=0, pad_mode=ops.PAD_ZERO, t_out=mel.shape[-1])
+            f0 = self.melspec_linear2.run(self.melspec_encoder(f0))
+            if f0.shape[2] != n:
+                f0 = f0[:, :, :n].contiguous()
+            return self.prosody_quantizer(f0, 1)
+
+        timbre, (z_p, codes_p, _, _, _), (z_c, codes_c, _, _, _) = ops.run_chains(
+            [lambda: self.timbre_encoder.forward_ragged(mel, lens, mask, hop), prosody_chain, lambda: self.content_quantizer(x, n_c)],
+            x.device, QUANT_STREAMS, inputs=[mel, x, lens, mask])
+        z_r, codes_r, _, _, _ = self.residual_quantizer(ops.sub2(x, z_p, z_c), 3)
+        outs = ops.layernorm_c_affine(ops.add(ops.add(z_p, z_c), z_r), self.timbre_linear(timbre))
+        ops.mask_tail_(outs, lens, hop)
+        codes = [ops.mask_tail_(c, lens, hop) for c in (codes_p, codes_c, codes_r)]
+        return outs, codes, timbre, frame_lens
 
     def decode_weights(self):
         """Per RVQ (prosody, content, residual) the decode_weights() of every quantizer."""

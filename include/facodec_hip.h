@@ -654,6 +654,24 @@ int fac_layernorm_c_affine(const float* x, const float* style, float* out, int B
  * tap inside the n_fft frame). wave (B, T). */
 int fac_stft_frames(const float* wave, float* frames, int B, int T, int n_win, int n_frames,
                     int hop, int pad, int n_off, fac_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Batches of clips with different lengths: the clips are right-padded with zeros to T samples, lens (B,) int32 on the
+ * device holds every row's own length in samples.  No call reads lens on the host; a length is clamped to [0, T] before it
+ * indexes anything, so validating it (e.g. pad < length) is the caller's business, where the lengths originate.
+ * ---------------------------------------------------------------------------------------- */
+
+/* fac_stft_frames with per-row lengths: row b reflects at lens[b] and has lens[b] / hop frames, bit-equal to
+ * fac_stft_frames on wave[b, :lens[b]]; frame columns f >= lens[b] / hop are written as zeros.  frames (B, n_win, n_frames). */
+int fac_stft_frames_ragged(const float* wave, const int32_t* lens, float* frames, int B, int T, int n_win, int n_frames,
+                           int hop, int pad, int n_off, fac_stream_t stream);
+/* x[b, :, t] = 0 for t >= lens[b] / unit, in place (unit = hop for frame-rate tensors, 1 for samples); x (B, C, T) fp32, or
+ * int64 (code tensors) for the _i64 form.  Store-only: 16-byte stores over the tails, nothing else is touched. */
+int fac_mask_tail(float* x, const int32_t* lens, int B, int C, int T, int unit, fac_stream_t stream);
+int fac_mask_tail_i64(int64_t* x, const int32_t* lens, int B, int C, int T, int unit, fac_stream_t stream);
+/* mask[b, f] = f < lens[b] / unit ? 1 : 0  (B, F) fp32, the mask of fac_attention / fac_masked_mean;
+ * n_valid (B,) int32 = min(lens[b] / unit, F), or NULL. */
+int fac_frame_mask(const int32_t* lens, float* mask, int32_t* n_valid, int B, int F, int unit, fac_stream_t stream);
 /* spec (B, 2F, n_frames) rows [0,F) = Re, [F,2F) = Im  ->  out (B, F, n_frames):
  * power == 2: re^2+im^2 ; power == 1: sqrt(re^2+im^2). */
 int fac_spec_power(const float* spec, float* out, int B, int F, int n_frames, int power,
