@@ -92,6 +92,97 @@ __device__ __forceinline__ int reflect_index(int t, int T, int Text) {
   return (j >= 0 && j < T) ? j : -1;
 }
 
+// ---- primitives shared by the split-bf16 kernels (conv1d_bsplit* / gemm_split / pw_split / wgrad_split, lstm_persist, the P8 pre-pass)
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// x = h + m + l up to the rounding of the last residual: three round-to-nearest-even bf16 planes, each the bf16 of what the planes
+// before it left over (both subtractions are exact).  "bf16 pipe, fp32-grade" and the bit-exact gates rest on this one function:
+// the weight packers, the staging waves, the weight-gradient plane kernels, the LSTM resident kernel and the P8 pre-pass all
+// call it, so an operand split ahead of time and one split inside a kernel are the same bits.
+__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
+  h = (__bf16)x;
+  const float r1 = x - (float)h;
+  m = (__bf16)r1;
+  l = (__bf16)(r1 - (float)m);
+}
+
+// Raw workgroup barrier between compiler fences: no s_waitcnt of its own (the caller has waited for exactly what it needs).
+__device__ __forceinline__ void wg_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// Position in the logical tile order of virtual workgroup v of n.  Workgroups are dispatched round-robin over the 8 XCDs
+// (observed: block i -> XCD i % 8, speed only, never correctness): the remap makes each XCD walk a CONTIGUOUS range of the
+// logical order (the first n % 8 XCDs take one tile more).  With a tile list ordered (co-tile slowest, then batch/phase, then time
+// tile) the workgroups resident on one XCD then share one C_out tile, i.e. stream the same weight slabs through that XCD's
+// private L2.  The kernels keep only their own unpacking of the id.  V is int or unsigned, whichever the caller's id is (the
+// shift then is the one that kernel was measured with).
+template <class V>
+__host__ __device__ constexpr int xcd_contiguous_id(V v, int n) {
+  const int q8 = n >> 3, r8 = n & 7;
+  const int xcd = v & 7, within = v >> 3;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+}
+constexpr bool xcd_contiguous_is_permutation(int n) {
+  bool seen[64] = {};
+  for (int v = 0; v < n; ++v) {
+    const int id = xcd_contiguous_id(v, n);
+    if (id < 0 || id >= n || seen[id]) return false;
+    seen[id] = true;
+  }
+  return true;
+}
+static_assert(xcd_contiguous_is_permutation(1) && xcd_contiguous_is_permutation(7) && xcd_contiguous_is_permutation(8) &&
+                  xcd_contiguous_is_permutation(9) && xcd_contiguous_is_permutation(13) && xcd_contiguous_is_permutation(64),
+              "xcd_contiguous_id must map [0, n) onto [0, n)");
+
+// The same idea for launches padded to a multiple of 8 workgroups: XCD k takes [k * per_xcd, (k + 1) * per_xcd) of the logical
+// order.  Host half: per_xcd and the padded 1-D grid for `total` workgroups.  The device half stays written out in its two
+// kernels (vq_fwd_kernel, conv1d_wgrad_kmajor_kernel): logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3), and the overhang
+// workgroups (blockIdx.x >> 3 >= per_xcd, or logical >= total) return at once -- behind a helper, with an id-or-minus-one or a
+// bool result alike, the compiler emitted a different test and schedule for both kernels.
+struct XcdGrid {
+  int per_xcd;
+  unsigned grid;
+};
+inline XcdGrid xcd_padded_grid(long long total) {
+  const int per_xcd = (int)((total + 7) / 8);
+  return {per_xcd, (unsigned)(8 * per_xcd)};
+}
+
+// ---- host-side launch helpers
+
+constexpr size_t FAC_LDS_MAX = 160 * 1024;   // LDS of one gfx950 CU: the most dynamic shared memory a kernel can be opted in to
+
+// Opts kernel Kern in to `bytes` of dynamic LDS, once per process.  The flag belongs to the kernel VALUE, not to its type: kernels
+// of one signature (every ConvArgs kernel) each get their own.
+template <auto Kern>
+inline void allow_dynamic_lds(size_t bytes = FAC_LDS_MAX) {
+  static bool done = false;
+  if (!done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done = true;
+  }
+}
+
+// Compute units of the current device (cached per device), 0 when unknown: each caller decides what "unknown" means to it.
+constexpr int FAC_MAX_DEV = 16;
+inline int device_cus() {
+  static int cus[FAC_MAX_DEV] = {0};
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FAC_MAX_DEV) return 0;
+  if (cus[dev] == 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) cus[dev] = v;
+  return cus[dev];
+}
+
 }  // namespace fac
 
 // Issue priorities (s_setprio) of the two wave roles of the split-bf16 kernels (conv1d_bsplit / bsplit2 / gemm_split / wgrad k-major):

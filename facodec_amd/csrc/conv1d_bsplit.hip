@@ -108,7 +108,7 @@ int conv_dispatch_bsplit(ConvArgs& a, hipStream_t s) {
 extern "C" int fac_debug_bsplit_occupancy(int lds_bytes) {
   int n = -1;
   auto kern = fac::conv1d_bsplit_kernel<7, 2, 4, fac::BS_NSW_WIDE>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fac::FAC_LDS_MAX);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, (4 + fac::BS_NSW) * 64, (size_t)lds_bytes) != hipSuccess) return -1;
   return n;
 }

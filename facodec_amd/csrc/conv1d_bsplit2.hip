@@ -23,18 +23,9 @@
 
 namespace fac {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int B2_CO = 32;                // output channels per tile
 constexpr int B2_NB = 4;                 // 32-column blocks per MFMA wave
 constexpr int B2_TT = 32 * B2_NB * 4;    // 512 columns per tile
-
-__device__ __forceinline__ void b2_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
 
 __host__ __device__ constexpr int b2_slots(int K1) { return (K1 + 1) & ~1; }
 
@@ -62,7 +53,7 @@ __device__ __forceinline__ void pack_conv_split2_body(const float* __restrict__ 
         if (scale != nullptr) w = __fmul_rn(w, sc);
       }
       __bf16 a, b2, c;
-      b2_split3(w, a, b2, c);
+      split3(w, a, b2, c);
       h[i] = a; m[i] = b2; l[i] = c;
     }
     const long long base = ((long long)ct * n_ch + ch) * 3;
@@ -108,10 +99,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_bsplit2_kernel(ConvArgs a) {
 
   int t0, co0, b;
   {
-    const int n = gridDim.x;
-    const int q8 = n >> 3, r8 = n & 7;
-    const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int id = xcd_contiguous_id<unsigned>(blockIdx.x, gridDim.x);
     const int nt = a.n_t_tiles;
     const int tt = id % nt;
     const int rest = id / nt;
@@ -208,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_bsplit2_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           __bf16 p0, p1, p2;
-          b2_split3(xr[j][i], p0, p1, p2);
+          split3(xr[j][i], p0, p1, p2);
           h[i] = p0; m[i] = p1; l[i] = p2;
         }
         *reinterpret_cast<bf16x8*>(xd + u_pos[j]) = h;
@@ -388,13 +376,9 @@ static int bsplit2_launch(ConvArgs& a, hipStream_t s) {
   const size_t epi = (size_t)B2_CO * (B2_TT + 4) * sizeof(float);
   if (lds < epi) lds = epi;
   static_assert(((B2_TT - 1) * S + KT + 63) / 64 <= 4 * XU, "staging units do not cover the input window");
-  auto kern = conv1d_bsplit2_kernel<KT, S, XU>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  if (lds > 160 * 1024) {
+  constexpr auto kern = conv1d_bsplit2_kernel<KT, S, XU>;
+  allow_dynamic_lds<kern>();
+  if (lds > FAC_LDS_MAX) {
     set_error("conv1d(bf16 split, 32-row tile): %zu B of LDS", lds);
     return FAC_ERR_ARG;
   }

@@ -8,20 +8,11 @@
 
 namespace fac {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BS_CO = 64;
 constexpr int BS96_CO = 96;   // the 96-row form (conv1d_bsplit96.hip)
 constexpr int BS_NSW = 4;   // staging waves
 constexpr int BS_NSW_WIDE = 4;
 constexpr int BS_XU = 3;    // (ci group, 64-column block) staging units per staging wave
-static inline int conv_device_cus() {
-  static int cus[16] = {0};
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  if (cus[dev] == 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) cus[dev] = v;
-  return cus[dev];
-}
 // Two shapes of the same kernel (the weight layout depends on G, so the choice is a pure function of C_in):
 //   wide    (C_in >= BS_WIDE_MIN): G = 2 groups of 8 channels per stage, 4 MFMA waves, tile 64 x 256
 //   narrow  (C_in <  BS_WIDE_MIN): G = 1, tap PAIRS per MFMA (7 taps + one zero tap), 8 MFMA waves, tile 64 x 512:
@@ -32,13 +23,6 @@ static inline int conv_device_cus() {
 //   the 32- and 48-channel layers (MPD).
 constexpr int BS_WIDE_MIN = 64;
 __host__ __device__ constexpr int bs_group(int C_in) { return C_in >= BS_WIDE_MIN ? 2 : 1; }
-
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
 
 __host__ __device__ constexpr int bs_slots(int K, int G) { return (G * K + 1) & ~1; }
 
@@ -64,7 +48,7 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
   const int n_chunks = (a.C_in + 8 * G - 1) / (8 * G);
   const int dil = a.dil;
 
-  // XCD-aware work decode (see conv1d_mfma.h): each XCD walks a contiguous range of (co tile, b, t tile).  v = virtual block id.
+  // XCD-aware work decode (xcd_contiguous_id): each XCD walks a contiguous range of (co tile, b, t tile).  v = virtual block id.
   const int n_tiles = a.n_tiles;
   // Per-tile code (tile decode, staging parameters, epilogue) reads the launch arguments through a pointer to the kernarg segment
   // that is laundered once per use site and tile: otherwise hipcc hoists every scalar load of the struct out of the tile loop and
@@ -77,9 +61,7 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
     return q;
   };
   auto decode = [&](KArgP ka, int v, int& t0_, int& co0_, int& b_) {
-    const int q8 = n_tiles >> 3, r8 = n_tiles & 7;
-    const int xcd = v & 7, within = v >> 3;
-    const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int id = xcd_contiguous_id(v, n_tiles);
     const int nt = ka->n_t_tiles;
     const int tt = id % nt;
     const int rest = id / nt;
@@ -669,20 +651,16 @@ static int bsplit_launch(ConvArgs& a, hipStream_t s) {
   // (kernel header): wide shape with fp32 inputs, an even number of chunks (stage / register-set parity continues across tiles),
   // more tiles than CUs, and the epilogue tile must fit behind stage 0.
   const int n_chunks = (a.C_in + 8 * G - 1) / (8 * G);
-  int cus = conv_device_cus() & ~7;
+  int cus = device_cus() & ~7;
   a.persist = (NMW == 4 && a.x_p8 == nullptr && n_chunks % 2 == 0 && cus >= 8 && n_wg > cus &&
-               stg + (stg > epi ? stg : epi) <= 160 * 1024) ? 1 : 0;
+               stg + (stg > epi ? stg : epi) <= FAC_LDS_MAX) ? 1 : 0;
   size_t lds = a.persist ? stg + (stg > epi ? stg : epi) : (2 * stg > epi ? 2 * stg : epi);
-  if (lds > 160 * 1024) {
+  if (lds > FAC_LDS_MAX) {
     set_error("conv1d(bf16 split): tile needs %zu B of LDS (dil=%d)", lds, a.dil);
     return FAC_ERR_ARG;
   }
-  auto kern = conv1d_bsplit_kernel<KT, G, NMW, NSW, MB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_bsplit_kernel<KT, G, NMW, NSW, MB>;
+  allow_dynamic_lds<kern>();
   a.n_tiles = (int)n_wg;
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.persist ? cus : n_wg)), dim3((NMW + NSW) * 64), lds, s, a);
   return check_launch("conv1d_bsplit");

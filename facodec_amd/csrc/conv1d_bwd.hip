@@ -552,13 +552,8 @@ extern "C" int fac_conv1d_bwd_weight(const float* x, const float* dy, float* dw,
   }
   a.XWl = (WG_TT - 1) * stride + (K - 1) * dilation + 1;
   const size_t lds = ((size_t)64 * (WG_TT + 1) + (size_t)a.CIT * a.XWl) * sizeof(float);
-  FAC_REQUIRE(lds <= 160 * 1024, "conv1d_bwd_weight: tile needs %zu B of LDS", lds);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  FAC_REQUIRE(lds <= FAC_LDS_MAX, "conv1d_bwd_weight: tile needs %zu B of LDS", lds);
+  allow_dynamic_lds<conv1d_wgrad_kernel>();
   dim3 grid((C_out + 63) / 64, (C_in + a.CIT - 1) / a.CIT, S);
   hipLaunchKernelGGL(conv1d_wgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
   const long long n = (long long)C_out * C_in * K;

@@ -25,8 +25,6 @@
 
 namespace fac {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int GS_ROWS = 128;                   // output rows (channels, or (channel, phase) pairs) per tile
 constexpr int GS_COLS = 128;                   // output columns per tile
 constexpr int GS_CI = 32;                      // input channels per stage
@@ -38,13 +36,6 @@ constexpr int GS_BPL = GS_XR * GS_RB;          // one plane of the inputs
 __host__ __device__ constexpr int gs_stage_bytes(int K) { return 3 * K * GS_APL + 3 * GS_BPL; }
 __host__ __device__ constexpr int gs_stages(int K) { return K == 1 ? 3 : 2; }
 
-__device__ __forceinline__ void gs_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-
 // XOR swizzle of the INPUT planes (round 6).  The weights keep slot = piece ^ ((row >> 2) & 3): they reach the LDS by DMA and are only
 // read.  The inputs are also WRITTEN by ds_write_b128 (fp32 inputs, split in the staging waves), and a 16-byte store is serviced in
 // groups of 8 consecutive lanes = 8 consecutive rows over a 128-byte bank window (two rows): with (row >> 2) & 3 rows r and r + 2 of
@@ -53,12 +44,6 @@ __device__ __forceinline__ void gs_split3(float x, __bf16& h, __bf16& m, __bf16&
 // {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} over a 256-byte window, rows shifted by the tap) conflict-free and makes 8 aligned
 // consecutive rows hit 8 different 16-byte slots (exhaustive search over the GF(2)-linear maps of the row bits: tools/tune/lds_swizzle_search.py).
 __device__ __forceinline__ int gs_xswz(int row) { return ((row >> 2) & 1) | ((((row >> 1) ^ (row >> 3)) & 1) << 1); }
-
-__device__ __forceinline__ void gs_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // Weights (R rows, C_in, K_total taps) given through strides (element (r, ci, k) at v[r*rs + ci*cs + k*ks]) [* row_scale[r]]
 // -> [row tile][chunk][plane][tap][row 128][slot 4][8 bf16], slot = piece ^ ((row >> 2) & 3), piece = (ci % 32) / 8.
@@ -89,7 +74,7 @@ __device__ __forceinline__ void pack_gemm_split_body(const float* __restrict__ v
         if (row_scale != nullptr) w = __fmul_rn(w, sc);
       }
       __bf16 a, b, c;
-      gs_split3(w, a, b, c);
+      split3(w, a, b, c);
       h[i] = a; m[i] = b; l[i] = c;
     }
     const int slot = piece ^ ((row >> 2) & 3);
@@ -134,13 +119,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool flat = a.gflat != 0;
 
-  // XCD-aware work decode (see conv1d_mfma.h): each XCD walks a contiguous range of (row tile, clip, column tile)
+  // XCD-aware work decode (xcd_contiguous_id): each XCD walks a contiguous range of (row tile, clip, column tile)
   int n0, row0, b;
   {
-    const int n = gridDim.x;
-    const int q8 = n >> 3, r8 = n & 7;
-    const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int id = xcd_contiguous_id<unsigned>(blockIdx.x, gridDim.x);
     const int nt = a.n_t_tiles, nb = flat ? 1 : a.B;
     if (a.grt > 0) {
       // Row tile fastest (round 5): the workgroups that are co-resident on an XCD cover ALL row tiles of a few consecutive
@@ -248,7 +230,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
       issue(0, 0);
       if (NST == 3) issue(1, 1);
       if (NST == 3) landed(true); else landed(false);
-      gs_barrier();                                                 // stage 0 visible to the MFMA waves
+      wg_barrier();                                                 // stage 0 visible to the MFMA waves
       for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
@@ -257,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
             // stage (c + NST - 1) % NST was read during iteration c - 1, which every wave has left
             if (c + NST - 1 < n_chunks) issue(c + NST - 1, (i + NST - 1) % NST);
             if (c + 1 < n_chunks) landed(NST == 3 && c + 2 < n_chunks);
-            gs_barrier();
+            wg_barrier();
           }
         }
       }
@@ -343,7 +325,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           __bf16 p0, p1, p2;
-          gs_split3(uin[j] ? xr[j][i] : 0.f, p0, p1, p2);
+          split3(uin[j] ? xr[j][i] : 0.f, p0, p1, p2);
           h[i] = p0; m[i] = p1; l[i] = p2;
         }
         *reinterpret_cast<bf16x8*>(xd + u_lds[j]) = h;
@@ -374,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
     if (n_chunks > 1) { load_b(1, xb, ib); after += NBL; }
     landed(after, xa);
     write_b(0, xa, ia);
-    gs_barrier();                                 // stage 0 visible to the MFMA waves
+    wg_barrier();                                 // stage 0 visible to the MFMA waves
     for (int base = 0; base < n_chunks; base += 6) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) {               // static LDS stage (i % NST) and register slot (i % 2)
@@ -394,7 +376,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
             if (i % 2 == 0) { landed(aft, xb); write_b((i + 1) % NST, xb, ib); }
             else { landed(aft, xa); write_b((i + 1) % NST, xa, ia); }
           }
-          gs_barrier();
+          wg_barrier();
         }
       }
     }
@@ -444,7 +426,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
           Bf[n][p] = *reinterpret_cast<const bf16x8*>(st + boff[k][ks] + p * GS_BPL + n * 32 * GS_RB);
     };
 
-    gs_barrier();   // stage 0 staged
+    wg_barrier();   // stage 0 staged
     bf16x8 A[2][2][3], Bf[2][2][3];
     for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
@@ -467,7 +449,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
                   acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[step & 1][m][TA[q]], Bf[step & 1][n][TB[q]], acc[m][n], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
-          gs_barrier();
+          wg_barrier();
         }
       }
     }
@@ -483,7 +465,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
         for (int r = 0; r < 16; ++r)
           tile[(mh * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq) * EP + nh * 64 + n * 32 + l31] = acc[m][n][r];
   }
-  gs_barrier();
+  wg_barrier();
 
   // ---- epilogue by all eight waves: one lane = 4 consecutive output samples of one channel
   {
@@ -608,12 +590,8 @@ bool conv_gsplit_ok(const ConvArgs& a) {
 
 template <int K>
 static int gsplit_launch(ConvArgs& a, hipStream_t s) {
-  auto kern = conv1d_gemm_split_kernel<K>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_gemm_split_kernel<K>;
+  allow_dynamic_lds<kern>();
   size_t lds = (size_t)gs_stages(K) * gs_stage_bytes(K);
   const size_t epi = (size_t)GS_ROWS * (GS_COLS + 4) * sizeof(float);
   if (lds < epi) lds = epi;

@@ -26,7 +26,6 @@
 
 namespace fac {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;
 
@@ -117,16 +116,11 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? CONV_WPE : 3)) 
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // [0, NMW): MFMA waves, then 4 staging waves
 
-  // Work decode.  Workgroups are dispatched round-robin over the 8 XCDs (observed: block i -> XCD
-  // i % 8, speed only, never correctness): remap so that each XCD walks a CONTIGUOUS range of the tile
-  // list ordered (co-tile slowest, then batch/phase, then time tile).  The workgroups resident on one
-  // XCD then share one C_out tile, i.e. stream the same weight slabs through that XCD's private L2.
+  // Work decode: each XCD walks a contiguous range (xcd_contiguous_id) of the tile list ordered (co-tile slowest, then
+  // batch/phase, then time tile).
   int t0, co0, b, phase;
   {
-    const int n = gridDim.x;
-    const int q8 = n >> 3, r8 = n & 7;
-    const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int id = xcd_contiguous_id<unsigned>(blockIdx.x, gridDim.x);
     const int nt = a.n_t_tiles, nbp = a.B * a.n_phase;
     const int tt = id % nt;
     const int rest = id / nt;
@@ -668,17 +662,12 @@ int launch_cfg(ConvArgs& a, hipStream_t s) {
     const size_t epi = (size_t)CO_TILE * (T_TILE + 4) * sizeof(float);
     if (lds < epi) lds = epi;
   }
-  if (lds > 160 * 1024) {
+  if (lds > FAC_LDS_MAX) {
     set_error("conv1d: tile needs %zu B of LDS (K=%d stride=%d dil=%d)", lds, a.K, a.stride, a.dil);
     return FAC_ERR_ARG;
   }
-  auto kern = conv1d_mfma_kernel<MB, NB, WM, WN, KT, FUSE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_mfma_kernel<MB, NB, WM, WN, KT, FUSE>;
+  allow_dynamic_lds<kern>();
   a.n_t_tiles = (a.T_out + T_TILE - 1) / T_TILE;
   if (a.rp > 1 && !((WM * WN == 8) && !FUSE && CO_TILE == 128)) {
     set_error("conv1d: row_phases needs the 128-row all-waves-epilogue tile");

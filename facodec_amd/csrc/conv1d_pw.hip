@@ -178,7 +178,7 @@ bool conv_pw_ok(const ConvArgs& a) {
   const int co = pw_slice_channels(a.C_in, a.C_out);
   if (!co || a.C_out_pad != a.C_out) return false;
   if (a.C_in % (2 * PW_D) != 0 || a.C_in < 2 * PW_D) return false;
-  if (((size_t)a.C_in * co + 5 * co) * sizeof(float) > 160 * 1024) return false;
+  if (((size_t)a.C_in * co + 5 * co) * sizeof(float) > FAC_LDS_MAX) return false;
   // enough column blocks that every wave slot of a 256-CU chip walks at least two of them
   const long long items = (long long)a.B * ((a.T_out + 31) / 32);
   const int nsplit = (co == 96 || co == 64) ? 1 : 2;                  // see conv_dispatch_pw
@@ -196,19 +196,10 @@ static int pw_launch(ConvArgs& a, hipStream_t s) {
   }
   constexpr int CO = 32 * MBW * NSPLIT;
   const size_t lds = ((size_t)a.C_in * CO + 5 * CO) * sizeof(float);
-  auto kern = conv1d_pw_kernel<MBW, NSPLIT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+  constexpr auto kern = conv1d_pw_kernel<MBW, NSPLIT>;
+  allow_dynamic_lds<kern>();
+  int n_cu = device_cus();
+  if (n_cu <= 0) n_cu = 256;
   constexpr int per_wg = PW_WAVES / NSPLIT;             // column blocks a workgroup works on at a time
   const int n_slices = a.C_out / CO;
   // one persistent workgroup per CU, in groups of 8 x n_slices (8 XCDs x the slices of one set of column blocks)

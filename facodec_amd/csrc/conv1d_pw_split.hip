@@ -18,15 +18,6 @@
 
 namespace fac {
 
-typedef __bf16 pws_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void pws_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-
 // MBW: accumulator blocks per wave; NSPLIT: waves sharing a column block (C_out slice = 32 * MBW * NSPLIT); WAVES per workgroup;
 // D: K steps of 16 input channels in flight per wave (C_in % (16 D) == 0)
 template <int MBW, int NSPLIT, int WAVES, int D>
@@ -51,17 +42,17 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pws_kernel(ConvArgs a, int 
       const int mb = rest % NB, s = rest / NB;
       const int co = co_base + 32 * mb + (ln & 31);
       const int ci0 = 16 * s + 8 * (ln >> 5);
-      pws_bf16x8 h, m, l;
+      bf16x8 h, m, l;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         __bf16 a0, a1, a2;
-        pws_split3(a.w[(long long)(ci0 + j) * a.C_out_pad + co], a0, a1, a2);
+        split3(a.w[(long long)(ci0 + j) * a.C_out_pad + co], a0, a1, a2);
         h[j] = a0; m[j] = a1; l[j] = a2;
       }
       unsigned char* dst = pws_sm + ((size_t)(s * NB + mb) * 3) * 1024 + ln * 16;
-      *reinterpret_cast<pws_bf16x8*>(dst) = h;
-      *reinterpret_cast<pws_bf16x8*>(dst + 1024) = m;
-      *reinterpret_cast<pws_bf16x8*>(dst + 2048) = l;
+      *reinterpret_cast<bf16x8*>(dst) = h;
+      *reinterpret_cast<bf16x8*>(dst + 1024) = m;
+      *reinterpret_cast<bf16x8*>(dst + 2048) = l;
     }
     for (int i = tid; i < CO; i += WAVES * 64) {
       const int co = co_base + i;
@@ -125,11 +116,11 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pws_kernel(ConvArgs a, int 
 #pragma unroll
       for (int q = 0; q < D; ++q) {
         const int s = s0 + q;
-        pws_bf16x8 B[3];
+        bf16x8 B[3];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           __bf16 b0, b1, b2;
-          pws_split3(xr[q][j], b0, b1, b2);
+          split3(xr[q][j], b0, b1, b2);
           B[0][j] = b0; B[1][j] = b1; B[2][j] = b2;
         }
         // refill this slot with K step s + D (the next block's first rows during the last trip)
@@ -139,9 +130,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pws_kernel(ConvArgs a, int 
         const unsigned char* as = Al + (size_t)s * NB * 3 * 1024;
 #pragma unroll
         for (int m = 0; m < MBW; ++m) {
-          const pws_bf16x8 A0 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 0) * 1024);
-          const pws_bf16x8 A1 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 1) * 1024);
-          const pws_bf16x8 A2 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 2) * 1024);
+          const bf16x8 A0 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 0) * 1024);
+          const bf16x8 A1 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 1) * 1024);
+          const bf16x8 A2 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 2) * 1024);
           // smallest terms first (as conv1d_gemm_split.hip): mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B[1], acc[m], 0, 0, 0);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, B[0], acc[m], 0, 0, 0);
@@ -220,17 +211,17 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pwt_kernel(ConvArgs a, int 
       const int mb = rest % NB, s = rest / NB;
       const int row = row_base + 32 * mb + (ln & 31);
       const int v0 = 16 * s + 8 * (ln >> 5);
-      pws_bf16x8 h, m, l;
+      bf16x8 h, m, l;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         __bf16 a0, a1, a2;
-        pws_split3(a.w[(long long)(v0 + j) * a.C_out_pad + row], a0, a1, a2);
+        split3(a.w[(long long)(v0 + j) * a.C_out_pad + row], a0, a1, a2);
         h[j] = a0; m[j] = a1; l[j] = a2;
       }
       unsigned char* dst = pws_sm + ((size_t)(s * NB + mb) * 3) * 1024 + ln * 16;
-      *reinterpret_cast<pws_bf16x8*>(dst) = h;
-      *reinterpret_cast<pws_bf16x8*>(dst + 1024) = m;
-      *reinterpret_cast<pws_bf16x8*>(dst + 2048) = l;
+      *reinterpret_cast<bf16x8*>(dst) = h;
+      *reinterpret_cast<bf16x8*>(dst + 1024) = m;
+      *reinterpret_cast<bf16x8*>(dst + 2048) = l;
     }
     for (int i = tid; i < CO; i += WAVES * 64) {
       const int ch = (row_base + i) / RP;
@@ -296,11 +287,11 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pwt_kernel(ConvArgs a, int 
 #pragma unroll
       for (int q = 0; q < D; ++q) {
         const int s = s0 + q;
-        pws_bf16x8 B[3];
+        bf16x8 B[3];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           __bf16 b0, b1, b2;
-          pws_split3(xr[q][j] * cc.f[j % KT], b0, b1, b2);
+          split3(xr[q][j] * cc.f[j % KT], b0, b1, b2);
           B[0][j] = b0; B[1][j] = b1; B[2][j] = b2;
         }
         if (last) {
@@ -313,9 +304,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv1d_pwt_kernel(ConvArgs a, int 
         const unsigned char* as = Al + (size_t)s * NB * 3 * 1024;
 #pragma unroll
         for (int m = 0; m < MBW; ++m) {
-          const pws_bf16x8 A0 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 0) * 1024);
-          const pws_bf16x8 A1 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 1) * 1024);
-          const pws_bf16x8 A2 = *reinterpret_cast<const pws_bf16x8*>(as + (m * 3 + 2) * 1024);
+          const bf16x8 A0 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 0) * 1024);
+          const bf16x8 A1 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 1) * 1024);
+          const bf16x8 A2 = *reinterpret_cast<const bf16x8*>(as + (m * 3 + 2) * 1024);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B[1], acc[m], 0, 0, 0);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, B[0], acc[m], 0, 0, 0);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, B[2], acc[m], 0, 0, 0);
@@ -395,12 +386,8 @@ static int pws_launch(ConvArgs& a, hipStream_t s) {
   }
   constexpr int CO = 32 * MBW * NSPLIT;
   const size_t lds = (size_t)(a.C_in / 16) * (CO / 32) * 3 * 1024 + 5 * CO * sizeof(float);
-  auto kern = conv1d_pws_kernel<MBW, NSPLIT, WAVES, D>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_pws_kernel<MBW, NSPLIT, WAVES, D>;
+  allow_dynamic_lds<kern>();
   constexpr int per_wg = WAVES / NSPLIT;
   const int n_slices = a.C_out / CO;
   long long groups = 256 / (8 * n_slices);
@@ -450,12 +437,8 @@ static int pwt_launch(ConvArgs& a, hipStream_t s) {
     return FAC_ERR_ARG;
   }
   const size_t lds = (size_t)(a.C_in * KT / 16) * 2 * 3 * 1024 + 3 * 64 * sizeof(float);
-  auto kern = conv1d_pwt_kernel<KT, S, RP, WAVES, D>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_pwt_kernel<KT, S, RP, WAVES, D>;
+  allow_dynamic_lds<kern>();
   const int n_slices = a.C_out * RP / 64;
   long long groups = 256 / (8 * n_slices);
   const long long need = (n_items + 8 * WAVES - 1) / (8 * WAVES);

@@ -405,11 +405,7 @@ int conv_dispatch_skinny(ConvArgs& a, void* ws, long long ws_bytes, hipStream_t 
   int tiles;
   const SkinnyGeom g = skinny_geom(a, &tiles);
   (void)ws_bytes;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_skinny_kernel<kSkinnyU>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    attr_set = true;
-  }
+  allow_dynamic_lds<conv1d_skinny_kernel<kSkinnyU>>(65536);
   float* part = reinterpret_cast<float*>(ws);
   const dim3 grid(g.co_tiles, g.S, g.n_cb * a.n_phase);
   hipLaunchKernelGGL(conv1d_skinny_kernel<kSkinnyU>, grid, dim3(256), 65536, s, a, g, part);

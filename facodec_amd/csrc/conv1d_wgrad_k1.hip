@@ -26,8 +26,6 @@
 
 namespace fac {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int WK1_WAVES = 4;      // one per SIMD: a wave holds a whole RB x CB quadrant (up to 144 accumulator + 192 fragment registers)
 
 struct Wk1Args {

@@ -30,10 +30,6 @@
 
 namespace fac {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WS_CO = 128;          // output channels per tile (A rows)
 constexpr int WS_NC = 128;          // (ci, k) columns per tile
@@ -62,13 +58,6 @@ struct WsArgs {
   int n_tt;            // 32-step time tiles per clip
   int tiles_per_split;
 };
-
-__device__ __forceinline__ void split3w(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
 
 // dst[p][row * s + ph][u] = plane p of pad(src[row])[u * s + ph - pad_left]  (0 beyond the padded signal), u < U (U % 8 == 0).
 // One thread = 8 consecutive u of one destination row: three 16-byte stores.
@@ -104,7 +93,7 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 a, b, c;
-      split3w(v[j], a, b, c);
+      split3(v[j], a, b, c);
       h[j] = a; m[j] = b; l[j] = c;
     }
     unsigned char* d = dst + (drow * U + uq * 8) * 2;
@@ -137,7 +126,7 @@ __global__ __launch_bounds__(256) void split_planes_rowsum_kernel(const float* _
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 a, b, c;
-      split3w(v[j], a, b, c);
+      split3(v[j], a, b, c);
       h[j] = a; m[j] = b; l[j] = c;
     }
     unsigned char* d = dst + (row * U + uq * 8) * 2;
@@ -407,7 +396,7 @@ static int ws_geometry(int B, int C_in_real, int T_in, int C_out, int T_out, int
   for (int p = 1; p <= 8; ++p) {
     const int pitch = 8 * a->nq + 8 * p;
     const size_t st = ((size_t)WS_A_STAGE + (size_t)a->NCP * 3 * a->R * pitch + 15) & ~(size_t)15;
-    if (2 * st > 160 * 1024) break;
+    if (2 * st > FAC_LDS_MAX) break;
     long score = 0;
     for (int blk = 0; blk < 4; ++blk) {               // the four 32-column blocks of the tile
       int cnt[64] = {0};
@@ -512,12 +501,6 @@ struct WkArgs {
                              // wave layouts; bit 1: their clamped duplicate rows are not staged
 };
 
-__device__ __forceinline__ void wk_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // 128 x 128 tile: 4 MFMA waves (64 x 64 each) + 4 DMA waves, three LDS stages of 48 KB.  (A 256 x 128 tile with eight MFMA waves
 // and two stages of 72 KB measured slower on every layer, C = 512 k7: 145 vs 163 TFLOP/s-eq, LSTM W_ih: 121 vs 135,
 // profiles/r04_wgrad_wide_tile.log: two stages expose the DMA latency that three hide.)
@@ -530,9 +513,9 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware order (round 5): the launch is 1-D; workgroup id i runs on XCD i % 8 (each XCD has its own L2), and XCD k takes
-  // the contiguous range [k * per_xcd, (k + 1) * per_xcd) of the logical order (row tile fastest, then column blocks, slice
-  // slowest).  Workgroups of one (b, t) slice read the SAME rows of both operand planes at the same time -- all row tiles share
+  // XCD-aware order (round 5, host half: xcd_padded_grid): the launch is 1-D; workgroup id i runs on XCD i % 8 (each XCD has its own
+  // L2), and XCD k takes the contiguous range [k * per_xcd, (k + 1) * per_xcd) of the logical order (row tile fastest, then column
+  // blocks, slice slowest).  Workgroups of one (b, t) slice read the SAME rows of both operand planes at the same time -- all row tiles share
   // the x planes, all column blocks the dy planes -- so a slice's workgroups now meet in one L2 instead of eight.
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (a.per_xcd > 0) {
@@ -625,7 +608,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
     issue(0, 0);
     if (n_chunks > 1) issue(1, 1);
     landed(n_chunks > 1);
-    wk_barrier();                                 // stage 0 visible to the MFMA waves
+    wg_barrier();                                 // stage 0 visible to the MFMA waves
     for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
       for (int i = 0; i < NST; ++i) {             // static LDS stage
@@ -634,7 +617,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
           // stage (c + NST - 1) % NST was read during iteration c - 1, which every wave has left
           if (c + NST - 1 < n_chunks) issue(c + NST - 1, (i + NST - 1) % NST);
           if (c + 1 < n_chunks) landed(c + 2 < n_chunks);
-          wk_barrier();
+          wg_barrier();
         }
       }
     }
@@ -692,7 +675,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
 #pragma unroll
         for (int n = 0; n < NB; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[m], y[n], acc[m][n], 0, 0, 0);
     };
-    wk_barrier();   // stage 0 staged
+    wg_barrier();   // stage 0 staged
     rd_a(sm, 2, Alo); rd_b(sm, 0, Bhi[0]); rd_a(sm, 0, Ahi[0]); rd_b(sm, 2, Blo);
     // chunk c lives in LDS stage c % 3 and in fragment set c & 1: the pattern repeats every 6 chunks
     for (int base = 0; base < n_chunks; base += 6) {
@@ -710,7 +693,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
           __builtin_amdgcn_sched_barrier(0);
           __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0), as a builtin so that the compiler's own wait-count bookkeeping
                                                    // sees it: every fragment of this stage is in registers
-          wk_barrier();                            // this stage may be overwritten; the next one has landed
+          wg_barrier();                            // this stage may be overwritten; the next one has landed
           // (behind the last chunk this reads a stage nobody filled: valid LDS, values never used -- no branch, no join)
           rd_a(stn, 2, Alo); rd_b(stn, 0, Bhi[nxt]); rd_a(stn, 0, Ahi[nxt]); rd_b(stn, 2, Blo);
           __builtin_amdgcn_sched_barrier(0);
@@ -790,7 +773,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
         Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
       }
     };
-    wk_barrier();   // stage 0 staged
+    wg_barrier();   // stage 0 staged
     for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
       for (int i = 0; i < NST; ++i) {
@@ -810,7 +793,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-          wk_barrier();
+          wg_barrier();
         }
       }
     }
@@ -847,7 +830,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
         Bd[p] = *reinterpret_cast<const bf16x8*>(st + boff1 + p * WK_PLANE + poff[ks]);
       }
     };
-    wk_barrier();   // stage 0 staged
+    wg_barrier();   // stage 0 staged
     for (int base = 0; base < n_chunks; base += NST) {
 #pragma unroll
       for (int i = 0; i < NST; ++i) {
@@ -867,7 +850,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
                 accr[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1[ks & 1][m][TA[q]], B1[ks & 1][TB[q]], accr[m], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
-          wk_barrier();
+          wg_barrier();
         }
       }
     }
@@ -915,7 +898,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
         Bf[n][p] = *reinterpret_cast<const bf16x8*>(st + boff + p * WK_PLANE + n * 32 * WK_ROWB + poff[ks]);
   };
 
-  wk_barrier();   // stage 0 staged
+  wg_barrier();   // stage 0 staged
   // both operands' fragments are requested a step ahead (two register sets)
   bf16x8 A[2][2][3], Bf[2][2][3];
   for (int base = 0; base < n_chunks; base += NST) {
@@ -943,7 +926,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_kmajor_kernel(WkArgs a) {
                 acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ks & 1][m][TA[q]], Bf[ks & 1][n][TB[q]], acc[m][n], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
-        wk_barrier();
+        wg_barrier();
       }
     }
   }
@@ -1035,12 +1018,8 @@ static int wk_geometry(int B, int C_in_real, int T_in, int C_out, int T_out, int
 
 template <int NB, int D>
 static void ws_launch(const WsArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-  auto kern = conv1d_wgrad_planes_kernel<NB, D>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = conv1d_wgrad_planes_kernel<NB, D>;
+  allow_dynamic_lds<kern>();
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, a);
 }
 
@@ -1136,14 +1115,8 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
       FAC_REQUIRE(db == nullptr, "conv1d_bwd_weight_split_db: too many rows for the fused bias gradient (B * C_out > 65535)");
       hipLaunchKernelGGL(split_planes_kernel, dim3(gb), dim3(256), 0, st, x, bp, (long long)B * C_in, T_in, T_ext, T_pad, stride, k.UB,
                          pad_left, pad_mode, k.b_plane_bytes);
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_wgrad_kmajor_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-      }
+      allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<false>>();
+      allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<true>>();
       dim3 grid((C_out + 127) / 128, (k.NBk + 3) / 4, S);
       // Measured policy (profiles/r05_wgrad_xcd_ksplit.log, same box, B = 16 training shapes):
       //  * XCD-aware order when the launch has at least 5 (b, t) slices: +4 .. +20 % on the ResidualUnit / strided / transposed
@@ -1158,9 +1131,9 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
       k.narrow_rows = narrow_on ? 3 : 0;      // bit 0: column-split layouts; bit 1: their duplicate rows are not staged
       k.gx = (int)grid.x; k.gy = (int)grid.y; k.gz = (int)grid.z; k.per_xcd = 0;
       if (xcd_order) {
-        const long long total = (long long)grid.x * grid.y * grid.z;
-        k.per_xcd = (int)((total + 7) / 8);
-        grid = dim3((unsigned)(8 * k.per_xcd), 1, 1);
+        const XcdGrid xg = xcd_padded_grid((long long)grid.x * grid.y * grid.z);
+        k.per_xcd = xg.per_xcd;
+        grid = dim3(xg.grid, 1, 1);
       }
       if (ksplit) hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<true>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
       else hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<false>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);

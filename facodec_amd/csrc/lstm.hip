@@ -17,8 +17,6 @@
 
 namespace fac {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // NW waves split the K = H reduction; GPW = k-groups (of 8) per wave, 0 = run-time loop.  With GPW
 // known at compile time every weight / state load of the step is issued before the first MFMA, so
 // the step pays ONE memory round trip (the step is latency- and weight-bandwidth-bound: M = 32).

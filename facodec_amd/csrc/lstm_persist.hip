@@ -38,9 +38,6 @@
 
 namespace fac {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int LSTM_SYNC_SLOTS = 64;
 constexpr int LSTM_MAX_WG = 256;
 struct alignas(256) LstmSync {
@@ -293,24 +290,15 @@ __global__ __launch_bounds__(1024) void lstm_fwd_persist_kernel(const float* __r
 //             per plane it writes 32 lanes x 16 B = 512 contiguous bytes = four whole 128-byte lines of a FRESH region per
 //             step that nobody else writes (the exchange above), by write-through stores.
 //             Consumers read their 3*NK pieces per lane with plain 16-byte loads through a 4-step register window.
-typedef __bf16 ls_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float ls_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int LS_NW = 8;
 
-__device__ __forceinline__ void ls_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-
 // 16-byte piece at (uniform base, lane offset): request only; the value is valid behind ls_wait_pieces
-__device__ __forceinline__ ls_bf16x8 ls_load_piece(const ls_bf16x8* base, unsigned lane_off) {
-  ls_bf16x8 v;
+__device__ __forceinline__ bf16x8 ls_load_piece(const bf16x8* base, unsigned lane_off) {
+  bf16x8 v;
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(lane_off), "s"(base) : "memory");
   return v;
 }
-__device__ __forceinline__ void ls_wait_pieces(ls_bf16x8 (&d)[3], int behind) {
+__device__ __forceinline__ void ls_wait_pieces(bf16x8 (&d)[3], int behind) {
   switch (behind) {   // constant after unrolling
     case 0: asm volatile("s_waitcnt vmcnt(0)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2])::"memory"); break;
     case 3: asm volatile("s_waitcnt vmcnt(3)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2])::"memory"); break;
@@ -321,7 +309,7 @@ __device__ __forceinline__ void ls_wait_pieces(ls_bf16x8 (&d)[3], int behind) {
 
 // W_hh (4H, H) -> packed[((ub*8 + w)*NK + s)*3 + plane][lane]: A fragment of step s of wave w (lane: row l%32 = gate*8 + unit,
 // k = (w*NK + s)*16 + 8*(l/32) .. +8)
-__global__ __launch_bounds__(256) void pack_whh_split_kernel(const float* __restrict__ w, ls_bf16x8* __restrict__ out, int H) {
+__global__ __launch_bounds__(256) void pack_whh_split_kernel(const float* __restrict__ w, bf16x8* __restrict__ out, int H) {
   const int NK = H / (16 * LS_NW);
   const long long n = (long long)(H / 8) * LS_NW * NK * 64;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long long)gridDim.x * 256) {
@@ -334,11 +322,11 @@ __global__ __launch_bounds__(256) void pack_whh_split_kernel(const float* __rest
     const int l31 = lane & 31, kq = lane >> 5;
     const int row = (l31 >> 3) * H + ub * 8 + (l31 & 7);
     const int k0 = (wv * NK + s) * 16 + 8 * kq;
-    ls_bf16x8 ph, pm, pl;
+    bf16x8 ph, pm, pl;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       __bf16 a, b, c;
-      ls_split3(w[(long long)row * H + k0 + i], a, b, c);
+      split3(w[(long long)row * H + k0 + i], a, b, c);
       ph[i] = a; pm[i] = b; pl[i] = c;
     }
     const long long o = (r * NK + s) * 3;      // r = ub*8 + wv
@@ -350,8 +338,8 @@ __global__ __launch_bounds__(256) void pack_whh_split_kernel(const float* __rest
 
 template <int NK>
 __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(const float* __restrict__ pre,          // (4H, T, BP)
-                                                                           const ls_bf16x8* __restrict__ wsplit,   // pack_whh_split_kernel
-                                                                           ls_bf16x8* hs,                          // T x 3 x H/16 x 64 pieces
+                                                                           const bf16x8* __restrict__ wsplit,   // pack_whh_split_kernel
+                                                                           bf16x8* hs,                          // T x 3 x H/16 x 64 pieces
                                                                            float* __restrict__ yT,                 // (H, T, BP)
                                                                            int slot, int T, int H, int BP) {
   constexpr int WIN = NK < 4 ? NK : 4;
@@ -367,9 +355,9 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
   const int nS = H >> 4;                         // 16-k steps of the whole contraction
   const long long hregion = 3ll * nS * 64;       // pieces per time step
 
-  ls_bf16x8 W[NK][3];
+  bf16x8 W[NK][3];
   {
-    const ls_bf16x8* wp = wsplit + ((long long)(ub * LS_NW + wave) * NK * 3) * 64 + lane;
+    const bf16x8* wp = wsplit + ((long long)(ub * LS_NW + wave) * NK * 3) * 64 + lane;
 #pragma unroll
     for (int s = 0; s < NK; ++s)
 #pragma unroll
@@ -398,14 +386,14 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
         // The pieces of step s are requested WIN steps ahead.  hipcc sinks plain loads down to their first use (one memory round
         // trip per step), so the loads and their waits are explicit: in-order return, s_waitcnt vmcnt(n) with n = the loads issued
         // behind the ones needed (tools/check_inflight_regs.py replays the queue on the ISA: tests/test_isa_inflight.py).
-        const ls_bf16x8* hp;                                                                       // uniform: scalar base
+        const bf16x8* hp;                                                                       // uniform: scalar base
         {
           const unsigned long long a = reinterpret_cast<unsigned long long>(hs + (long long)(t - 1) * hregion + (long long)(wave * NK) * 64);
           const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-          hp = reinterpret_cast<const ls_bf16x8*>(((unsigned long long)hi << 32) | lo);
+          hp = reinterpret_cast<const bf16x8*>(((unsigned long long)hi << 32) | lo);
         }
-        ls_bf16x8 hb[WIN][3];
-        ls_f32x16 acc;
+        bf16x8 hb[WIN][3];
+        f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -450,7 +438,7 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
       hv = __fmul_rn(og, tanhf(c_new));
       if (t + 1 < T) {
         __bf16 a, b, c;
-        ls_split3(hv, a, b, c);
+        split3(hv, a, b, c);
         piece[0][col][u] = a;
         piece[1][col][u] = b;
         piece[2][col][u] = c;
@@ -459,7 +447,7 @@ __global__ __launch_bounds__(LS_NW * 64) void lstm_fwd_persist_split_kernel(cons
     if (t + 1 < T) {
       __syncthreads();
       if (tid < 96) {    // first: the write-through of the pieces is the critical path
-        const ls_bf16x8 v = *reinterpret_cast<const ls_bf16x8*>(&piece[sp][sc][0]);
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(&piece[sp][sc][0]);
         asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(hs + (long long)t * hregion + spos), "v"(v) : "memory");
       }
     }
@@ -615,14 +603,6 @@ static int lstm_sync_slot(hipStream_t stream) {
 
 constexpr int LSTM_MAX_DEV = 16;
 
-static int device_cus() {
-  static int cus[LSTM_MAX_DEV] = {0};
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LSTM_MAX_DEV) return 0;
-  if (cus[dev] == 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) cus[dev] = v;
-  return cus[dev];
-}
-
 // The resident kernels spin on flags written by the OTHER workgroups of their grid, so the whole grid must be resident at once
 // (ADVICE r3).  Two guards, both on the host:
 //  * the runtime's own occupancy figure for the kernel x the device's CUs must cover the grid (a workgroup is 1024 threads + ~35 KB
@@ -737,7 +717,7 @@ static bool persist_split_shape_ok(int H, int B) {
 
 using FwdKern = void (*)(const float*, const float*, float*, float*, float*, float*, int, int, int, int);
 using BwdKern = void (*)(const float*, const float*, const float*, const float*, float*, float*, float*, int, int, int, int);
-using SplitKern = void (*)(const float*, const ls_bf16x8*, ls_bf16x8*, float*, int, int, int, int);
+using SplitKern = void (*)(const float*, const bf16x8*, bf16x8*, float*, int, int, int, int);
 
 static FwdKern fwd_kernel_for(int H, int B) {
   switch ((H / 64) * 10 + (B + 15) / 16) {
@@ -832,7 +812,7 @@ extern "C" int fac_mask_flags_if(float* flags, int n, const float* poison, fac_s
 extern "C" int fac_pack_lstm_whh_split(const float* w_hh, void* packed, int H, fac_stream_t stream) {
   using namespace fac;
   FAC_REQUIRE(w_hh && packed && H > 0 && H % 128 == 0, "pack_lstm_whh_split: H must be a multiple of 128");
-  hipLaunchKernelGGL(pack_whh_split_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, w_hh, reinterpret_cast<ls_bf16x8*>(packed), H);
+  hipLaunchKernelGGL(pack_whh_split_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, w_hh, reinterpret_cast<bf16x8*>(packed), H);
   return check_launch("pack_lstm_whh_split");
 }
 
@@ -853,8 +833,8 @@ extern "C" int fac_lstm_layer_fwd_persist_split(const float* pre, const void* ws
   {
     ResidentLaunch order((hipStream_t)stream);
     arm_timeout_word((hipStream_t)stream);
-    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(LS_NW * 64), 0, (hipStream_t)stream, pre, reinterpret_cast<const ls_bf16x8*>(wsplit),
-                       reinterpret_cast<ls_bf16x8*>(hsplit), yT, slot, T, H, BP);
+    hipLaunchKernelGGL(kern, dim3(H / 8), dim3(LS_NW * 64), 0, (hipStream_t)stream, pre, reinterpret_cast<const bf16x8*>(wsplit),
+                       reinterpret_cast<bf16x8*>(hsplit), yT, slot, T, H, BP);
     rc = check_launch("lstm_layer_fwd_persist_split");
   }
   return rc;

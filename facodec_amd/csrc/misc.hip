@@ -734,16 +734,11 @@ extern "C" int fac_attention(const float* q, const float* k, const float* v, con
                              float* out, int B, int n_heads, int dk, int T, fac_stream_t stream) {
   FAC_REQUIRE(q && k && v && out && B > 0 && n_heads > 0 && dk > 0 && T > 0, "attention: bad arguments");
   size_t lds = ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float);
-  FAC_REQUIRE(lds <= 160 * 1024, "attention: T=%d too long for the LDS score tile", T);
+  FAC_REQUIRE(lds <= FAC_LDS_MAX, "attention: T=%d too long for the LDS score tile", T);
   const size_t lds_v = lds + (size_t)16 * (T + 1) * sizeof(float);       // + 16 rows of V per pass
-  const int stage_v = lds_v <= 160 * 1024 ? 1 : 0;
+  const int stage_v = lds_v <= FAC_LDS_MAX ? 1 : 0;
   if (stage_v) lds = lds_v;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  allow_dynamic_lds<attention_kernel>();
   dim3 grid((T + 15) / 16, n_heads, B);
   hipLaunchKernelGGL(attention_kernel, grid, dim3(256), lds, (hipStream_t)stream, q, k, v, mask, out,
                      n_heads, dk, T, stage_v);
@@ -865,15 +860,14 @@ extern "C" int fac_stft_frames_bwd(const float* dframes, float* dwave, int B, in
 // One thread = one (clip, 8-channel group, time step): 8 coalesced fp32 loads (rows T apart), optional Snake, the exact
 // round-to-nearest three-way bf16 split, three 16-byte stores (one per plane).  HBM-bound: 4 B read + 6 B written per element.
 namespace fac {
-typedef __bf16 p8_bf16x8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(256) void to_p8_kernel(const float* __restrict__ x, const float* __restrict__ alpha, p8_bf16x8* __restrict__ out,
+__global__ __launch_bounds__(256) void to_p8_kernel(const float* __restrict__ x, const float* __restrict__ alpha, bf16x8* __restrict__ out,
                                                     int C8, int T, long long n, long long plane_units) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int t = (int)(i % T);
     const long long bg = i / T;                 // b * C8 + g
     const int g = (int)(bg % C8);
     const float* row = x + (bg * 8) * T + t;
-    p8_bf16x8 h, m, l;
+    bf16x8 h, m, l;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float v = row[(long long)k * T];
@@ -881,10 +875,8 @@ __global__ __launch_bounds__(256) void to_p8_kernel(const float* __restrict__ x,
         const float al = alpha[g * 8 + k];
         v = snake_apply(v, al, snake_inv(al));
       }
-      const __bf16 a = (__bf16)v;
-      const float r1 = v - (float)a;
-      const __bf16 b2 = (__bf16)r1;
-      const __bf16 c = (__bf16)(r1 - (float)b2);
+      __bf16 a, b2, c;
+      split3(v, a, b2, c);
       h[k] = a; m[k] = b2; l[k] = c;
     }
     out[i] = h;
@@ -892,7 +884,7 @@ __global__ __launch_bounds__(256) void to_p8_kernel(const float* __restrict__ x,
     out[2 * plane_units + i] = l;
   }
   if (blockIdx.x == 0 && threadIdx.x < 3) {     // the zero unit that closes every plane (what consumers read for padding columns)
-    p8_bf16x8 z;
+    bf16x8 z;
 #pragma unroll
     for (int k = 0; k < 8; ++k) z[k] = (__bf16)0.f;
     out[(long long)threadIdx.x * plane_units + n] = z;
@@ -905,6 +897,6 @@ extern "C" int fac_to_p8(const float* x, const float* alpha, void* out, int B, i
   FAC_REQUIRE(x && out && B > 0 && C > 0 && C % 8 == 0 && T > 0, "to_p8: bad arguments (C must be a multiple of 8)");
   const long long n = (long long)B * (C / 8) * T;
   const int blocks = (int)((n + 255) / 256 < 262144 ? (n + 255) / 256 : 262144);
-  hipLaunchKernelGGL(to_p8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, alpha, reinterpret_cast<p8_bf16x8*>(out), C / 8, T, n, n + 1);
+  hipLaunchKernelGGL(to_p8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, alpha, reinterpret_cast<bf16x8*>(out), C / 8, T, n, n + 1);
   return check_launch("to_p8");
 }

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void vq_fwd_kernel(VqArgs a, int n_tiles, int 
   float* wsm = reinterpret_cast<float*>(bestk + VG * VT);   // [D][8] in-proj weights
 
   const int tid = threadIdx.x, tl = tid & (VT - 1), g = tid >> 4, wave = tid >> 6;
-  // XCD-aware decode: workgroup id i runs on XCD i % 8
+  // XCD-aware decode (host half: xcd_padded_grid): workgroup id i runs on XCD i % 8
   const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   if ((blockIdx.x >> 3) >= per_xcd || logical >= a.B * n_tiles) return;
   const int b = logical / n_tiles;
@@ -445,22 +445,12 @@ extern "C" int fac_vq_fwd(const fac_vq_desc* d, fac_stream_t stream) {
   a.loss_part = d->loss_part; a.codes_bs = d->codes_bs;
   a.B = d->B; a.D = d->D; a.T = d->T; a.Kc = d->Kc;
   const size_t lds = ((size_t)d->Kc * VQ_CD + ((d->Kc + 3) & ~3) + 4 * VQ_CD * VT + VQ_CD * VT + 2 * VG * VT + (size_t)d->D * VQ_CD) * 4;
-  FAC_REQUIRE(lds <= 160 * 1024, "vq_fwd: codebook of %d entries + %d in-proj rows do not fit LDS", d->Kc, d->D);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_fwd_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  FAC_REQUIRE(lds <= FAC_LDS_MAX, "vq_fwd: codebook of %d entries + %d in-proj rows do not fit LDS", d->Kc, d->D);
+  allow_dynamic_lds<vq_fwd_kernel>();
   if (d->T <= 8 && !d->loss_part && d->D <= 4096) {   // streaming hops: one workgroup per (b, t)
     const size_t lds_s = ((size_t)d->Kc * (VQ_CD + 1) + (size_t)d->D * (VQ_CD + 1) + 4 * VQ_CD + VQ_CD + 512) * 4;
-    if (lds_s <= 160 * 1024) {
-      static bool attr_s = false;
-      if (!attr_s) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_fwd_small_t_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_s = true;
-      }
+    if (lds_s <= FAC_LDS_MAX) {
+      allow_dynamic_lds<vq_fwd_small_t_kernel>();
       hipLaunchKernelGGL(vq_fwd_small_t_kernel, dim3(d->T, d->B), dim3(256), lds_s, (hipStream_t)stream, a);
       return check_launch("vq_fwd(small T)");
     }
@@ -468,8 +458,8 @@ extern "C" int fac_vq_fwd(const fac_vq_desc* d, fac_stream_t stream) {
   const int n_tiles = (d->T + VT - 1) / VT;
   const long long total = (long long)d->B * n_tiles;
   FAC_REQUIRE(total <= (1ll << 28), "vq_fwd: too many tiles");
-  const int per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL(vq_fwd_kernel, dim3(8 * per_xcd), dim3(256), lds, (hipStream_t)stream, a, n_tiles, per_xcd);
+  const XcdGrid xg = xcd_padded_grid(total);
+  hipLaunchKernelGGL(vq_fwd_kernel, dim3(xg.grid), dim3(256), lds, (hipStream_t)stream, a, n_tiles, xg.per_xcd);
   return check_launch("vq_fwd");
 }
 
@@ -478,13 +468,8 @@ extern "C" int fac_vq_search(const float* latents, const float* codebook, int64_
   using namespace fac;
   FAC_REQUIRE(latents && codebook && idx && N > 0 && Kc > 0, "vq_search: bad arguments");
   const size_t lds = ((size_t)Kc * (VQ_CD + 1) + 8 * VQ_TT) * 4;
-  FAC_REQUIRE(lds <= 160 * 1024, "vq_search: codebook of %d entries does not fit LDS", Kc);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_search_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  FAC_REQUIRE(lds <= FAC_LDS_MAX, "vq_search: codebook of %d entries does not fit LDS", Kc);
+  allow_dynamic_lds<vq_search_kernel>();
   long long tiles = (N + VQ_TT - 1) / VQ_TT;
   int grid = (int)(tiles < 2048 ? tiles : 2048);
   hipLaunchKernelGGL(vq_search_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, latents,

@@ -212,13 +212,8 @@ extern "C" int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream) {
   while ((1 << tt_log2) < VD_TT && (1 << tt_log2) < d->T) ++tt_log2;
   const int TT = 1 << tt_log2;
   const size_t lds = ((((size_t)d->D * (TT + 1) + 3) & ~(size_t)3) + (size_t)nqt * VD_TT * VD_CD + 2 * 4 * VD_TT + 2 * VD_TT) * 4;
-  FAC_REQUIRE(lds <= 160 * 1024, "vq_decode: %d channels x %d frames do not fit LDS", d->D, TT);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
+  FAC_REQUIRE(lds <= FAC_LDS_MAX, "vq_decode: %d channels x %d frames do not fit LDS", d->D, TT);
+  allow_dynamic_lds<vq_decode_kernel>();
   VqDecArgs a;
   for (int r = 0; r < 3; ++r) {
     a.codes[r] = reinterpret_cast<const long long*>(d->codes[r]);

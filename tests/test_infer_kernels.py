@@ -740,7 +740,8 @@ def test_dispatch_restatements_match_the_source():
     assert _snake_branch(1, 65536, 1024) == "flat" and _snake_branch(SNAKE_B, SNAKE_C, 1023) == "flat"
     assert "size_t lds = ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float);" in src
     assert "const size_t lds_v = lds + (size_t)16 * (T + 1) * sizeof(float);" in src
-    assert "const int stage_v = lds_v <= 160 * 1024 ? 1 : 0;" in src
+    assert "const int stage_v = lds_v <= FAC_LDS_MAX ? 1 : 0;" in src
+    assert "constexpr size_t FAC_LDS_MAX = 160 * 1024;" in open(os.path.join(REPO, "facodec_amd", "csrc", "common.h")).read()
     assert _attn_stages_v(256, 1151) and not _attn_stages_v(256, 1152)
     assert {c[3] for c in ATTN_CASES} == {True, False} and all(_attn_stages_v(c[0], c[1]) == c[3] for c in ATTN_CASES)
     assert "if (g > 8192) g = 8192;" in src and max(EW_N) > 8192 * 256

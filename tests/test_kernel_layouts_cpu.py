@@ -104,7 +104,7 @@ def test_a_workgroup_publishes_whole_cache_lines(H):
 
 # ----------------------------------------------------------------- bf16 x 3 resident forward (lstm_fwd_persist_split_kernel)
 def _split3(x):
-    """fp32 -> three round-to-nearest-even bf16 terms (as float32 arrays), the ls_split3 of the kernel."""
+    """fp32 -> three round-to-nearest-even bf16 terms (as float32 arrays), the split3 of the kernels (csrc/common.h)."""
     import torch
     t = torch.as_tensor(np.asarray(x, dtype=np.float32))
     hi = t.to(torch.bfloat16).float()
