@@ -32,6 +32,7 @@ class ConvDesc(C.Structure):
         ("K1", C.c_int32), ("dilation2", C.c_int32), ("row_phases", C.c_int32),
         ("x_p8", _p), ("x_p8_plane_bytes", _i64), ("y2_p8", _p), ("y2_p8_plane_bytes", _i64),
         ("pw_split", C.c_int32), ("split_rows", C.c_int32),
+        ("gate_cond", _p), ("gate_cond_bs", _i64),
     ]
 
 

@@ -16,7 +16,7 @@ enum ConvKernel : int {
   CK_FUSED_RU = 7,   // fused ResidualUnit (w_k1)
   CK_128x160 = 8,
   CK_NARROW = 9,     // VALU kernel for C_out <= 2 over many (batch, 1024-step) tiles
-  CK_SKINNY = 10,    // split reduction, <= 640 columns (its gemv sub-path included)
+  CK_SKINNY = 10,    // split reduction, <= 640 columns (its single-launch sub-path for <= 4 columns included: named apart)
   CK_BSPLIT = 11,    // split-bf16 kernel, K = 3 / 5 / 7
   CK_CIN1 = 12,      // store-stream kernel for C_in = 1
   CK_THIN = 13,      // channel-split VALU kernel for C_out <= 8 over few tiles
@@ -91,6 +91,10 @@ static int conv_plan(const fac_conv_desc* d, ConvArgs& a, ConvKernel& k) {
   a.y_tstride = d->y_tstride; a.act = d->act; a.w_batched = d->w_batched;
   a.phase_shift = d->phase_shift;
   a.rp = d->row_phases > 1 ? d->row_phases : 1;
+  FAC_REQUIRE(!d->gate_cond || (d->act == FAC_ACT_GATE && d->gate_cond_bs >= 0),
+              "conv1d: gate_cond is the conditioning row of the FAC_ACT_GATE epilogue (act=%d gate_cond_bs=%lld)", d->act,
+              (long long)d->gate_cond_bs);
+  a.gate_cond = d->gate_cond; a.gate_cond_bs = d->gate_cond_bs;
   if (a.rp > 1) {
     FAC_REQUIRE(d->n_phase == 1 && d->y_tstride == 1 && d->phase_shift == 0 && d->stride == 1 && a.rp <= 128 && !d->w_k1 &&
                     !d->w_batched && d->C_out_pad == fac_convtr_rows(d->C_out, a.rp) && !(d->K1 > 0 && d->K1 < d->K),
@@ -233,7 +237,10 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
     case CK_NARROW:
       snprintf(name, name_len, conv_two_level(a) ? "conv1d_narrow_kernel (VALU, C_out<=2, two-level taps)" : "conv1d_narrow_kernel (VALU, C_out<=2)");
       break;
-    case CK_SKINNY: snprintf(name, name_len, "conv1d_skinny_kernel (split reduction, <=640 columns)"); break;
+    case CK_SKINNY:
+      snprintf(name, name_len, conv_skinny_single_launch(a) ? "conv1d_gemv_kernel (single launch, <=4 columns)"
+                                                            : "conv1d_skinny_kernel (split reduction, <=640 columns)");
+      break;
     case CK_BSPLIT: snprintf(name, name_len, "conv1d_bsplit_kernel<%d> 64x256 (bf16x3 split, fp32-grade)", a.K); break;
     case CK_CIN1: snprintf(name, name_len, "conv1d_cin1_kernel (VALU, C_in=1, store stream)"); break;
     case CK_THIN: snprintf(name, name_len, "conv1d_thin_kernel (VALU, C_out<=8, split channels)"); break;

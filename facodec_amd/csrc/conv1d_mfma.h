@@ -70,6 +70,8 @@ struct ConvArgs {
   long long y2_p8_ps;
   int rp;      // > 1: output rows are (channel, phase) pairs, phase fastest, CO_TILE / rp channels per tile (all-phases
                // ConvTranspose1d, fac_conv_desc.row_phases); the all-waves epilogue interleaves them into contiguous runs
+  const float* gate_cond;      // FAC_ACT_GATE: per-clip conditioning row (2 * (C_out / 2) values) added before the gate, or NULL
+  long long gate_cond_bs;      // floats between the rows of two clips
 };
 
 // largest tap offset of a (possibly two-level) conv
@@ -716,6 +718,7 @@ int conv_dispatch_pws(ConvArgs& a, hipStream_t s);
 bool conv_pwt_ok(const ConvArgs& a);        // streaming kernel with taps: stride-2 ConvTranspose1d (all phases) / k = 4 stride-2 conv, few channels
 int conv_dispatch_pwt(ConvArgs& a, hipStream_t s);
 bool conv_skinny_ok(const ConvArgs& a, const void* ws, long long ws_bytes);
+bool conv_skinny_single_launch(const ConvArgs& a);   // a launch conv_skinny_ok takes runs on conv1d_gemv_kernel (one launch)
 int conv_dispatch_skinny(ConvArgs& a, void* ws, long long ws_bytes, hipStream_t s);
 
 }  // namespace fac

@@ -182,6 +182,8 @@ __global__ __launch_bounds__(256) void conv1d_skinny_reduce_kernel(ConvArgs a, S
 // FAC_ACT_GATE: channel co of the first half of the output channels and co + C_out / 2 live in two tiles; one thread adds the
 // S partial sums of both (slice order, as above) and writes tanh(a) * sigmoid(b) -- gate_kernel's arithmetic (misc.hip) on the
 // values the plain reduction would have written.  C_out / 2 is a multiple of the 128-row tile, S > 1.
+// gate_cond: the clip's conditioning row is added to both pre-activations AFTER the bias, (sum + bias) + g -- the fp32 sum, in
+// the order, of the plain reduction followed by gate_kernel with g.
 __global__ __launch_bounds__(256) void conv1d_skinny_reduce_gate_kernel(ConvArgs a, SkinnyGeom g, const float* __restrict__ part) {
   const int half_tiles = g.co_tiles >> 1;
   const int pair = blockIdx.x >> 2, quarter = blockIdx.x & 3;
@@ -216,7 +218,12 @@ __global__ __launch_bounds__(256) void conv1d_skinny_reduce_gate_kernel(ConvArgs
     const int c2 = cb * 32 + (ln & 31);
     if (co >= half || c2 >= ncol) continue;
     const int b2 = c2 / a.T_out, t2 = c2 - b2 * a.T_out;
-    const float ta = va[j] + (a.bias ? a.bias[co] : 0.f), sa = vb[j] + (a.bias ? a.bias[co + half] : 0.f);
+    float ta = va[j] + (a.bias ? a.bias[co] : 0.f), sa = vb[j] + (a.bias ? a.bias[co + half] : 0.f);
+    if (a.gate_cond) {
+      const float* gr = a.gate_cond + (long long)b2 * a.gate_cond_bs;
+      ta = __fadd_rn(ta, gr[co]);
+      sa = __fadd_rn(sa, gr[co + half]);
+    }
     a.y[(long long)b2 * a.y_bs + (long long)co * a.y_cs + t2] = __fmul_rn(tanhf(ta), sigmoid_f(sa));
   }
 }
@@ -317,7 +324,13 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvArgs a) {
   float v = tot[tid];
   if (gate) {
     if (i >= 4) return;
-    a.y[(long long)b2 * a.y_bs + (long long)co * a.y_cs + t2] = __fmul_rn(tanhf(v), sigmoid_f(tot[tid + 16]));
+    float sv = tot[tid + 16];
+    if (a.gate_cond) {                 // (sum + bias) + g, as gate_kernel adds g to the conv's stored output
+      const float* gr = a.gate_cond + (long long)b2 * a.gate_cond_bs;
+      v = __fadd_rn(v, gr[co]);
+      sv = __fadd_rn(sv, gr[co + half]);
+    }
+    a.y[(long long)b2 * a.y_bs + (long long)co * a.y_cs + t2] = __fmul_rn(tanhf(v), sigmoid_f(sv));
     return;
   }
   const long long o = (long long)b2 * a.y_bs + (long long)co * a.y_cs + (long long)t2 * a.y_tstride + phase;
@@ -352,6 +365,7 @@ static int gemv_co(const ConvArgs& a) {
   return row_bytes8 / 2 <= max_wg ? 4 : 0;
 }
 static bool gemv_ok(const ConvArgs& a) { return gemv_co(a) != 0; }
+bool conv_skinny_single_launch(const ConvArgs& a) { return gemv_ok(a); }
 
 // tuned with tools/tune/skinny_probe.py: workgroups aimed at, fewest (ci-pair, tap) rows per slice, rows in flight per wave
 constexpr int kSkinnyWgs = 512;

@@ -550,14 +550,16 @@ def p8_prepass(x, flop_per_in_byte):
 
 def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None, pad_mode=PAD_REFLECT,
            t_out=None, alpha_in=None, alpha_out=None, res=None, act=ACT_NONE, out=None, causal=True,
-           alpha_y2=None, want_y=True, w_k1=None, bias_k1=None, w_split=None, k1=0, dilation2=0, skip_acc=None):
+           alpha_y2=None, want_y=True, w_k1=None, bias_k1=None, w_split=None, k1=0, dilation2=0, skip_acc=None, gate_cond=None):
     """Fused conv (see fac_conv1d_fwd).  x (B, C_in, T).  With pad_left=None the SConv1d padding
     rule is applied (causal: everything on the left; non-causal: asymmetric split).
     k1 / dilation2: two-level taps (tap k = k2 * k1 + k1' reads offset k2 * dilation2 + k1' * dilation), see fac_conv_desc.
     alpha_y2: also produce y2 = snake(y, alpha_y2) (returned as (y, y2); y is None if not want_y).
     w_k1 / bias_k1: fused ResidualUnit tail -- y = w_k1 * snake(conv + bias, alpha_out) + bias_k1 + res.
     act=ACT_GATE / ACT_WN_RES_SKIP (streaming hops only, facodec_hip.h): the output has c_out / 2 channels; ACT_WN_RES_SKIP adds
-    the first half of the channels to `res` (-> out, which may be res itself) and the second half onto `skip_acc` in place."""
+    the first half of the channels to `res` (-> out, which may be res itself) and the second half onto `skip_acc` in place.
+    gate_cond (act=ACT_GATE only): (B, c_out) conditioning rows added to the pre-activations before the gate, as
+    gate_tanh_sigmoid(a, g) adds them (bit-identical to that pair of launches); may be a column slice of a wider (B, n) tensor."""
     x_p8 = x if isinstance(x, P8) else None
     if x_p8 is not None:
         B, c_in, t_in = x_p8.shape
@@ -609,6 +611,12 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
     d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = k, stride, dilation, pad_left, pad_mode
     d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = 1, 1, act, 0, 0
     d.K1, d.dilation2 = k1, dilation2
+    if gate_cond is not None:
+        if not (gate_cond.is_cuda and gate_cond.dtype == torch.float32 and gate_cond.dim() == 2 and gate_cond.shape == (B, c_out)
+                and (gate_cond.stride(1) == 1 or c_out == 1)):
+            raise ValueError(f"gate_cond must be a float32 GPU tensor (B={B}, c_out={c_out}) with contiguous rows, "
+                             f"got {tuple(gate_cond.shape)} {gate_cond.dtype} {gate_cond.device}")
+        d.gate_cond, d.gate_cond_bs = gate_cond.data_ptr(), gate_cond.stride(0)
     d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and (k == 1 or (PW_TAPS and k == 4 and stride == 2))) else 0
     _launch_conv(d, "fac_conv1d_fwd")
     return (out, y2) if alpha_y2 is not None else out
@@ -1045,11 +1053,12 @@ def gate_tanh_sigmoid(a, g=None):
     return out
 
 
-def embed_sum(codes, tables, code_row0=0, out=None):
-    """out (B, E, T) (+)= sum_i tables[i][codes[:, code_row0 + i]]; tables (n, V, E), codes (B, N, T) int64."""
+def embed_sum(codes, tables, code_row0=0, out=None, accumulate=None):
+    """out (B, E, T) (+)= sum_i tables[i][codes[:, code_row0 + i]]; tables (n, V, E), codes (B, N, T) int64.
+    A given `out` is added to unless accumulate=False (a static buffer that the launch overwrites)."""
     B, n_codes, T = codes.shape
     n_tab, V, E = tables.shape
-    acc = out is not None
+    acc = out is not None if accumulate is None else bool(accumulate) and out is not None
     if out is None:
         out = torch.empty(B, E, T, device=codes.device, dtype=torch.float32)
     _lib.check(_lib.load().fac_embed_sum(_ptr(codes.contiguous()), _ptr(_dev(tables)), _ptr(out), B, n_tab, n_codes,

@@ -247,6 +247,33 @@ class _DecoderStream:
         return _conv(mods[-2], self.tap_out, x_act, act=ops.ACT_TANH)
 
 
+def _wn_layers(wn, taps, h, n, cond=None):
+    """WN.forward (modules/wavenet.py:138-166) over one chunk of n frames: a left-context tap in front of every in_layer;
+    h (B, H, n) is consumed (the residual sums are written into it) -> the skip sum (B, H, n).  cond: the (B, 2 H L) output of
+    cond_layer, constant over time; layer i adds its column slice to the gate's pre-activations."""
+    out = torch.zeros_like(h)
+    H2 = 2 * wn.hidden_channels
+    fold = ops.STREAM_FOLD and h.shape[0] * n <= ops.SKINNY_MAX_COLS
+    for i in range(wn.n_layers):                       # WN.forward, modules/wavenet.py:138-166
+        last = i == wn.n_layers - 1
+        g = None if cond is None else cond[:, i * H2:(i + 1) * H2]
+        if not fold:
+            a = _conv(wn.in_layers[i], taps[i], h)
+            rs = wn.res_skip_layers[i].run(ops.gate_tanh_sigmoid(a, g))
+            ops.wn_res_skip_(rs, h, out, last=last)
+            continue
+        # the same arithmetic with the gate and the residual / skip adds as epilogues of the two convs' reduction kernels
+        acts = _conv(wn.in_layers[i], taps[i], h, act=ops.ACT_GATE, gate_cond=g)
+        rsl = wn.res_skip_layers[i]
+        w = rsl.w
+        if last:
+            ops.conv1d(acts, w.packed(), w.c_out, 1, bias=w.bias, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n, res=out, out=out)
+        else:
+            ops.conv1d(acts, w.packed(), w.c_out, 1, bias=w.bias, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n, res=h, out=h,
+                       skip_acc=out, act=ops.ACT_WN_RES_SKIP)
+    return out
+
+
 class _QuantizerStream:
     """FAquantizer.forward_v2 (modules/quantize.py:375-454), eval, per chunk of frames, with a fixed timbre."""
 
@@ -328,25 +355,7 @@ class _QuantizerStream:
         mel = self._mel(f0, n, final)
         h = ops.conv1d(mel[:, :20], q.melspec_linear.w.packed(), 256, 1, bias=q.melspec_linear.w.bias, pad_left=0,
                        pad_mode=ops.PAD_ZERO, t_out=n)
-        wn = q.melspec_encoder
-        out = torch.zeros_like(h)
-        fold = ops.STREAM_FOLD and h.shape[0] * n <= ops.SKINNY_MAX_COLS
-        for i in range(wn.n_layers):                       # WN.forward, modules/wavenet.py:138-166
-            last = i == wn.n_layers - 1
-            if not fold:
-                a = _conv(wn.in_layers[i], self.wn_taps[i], h)
-                rs = wn.res_skip_layers[i].run(ops.gate_tanh_sigmoid(a))
-                ops.wn_res_skip_(rs, h, out, last=last)
-                continue
-            # the same arithmetic with the gate and the residual / skip adds as epilogues of the two convs' reduction kernels
-            acts = _conv(wn.in_layers[i], self.wn_taps[i], h, act=ops.ACT_GATE)
-            rsl = wn.res_skip_layers[i]
-            w = rsl.w
-            if last:
-                ops.conv1d(acts, w.packed(), w.c_out, 1, bias=w.bias, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n, res=out, out=out)
-            else:
-                ops.conv1d(acts, w.packed(), w.c_out, 1, bias=w.bias, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n, res=h, out=h,
-                           skip_acc=out, act=ops.ACT_WN_RES_SKIP)
+        out = _wn_layers(q.melspec_encoder, self.wn_taps, h, n)
         f0_feat = q.melspec_linear2.run(out)
         z_p, codes_p = self._rvq(q.prosody_quantizer, f0_feat, 1)
         return n, z_p, codes_p
@@ -377,33 +386,17 @@ class _QuantizerStream:
         return self.rest(x, pros, self.content(n_c, x))
 
 
-class StreamingCodec:
-    """One streaming session over B parallel streams.
+class _HopSession:
+    """What the sessions that take 480-sample hops share: prime / push / finish, the two-stream split of a steady-state hop
+    and the five-phase graph capture.  A subclass builds its chains in __init__ (after _init_hops, before which no stream object
+    may register its counters) and supplies `_back_half`."""
 
-        sess = StreamingCodec(model, timbre)            # model = build_model(...) (causal), timbre (B, 1024)
-        out = sess.prime(wave[:, :, :4800])             # first chunk, >= 4 800 samples, multiple of 2 400
-        out = sess.push(wave[:, :, t:t + 480])          # every hop: dict(codes=[p, c, r], wave=(B, 1, 300 n))
-        out = sess.finish()                             # frames that were waiting for look-ahead
-
-    Each call returns the frames completed by it (`frames` = index of the first one).  With graphs enabled the
-    returned tensors are static buffers, valid until the next call.
-    """
-
-    def __init__(self, model, timbre, n_c=2, prime_samples=4800, use_graphs=True):
-        enc, q, dec = model.encoder, model.quantizer, model.decoder
+    def _init_hops(self, device, B, prime_samples, use_graphs):
         if prime_samples % PERIOD or prime_samples < 2 * PERIOD:
             raise ValueError(f"prime_samples must be a multiple of {PERIOD} and at least {2 * PERIOD}")
-        self.device = timbre.device
-        self.B, self.n_c, self.prime_samples = timbre.shape[0], n_c, prime_samples
+        self.device = device
+        self.B, self.prime_samples = B, prime_samples
         self._counters = []
-        for m in list(enc.modules()) + list(q.modules()) + list(dec.modules()):
-            if isinstance(m, ConvWeights):
-                m.freeze_packed = True               # inference: materialise w = g v/||v|| once
-        B = self.B
-        max_frames = prime_samples // FRAME
-        self.enc = _EncoderStream(self, enc, B, prime_samples)
-        self.qs = _QuantizerStream(self, q, B, timbre, max_frames, prime_samples)
-        self.dec = _DecoderStream(self, dec, B, max_frames)
         self.n_samples = 0
         self.hops = 0
         self.use_graphs = use_graphs
@@ -413,6 +406,11 @@ class StreamingCodec:
         self._graphs = {}
         self._snap = {}
         self._hop_in = torch.zeros(B, 1, HOP, device=self.device)
+
+    def _back_half(self, final, x=None):
+        """Everything behind the latent FIFO for the frames whose look-ahead is complete -> (codes, wave) or None when no frame
+        is due.  x: their latents if `take_latents` already copied them out."""
+        raise NotImplementedError
 
     # ------------------------------------------------------------------------------------------ steps
     def _step(self, wave_new, final=False):
@@ -426,8 +424,7 @@ class StreamingCodec:
                 main = torch.cuda.current_stream(self.device)
                 self._side.wait_stream(main)
                 with torch.cuda.stream(self._side):
-                    outs, codes = self.qs.run(self.n_c, final, x=x)
-                    wave = self.dec.run(outs)
+                    codes, wave = self._back_half(final, x=x)
                 self.qs.push(None, self.enc.run(wave_new))
                 # join: everything later on the caller's stream (reading the outputs, the next hop's fork) is ordered behind both
                 main.wait_stream(self._side)
@@ -436,11 +433,10 @@ class StreamingCodec:
         elif wave_new is not None:
             z = self.enc.run(wave_new)
             self.qs.push(wave_new, z)
-        r = self.qs.run(self.n_c, final)
+        r = self._back_half(final)
         if r is None:
             return dict(frame0=first, codes=None, wave=None)
-        outs, codes = r
-        return dict(frame0=first, codes=codes, wave=self.dec.run(outs))
+        return dict(frame0=first, codes=r[0], wave=r[1])
 
     def prime(self, wave):
         if self.n_samples:
@@ -492,6 +488,190 @@ class StreamingCodec:
         if self.n_samples % FRAME:
             raise ValueError("finish(): stream length must be a multiple of 300 samples")
         return self._step(None, final=True)
+
+
+class StreamingCodec(_HopSession):
+    """One streaming session over B parallel streams.
+
+        sess = StreamingCodec(model, timbre)            # model = build_model(...) (causal), timbre (B, 1024)
+        out = sess.prime(wave[:, :, :4800])             # first chunk, >= 4 800 samples, multiple of 2 400
+        out = sess.push(wave[:, :, t:t + 480])          # every hop: dict(codes=[p, c, r], wave=(B, 1, 300 n))
+        out = sess.finish()                             # frames that were waiting for look-ahead
+
+    Each call returns the frames completed by it (`frames` = index of the first one).  With graphs enabled the
+    returned tensors are static buffers, valid until the next call.
+    """
+
+    def __init__(self, model, timbre, n_c=2, prime_samples=4800, use_graphs=True):
+        enc, q, dec = model.encoder, model.quantizer, model.decoder
+        self._init_hops(timbre.device, timbre.shape[0], prime_samples, use_graphs)
+        self.n_c = n_c
+        for m in list(enc.modules()) + list(q.modules()) + list(dec.modules()):
+            if isinstance(m, ConvWeights):
+                m.freeze_packed = True               # inference: materialise w = g v/||v|| once
+        B = self.B
+        max_frames = prime_samples // FRAME
+        self.enc = _EncoderStream(self, enc, B, prime_samples)
+        self.qs = _QuantizerStream(self, q, B, timbre, max_frames, prime_samples)
+        self.dec = _DecoderStream(self, dec, B, max_frames)
+
+    def _back_half(self, final, x=None):
+        r = self.qs.run(self.n_c, final, x=x)
+        if r is None:
+            return None
+        outs, codes = r
+        return codes, self.dec.run(outs)
+
+
+def _first_non_causal(model, keys, prefix):
+    """Name of the first conv under model[key], in execution order, that looks to the right of its output column, or None.
+    (A k = 1 conv pads nothing, whatever its `causal` flag says: the WaveNet's cond_layer.)"""
+    from .layers import SConv1d, SConvTranspose1d
+    for key in keys:
+        for name, m in model[key].named_modules():
+            if isinstance(m, SConvTranspose1d) and not m.causal:
+                return f"{prefix}.{key}.{name}"
+            if isinstance(m, SConv1d) and not m.causal and (m.kernel_size - 1) * m.dilation + 1 - m.stride > 0:
+                return f"{prefix}.{key}.{name}"
+    return None
+
+
+def _check_timbre(timbre, B, dim, what):
+    if not isinstance(timbre, torch.Tensor) or timbre.dim() != 2 or timbre.shape[1] != dim or (B is not None and timbre.shape[0] != B):
+        got = tuple(timbre.shape) if isinstance(timbre, torch.Tensor) else type(timbre).__name__
+        raise ValueError(f"{what} must be a float32 GPU tensor ({'B' if B is None else B}, {dim}), got {got}")
+    if timbre.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {timbre.dtype}")
+    if not timbre.is_cuda:
+        raise ValueError(f"{what} must live on the GPU, got {timbre.device}; there is no CPU path")
+
+
+class _RedecoderStream:
+    """Redecoder.forward (modules/redecoder.py:35-48), eval, per chunk of frames: code embeddings summed into a static buffer ->
+    16-layer causal WaveNet with a left-context tap per layer, conditioned on a target timbre through `cond` -> 1x1 conv.
+    cond = cond_layer(timbre) is constant over time: computed once per target (set_target) into a static (B, 2 H L) buffer whose
+    column slices the gate epilogues read, so nothing is broadcast per hop and captured graphs survive a change of target."""
+
+    def __init__(self, sess, r, B, timbre, use_p_code, n_c, max_frames):
+        self.r = r
+        wn = r.encoder
+        E = r.embed_dim
+        dev = sess.device
+        # the tables in use, stacked once per session (Redecoder.forward stacks them on every call)
+        self.p_tabs = torch.stack([e.weight.detach() for e in r.prosody_embed]) if use_p_code and r.n_p_codebooks else None
+        self.c_tabs = torch.stack([e.weight.detach() for e in list(r.content_embed)[:n_c]])
+        self.x = torch.zeros(B * E * max_frames, device=dev)                 # (B, E, n) of the chunk, n <= max_frames
+        self.max_frames = max_frames
+        self.taps = [_Tap(sess, B, E, m.kernel_size, 1, m.dilation, max_frames) for m in wn.in_layers]
+        self.cond = torch.zeros(B, 2 * wn.hidden_channels * wn.n_layers, device=dev)
+        self.w_out = ops.pack_conv_weight(r.conv_out.weight.detach())
+        self.b_out = r.conv_out.bias.detach()
+        self.set_target(timbre)
+
+    def set_target(self, timbre):
+        B = timbre.shape[0]
+        self.cond.copy_(self.r.encoder.cond_layer.run(timbre.contiguous().reshape(B, -1, 1)).reshape(B, -1))
+
+    def run(self, codes_p, codes_c, n):
+        r = self.r
+        B, E = codes_c.shape[0], r.embed_dim
+        if n > self.max_frames:
+            raise RuntimeError(f"a chunk of {n} frames exceeds the session's {self.max_frames}")
+        x = self.x[:B * E * n].view(B, E, n)
+        first = True
+        for codes, tabs in ((codes_p, self.p_tabs), (codes_c, self.c_tabs)):
+            if tabs is not None:
+                ops.embed_sum(codes, tabs, 0, out=x, accumulate=not first)
+                first = False
+        out = _wn_layers(r.encoder, self.taps, x, n, cond=self.cond)
+        return ops.conv1d(out, self.w_out, r.conv_out.c_out, 1, bias=self.b_out, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=n)
+
+
+class StreamingConverter(_HopSession):
+    """Real-time voice conversion over B parallel streams: source audio in 480-sample hops in, the same speech in the target
+    voice out (reconstruct_redecoder.py:95-122, one hop at a time).
+
+        vc  = StreamingConverter(codec, redecoder, target_timbre)     # codec = build_model(...) (causal stage 'codec'),
+                                                                      # redecoder = build_model(..., stage='redecoder') with
+                                                                      # decoder_causal=True; target_timbre (B, 1024) fp32, GPU
+        out = vc.prime(wave[:, :, :4800])              # dict(frame0, codes=[p, c], wave=(B, 1, 300 n) | None)
+        out = vc.push(wave[:, :, t:t + 480])
+        out = vc.finish()
+        vc.set_target(timbre)                          # switch the target voice between hops
+
+    A hop runs the codec's encoder, the prosody branch and the content RVQ with n_c quantizers on the source (no residual RVQ, no
+    timbre LayerNorm, no codec decoder), then the redecoder -- code embeddings, the timbre-conditioned causal WaveNet, conv_out --
+    and the redecoder's decoder.  The prosody branch runs even with use_p_code=False: codes[0] is emitted either way, as the
+    reference derives the prosody codes from the waveform regardless of what the redecoder consumes.  Codes equal the offline
+    quantizer's, the concatenated waveform equals `redecoder.encoder(codes ...) -> redecoder.decoder` on the whole signal within
+    fp32 noise.  The defaults use_p_code=False, n_c=1 are the call of reconstruct_redecoder.py:121.
+
+    target_timbre comes from the offline quantizer on an enrolment clip of the target speaker.  source_timbre is accepted for
+    symmetry with StreamingCodec and checked, but no step of the conversion hop reads the source's timbre.
+
+    prime / push / finish, the two-stream split and the graph capture are StreamingCodec's (_HopSession); with graphs enabled the
+    returned tensors are static buffers, valid until the next call.
+    """
+
+    def __init__(self, codec, redecoder, target_timbre, source_timbre=None, use_p_code=False, n_c=1, prime_samples=4800,
+                 use_graphs=True):
+        enc, q = codec.encoder, codec.quantizer
+        red, dec = redecoder.encoder, redecoder.decoder
+        # ---- everything that can be refused is refused here, on the host, before any launch
+        if getattr(red, "encoder_type", None) != "wavenet":
+            raise NotImplementedError(f"redecoder encoder_type {getattr(red, 'encoder_type', None)!r}: only 'wavenet' streams")
+        bad = _first_non_causal(redecoder, ("encoder", "decoder"), "redecoder")
+        if bad is not None:
+            raise NotImplementedError(f"{bad} is not causal: a streaming conversion needs the redecoder built with "
+                                      "decoder_causal=True (a hop cannot wait for frames to the right of it)")
+        n_c = int(n_c)
+        if n_c < 1 or n_c > red.n_c_codebooks or n_c > q.content_quantizer.n_codebooks:
+            raise ValueError(f"n_c = {n_c}: the redecoder has {red.n_c_codebooks} content tables, the codec's content RVQ "
+                             f"{q.content_quantizer.n_codebooks} quantizers (1 .. the smaller of the two)")
+        _check_timbre(target_timbre, None, q.in_dim, "target_timbre")
+        B = target_timbre.shape[0]
+        if source_timbre is not None:
+            _check_timbre(source_timbre, B, q.in_dim, "source_timbre")
+        self._init_hops(target_timbre.device, B, prime_samples, use_graphs)
+        self.n_c, self.use_p_code = n_c, bool(use_p_code)
+        self._dim = q.in_dim
+        for m in list(enc.modules()) + list(q.modules()) + list(red.modules()) + list(dec.modules()):
+            if isinstance(m, ConvWeights):
+                m.freeze_packed = True               # inference: materialise w = g v/||v|| once
+        max_frames = prime_samples // FRAME
+        with torch.no_grad():
+            self.enc = _EncoderStream(self, enc, B, prime_samples)
+            style_src = source_timbre if source_timbre is not None else torch.zeros_like(target_timbre)
+            self.qs = _QuantizerStream(self, q, B, style_src, max_frames, prime_samples)
+            self.red = _RedecoderStream(self, red, B, target_timbre, self.use_p_code, n_c, max_frames)
+            self.dec = _DecoderStream(self, dec, B, max_frames)
+
+    def set_target(self, timbre):
+        """Switches the target voice: recomputes cond = cond_layer(timbre) into the static buffer the gate epilogues read, so
+        captured graphs stay valid and the next hop already speaks with the new voice.  Call it between hops, on the stream the
+        hops are pushed on.  The left contexts (WaveNet taps, decoder taps, LSTM state) are not reset: they keep what the previous
+        voice wrote, so the first frames after a switch see up to a receptive field of the old voice's activations."""
+        _check_timbre(timbre, self.B, self._dim, "timbre")
+        with torch.no_grad():
+            self.red.set_target(timbre)
+
+    def _back_half(self, final, x=None):
+        qs = self.qs
+        f0 = qs.c[0]
+        pros = qs.prosody(final)
+        if pros is None:
+            return None
+        n, _, codes_p = pros
+        if x is None:
+            x = qs.z_fifo.window(f0, n).contiguous()
+        _, codes_c = qs.content(self.n_c, x)             # z_p is no input of the content RVQ (modules/quantize.py:415-420)
+        qs.c[0] += n
+        z = self.red.run(codes_p, codes_c, n)
+        return [codes_p, codes_c], self.dec.run(z)
+
+    def _step(self, wave_new, final=False):
+        with torch.no_grad():
+            return super()._step(wave_new, final)
 
 
 class StreamingDecoder:

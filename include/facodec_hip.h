@@ -42,7 +42,8 @@ typedef void* fac_stream_t; /* hipStream_t */
  * the streaming hop (B * T_out <= 640; fac_conv1d_fwd fails for any other shape -- there the elementwise kernels
  * fac_gate_tanh_sigmoid / fac_wn_res_skip do the same arithmetic):
  *   FAC_ACT_GATE        : y (B, C_out / 2, T) = tanh(c[:, :C_out/2]) * sigmoid(c[:, C_out/2:]) of c = conv + bias
- *                         (fused_add_tanh_sigmoid_multiply without conditioning, modules/commons.py:113-120); C_out % 256 == 0.
+ *                         (fused_add_tanh_sigmoid_multiply, modules/commons.py:113-120; its conditioning input is
+ *                         fac_conv_desc.gate_cond); C_out % 256 == 0.
  *   FAC_ACT_WN_RES_SKIP : c = conv + bias; y (B, C_out / 2, T) = res + c[:, :C_out/2] (res may be y itself) and
  *                         y2 (B, C_out / 2, T) += c[:, C_out/2:] (no alpha_y2; y2 is the running skip sum). */
 #define FAC_ACT_GATE 4
@@ -184,6 +185,12 @@ typedef struct fac_conv_desc {
    * (fac_pack_conv_w_split_rows).  96 selects the 96-row form of the split kernel (conv1d_bsplit96.hip: C_out % 96 == 0, C_in % 8 ==
    * 0); such weights fit no other kernel, so a launch outside its shapes is an error. */
   int32_t split_rows;
+  /* Optional, FAC_ACT_GATE only (any other act with it is an error): per-clip conditioning rows of the gate, clip b's 2 * (C_out / 2)
+   * values at gate_cond + b * gate_cond_bs (a row slice of a wider (B, n) tensor is fine), added to the pre-activations after the
+   * bias: y = tanh((c + g)[:C_out/2]) * sigmoid((c + g)[C_out/2:]), the same fp32 sums in the same order as fac_conv1d_fwd
+   * followed by fac_gate_tanh_sigmoid with g (WN with gin_channels, modules/wavenet.py:146-155).  NULL: no conditioning. */
+  const float* gate_cond;
+  int64_t gate_cond_bs;
 } fac_conv_desc;
 
 int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream);
