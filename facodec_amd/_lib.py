@@ -57,6 +57,16 @@ class VqDecodeDesc(C.Structure):
         ("B", C.c_int32), ("D", C.c_int32), ("T", C.c_int32), ("Kc", C.c_int32),
     ]
 
+
+class ResampleDesc(C.Structure):
+    _fields_ = [
+        ("hist", _p), ("x", _p), ("lens", _p), ("y", _p), ("hist_out", _p), ("table", _p), ("offs", _p),
+        ("hist_bs", _i64), ("x_bs", _i64), ("y_bs", _i64), ("q0", _i64), ("m_lo", _i64),
+        ("B", C.c_int32), ("n_hist", C.c_int32), ("T", C.c_int32), ("n_out", C.c_int32),
+        ("o", C.c_int32), ("n", C.c_int32), ("taps", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/facodec_hip.h declares
 SIGNATURES = {
     "fac_version": (_i, []),
@@ -189,6 +199,8 @@ SIGNATURES = {
     "fac_mask_tail": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_mask_tail_i64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_frame_mask": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "fac_resample": (_i, [C.POINTER(ResampleDesc), _p]),
+    "fac_resample_form": (_i, [C.POINTER(ResampleDesc), _p]),
     "fac_spec_power": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_reduce_pair": (_i, [_p, _p, _p, _p, _i64, _i, _f, _f, _i, _p]),
     "fac_aa_snakebeta_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

@@ -189,9 +189,16 @@ def _need_gpu(tensors, what):
             raise FacodecHipError(f"{what} must live on the GPU (got {t.device}); there is no CPU path")
 
 
-def _clip_lengths(model, tensors, what, per_item=1):
+MODEL_RATE = 24000   # the codec's sample rate (DAC.sr); the clip-list calls resample from / to any other (ops.resample)
+
+
+def _clip_lengths(model, tensors, what, per_item=1, ratio=None):
+    """Lengths in samples at the model's rate, checked against min_clip_samples; ratio (o, n): the clips are at another rate and
+    are resampled by n / o first, so what counts is ceil(T n / o)."""
     _need_gpu(tensors, what)
     lengths = [int(t.shape[-1]) * per_item for t in tensors]
+    if ratio is not None:
+        lengths = [-(-n * ratio[1] // ratio[0]) for n in lengths]
     need = min_clip_samples(model)
     hop = model.quantizer.hop_length
     for i, n in enumerate(lengths):
@@ -202,7 +209,7 @@ def _clip_lengths(model, tensors, what, per_item=1):
 
 
 @torch.no_grad()
-def encode_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
+def encode_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES, sample_rate=MODEL_RATE, quality="best"):
     """Clips of different lengths -> codes and timbre per clip, in the caller's order:
 
         clips = encode_clips(model, [wave_0 (T_0,), wave_1 (1, T_1), ...])         # GPU tensors, float32, 24 kHz
@@ -211,20 +218,31 @@ def encode_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
     every entry what the single-clip calls `model.encoder(w)`, `model.quantizer(z, w, n_c, return_codes=True)` give on that clip
     alone.  The clips are sorted by length and grouped into zero-padded batches under a sample budget (plan_groups); each group
     is one encoder pass and one FAquantizer.forward_ragged.  The reference's `collate` output (zero-padded `waves` (B, T) and
-    `wave_lens`) maps onto it as `[waves[b, :wave_lens[b]] for b in range(B)]`."""
+    `wave_lens`) maps onto it as `[waves[b, :wave_lens[b]] for b in range(B)]`.
+
+    sample_rate: the clips' rate.  Other than 24000, every group is resampled to 24 kHz as one padded batch with its lengths in
+    one ops.resample launch (`quality`), which gives every clip what ops.resample gives it alone; groups are planned and
+    the shortest-clip check is made on the lengths AFTER resampling, ceil(T_i 24000 / sample_rate)."""
+    from . import ops
+    ratio = None
+    if sample_rate != MODEL_RATE:
+        geo = ops.resample_table(sample_rate, MODEL_RATE, quality)
+        ratio = (geo["o"], geo["n"])
     waves = list(waves)
     if not waves:
         return []
     for w in waves:
         if isinstance(w, torch.Tensor) and not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
             raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
-    lengths = _clip_lengths(model, waves, "clips")
-    from . import ops
+    lengths = _clip_lengths(model, waves, "clips", ratio=ratio)
     dev, hop = waves[0].device, model.quantizer.hop_length
     out = [None] * len(waves)
     for group in plan_groups(lengths, max_batch_samples):
         batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True).unsqueeze(1)
         lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), dev)
+        if ratio is not None:
+            lens_in = ops.h2d(torch.tensor([waves[i].shape[-1] for i in group], dtype=torch.int32), dev)
+            batch = ops.resample(batch, sample_rate, MODEL_RATE, lens=lens_in, quality=quality)
         z = model.encoder(batch)
         _, codes, timbre, _ = model.quantizer.forward_ragged(z, batch, lens, n_c=n_c)
         for j, i in enumerate(group):
@@ -233,12 +251,20 @@ def encode_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
 
 
 @torch.no_grad()
-def decode_clips(model, codes_list, timbres, max_batch_samples=MAX_BATCH_SAMPLES):
+def decode_clips(model, codes_list, timbres, max_batch_samples=MAX_BATCH_SAMPLES, sample_rate=MODEL_RATE, quality="best"):
     """Codes of clips of different lengths -> list of waves (1, 300 F_i), in the caller's order.  codes_list[i] =
     [p (n_p, F_i), c (n_c, F_i), r (n_r, F_i)] int64 as encode_clips returns them (the same row counts for every clip);
     timbres[i] (1024,): the clip's own or another clip's / speaker's (timbre swap, as in decode_codes).  Per group of
     plan_groups the codes are padded with code 0 and decoded by one fac_vq_decode launch and one decoder pass (causal: the
-    padding cannot reach back into a clip); every wave is cropped to its clip."""
+    padding cannot reach back into a clip); every wave is cropped to its clip.
+
+    sample_rate other than 24000: every group's waves are resampled to it in one ops.resample launch with the clips' lengths,
+    and clip i comes back with ceil(300 F_i sample_rate / 24000) samples, what ops.resample gives its 24 kHz wave alone."""
+    from . import ops
+    ratio = None
+    if sample_rate != MODEL_RATE:
+        geo = ops.resample_table(MODEL_RATE, sample_rate, quality)
+        ratio = (geo["o"], geo["n"])
     codes_list = [list(c) for c in codes_list]
     if not codes_list:
         return []
@@ -259,16 +285,21 @@ def decode_clips(model, codes_list, timbres, max_batch_samples=MAX_BATCH_SAMPLES
                  for s in range(3)]
         timbre = torch.stack([timbres[i].reshape(-1) for i in group])
         wave = decode_codes(model, codes, timbre)
+        if ratio is not None:
+            lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), wave.device)
+            wave = ops.resample(wave, MODEL_RATE, sample_rate, lens=lens, quality=quality)
         for j, i in enumerate(group):
-            out[i] = wave[j, :, :lengths[i]]
+            out[i] = wave[j, :, :lengths[i] if ratio is None else -(-lengths[i] * ratio[1] // ratio[0])]
     return out
 
 
 @torch.no_grad()
-def reconstruct_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES):
-    """encode_clips then decode_clips with every clip's own timbre: list of waves (1, 300 (T_i // 300))."""
-    clips = encode_clips(model, waves, n_c=n_c, max_batch_samples=max_batch_samples)
-    return decode_clips(model, [c["codes"] for c in clips], [c["timbre"] for c in clips], max_batch_samples=max_batch_samples)
+def reconstruct_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES, sample_rate=MODEL_RATE, quality="best"):
+    """encode_clips then decode_clips with every clip's own timbre: list of waves (1, 300 (T_i // 300)) -- at sample_rate,
+    which is the rate of the clips going in and of the waves coming out."""
+    clips = encode_clips(model, waves, n_c=n_c, max_batch_samples=max_batch_samples, sample_rate=sample_rate, quality=quality)
+    return decode_clips(model, [c["codes"] for c in clips], [c["timbre"] for c in clips], max_batch_samples=max_batch_samples,
+                        sample_rate=sample_rate, quality=quality)
 
 
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):

@@ -112,3 +112,70 @@ def kaiser_sinc_filter1d(cutoff, half_width, kernel_size):
     filt = 2 * cutoff * window * torch.sinc(2 * cutoff * time)
     filt = filt / filt.sum()
     return filt.view(1, 1, kernel_size)
+
+
+# ------------------------------------------------------------------------------------ sample-rate conversion
+# quality -> (W = half width in zero crossings, rolloff, Kaiser beta).  "best" is the kaiser_best parameter set of resampy /
+# torchaudio.functional.resample (lowpass_filter_width 64), "fast" a quarter of the width with an earlier roll-off.
+RESAMPLE_QUALITIES = {
+    "best": (64, 0.9475937167399596, 14.769656459379492),
+    "fast": (16, 0.85, 8.555504641634386),
+}
+RESAMPLE_MAX_RATIO = 640          # largest o = rate_in / gcd and n = rate_out / gcd the kernel is launched with
+
+_RESAMPLE_TABLES = {}
+
+
+def resample_ratio(rate_in, rate_out):
+    """-> (o, n) = (rate_in, rate_out) / gcd; ValueError for rates that are no positive integers or reduce to more than 640."""
+    for r in (rate_in, rate_out):
+        if isinstance(r, bool) or int(r) != r or r <= 0:
+            raise ValueError(f"sample rates must be positive integers, got {rate_in!r} -> {rate_out!r}")
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    g = math.gcd(rate_in, rate_out)
+    o, n = rate_in // g, rate_out // g
+    if o > RESAMPLE_MAX_RATIO or n > RESAMPLE_MAX_RATIO:
+        raise ValueError(f"{rate_in} -> {rate_out} Hz reduces to {o} : {n}; both sides of the ratio must be at most {RESAMPLE_MAX_RATIO}")
+    return o, n
+
+
+def resample_table(rate_in, rate_out, quality="best"):
+    """Coefficients of the polyphase windowed-sinc resampler, built in float64 and rounded ONCE to float32.
+
+    With o, n = rate_in, rate_out over their gcd, base = min(o, n) * rolloff and
+        win(t) = I0(beta sqrt(1 - (t / W)^2)) / I0(beta)  for |t| < W, else 0;     h(t) = sinc(t) win(t) base / o,
+    output m of a signal x is  y[m] = sum_q h((q / o - m / n) base) x[q]  over the q with |(q / o - m / n) base| < W.  h depends on m
+    through p = m mod n only: with m = k n + p and q = k o + d the argument is (d n - p o) base / (o n), evaluated here from that
+    integer numerator.  Row p of the table holds h for d = offs[p], offs[p] + 1, ..., offs[p] being the first d inside the window;
+    rows with fewer taps than the longest end in zeros.
+
+    -> dict(o, n, taps, W, rolloff, beta, base, half = ceil(W o / base) input samples reached on either side,
+            offs (n,) int32, table64 (n, taps) float64, table (n, taps) float32); cached, treat the arrays as read-only."""
+    if quality not in RESAMPLE_QUALITIES:
+        raise ValueError(f"unknown resampling quality {quality!r}: one of {sorted(RESAMPLE_QUALITIES)}")
+    o, n = resample_ratio(rate_in, rate_out)
+    key = (o, n, quality)
+    if key in _RESAMPLE_TABLES:
+        return _RESAMPLE_TABLES[key]
+    W, rolloff, beta = RESAMPLE_QUALITIES[quality]
+    base = min(o, n) * rolloff
+    U = W * o * n / base                                        # |d n - p o| < U  <=>  |t| < W
+    p = np.arange(n, dtype=np.int64)[:, None]
+
+    def h_of(d):
+        t = (d * n - p * o).astype(np.float64) / (o * n) * base
+        inside = np.abs(t) < W
+        win = np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (t / W) ** 2))) / np.i0(beta)
+        return np.where(inside, np.sinc(t) * win * (base / o), 0.0), inside
+
+    first = np.floor((p * o - U) / n).astype(np.int64) - 1       # one or two candidates before the window on either side
+    cand = first + np.arange(int(2 * U / n) + 6, dtype=np.int64)[None, :]
+    _, inside = h_of(cand)
+    offs = cand[np.arange(n), np.argmax(inside, axis=1)]
+    taps = int(inside.sum(axis=1).max())
+    table64, _ = h_of(offs[:, None] + np.arange(taps, dtype=np.int64)[None, :])
+    out = dict(o=o, n=n, taps=taps, W=W, rolloff=rolloff, beta=beta, base=base, half=int(math.ceil(W * o / base)),
+               offs=offs.astype(np.int32), table64=table64, table=table64.astype(np.float32))
+    _RESAMPLE_TABLES[key] = out
+    return out
+

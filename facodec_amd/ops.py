@@ -12,7 +12,7 @@ from . import _lib
 from .wprep import prepared
 # the layout / launch-form policy, its predicates and the layout names live in convplan.py; re-exported for call sites, tests and tools
 from .convplan import *  # noqa: F401,F403
-from ._lib import ConvDesc, VqDesc, VqDecodeDesc, PAD_REFLECT, PAD_ZERO, ACT_NONE, ACT_TANH, ACT_MISH, ACT_LOG_MEL, ACT_GATE, ACT_WN_RES_SKIP  # noqa: F401
+from ._lib import ConvDesc, VqDesc, VqDecodeDesc, ResampleDesc, PAD_REFLECT, PAD_ZERO, ACT_NONE, ACT_TANH, ACT_MISH, ACT_LOG_MEL, ACT_GATE, ACT_WN_RES_SKIP  # noqa: F401
 
 
 def pad32(n):
@@ -1207,6 +1207,75 @@ def frame_mask(lens, n_frames, unit):
     n_valid = torch.empty(B, device=lens.device, dtype=torch.int32)
     _lib.check(_lib.load().fac_frame_mask(_ptr(lens), _ptr(mask), _ptr(n_valid), B, n_frames, unit, _stream()), "fac_frame_mask")
     return mask, n_valid
+
+
+# --------------------------------------------------------------------------------- sample-rate conversion
+_RESAMPLE_DEV = {}
+
+
+def resample_table(rate_in, rate_out, quality="best"):
+    """The resampler's coefficients and geometry on the host (dsp.resample_table): dict(o, n, taps, offs (n,) int32 first-tap
+    offsets, table (n, taps) float32 = table64 rounded once, half, W, rolloff, beta, base).  ValueError for an unknown quality,
+    rates that are no positive integers, or a ratio with a side above 640."""
+    from . import dsp
+    return dsp.resample_table(rate_in, rate_out, quality)
+
+
+def _resample_device_table(rate_in, rate_out, quality, device):
+    """-> (geometry dict, table, offs) on `device`, uploaded once per (rate_in, rate_out, quality, device)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(rate_in), int(rate_out), quality, device)
+    hit = _RESAMPLE_DEV.get(key)
+    if hit is None:
+        geo = resample_table(rate_in, rate_out, quality)
+        hit = _RESAMPLE_DEV[key] = (geo, h2d(torch.from_numpy(geo["table"]), device), h2d(torch.from_numpy(geo["offs"]), device))
+    return hit
+
+
+def resample_desc(geo, table, offs, x, y, n_out, lens=None, hist=None, hist_out=None, q0=0, m_lo=0, T=None):
+    """fac_resample_desc for x (B, T) -> y (B, >= n_out) rows (last dimension dense); hist / hist_out (B, n_hist) or None.
+    T: how many columns of x are the block, where that is not all of them (T = 0: the end of a stream, any x)."""
+    d = _lib.ResampleDesc()
+    d.hist, d.x, d.lens, d.y, d.hist_out, d.table, d.offs = (t.data_ptr() if t is not None else None
+                                                             for t in (hist, x, lens, y, hist_out, table, offs))
+    d.hist_bs = hist.stride(0) if hist is not None else 0
+    d.x_bs, d.y_bs, d.q0, d.m_lo = x.stride(0), y.stride(0), q0, m_lo
+    d.B, d.n_hist, d.T, d.n_out = x.shape[0], hist.shape[1] if hist is not None else 0, x.shape[1] if T is None else T, n_out
+    d.o, d.n, d.taps = geo["o"], geo["n"], geo["taps"]
+    return d
+
+
+def resample_form(d):
+    """-> (form, outputs per tile, threads, LDS bytes, grid x) of the launch fac_resample makes for the descriptor (host only)."""
+    out = (C.c_int32 * 4)()
+    form = _lib.load().fac_resample_form(C.byref(d), out)
+    if form < 0:
+        _lib.check(-1, "fac_resample_form")
+    return (form,) + tuple(out)
+
+
+def resample(x, rate_in, rate_out, lens=None, quality="best"):
+    """x (B, T) or (B, 1, T) fp32 at rate_in -> the same rank with ceil(T n / o) columns at rate_out (o, n = the rates over their
+    gcd), one launch; the input itself when the rates are equal.  lens (B,) int32 on the device: row b is resampled as
+    x[b, :lens[b]] -- what sits behind is never read as signal -- and the outputs from ceil(lens[b] n / o) on are zeros; row b
+    is bit-equal to the call on that slice alone."""
+    geo = resample_table(rate_in, rate_out, quality)                 # ValueError: quality, rates, ratio
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+        raise ValueError(f"resample takes (B, T) or (B, 1, T), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    x = _dev(x, "x")
+    if int(rate_in) == int(rate_out):
+        return x
+    B, T = x.shape[0], x.shape[-1]
+    geo, table, offs = _resample_device_table(rate_in, rate_out, quality, x.device)
+    n_out = -(-T * geo["n"] // geo["o"])
+    y = torch.empty(x.shape[:-1] + (n_out,), device=x.device, dtype=torch.float32)
+    if B == 0 or n_out == 0:
+        return y
+    d = resample_desc(geo, table, offs, x.view(B, T), y.view(B, n_out), n_out, lens=_lens(lens, B) if lens is not None else None)
+    _lib.check(_lib.load().fac_resample(C.byref(d), _stream()), "fac_resample")
+    return y
 
 
 def spec_power(spec, power):

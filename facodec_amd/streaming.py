@@ -27,6 +27,7 @@ How the offline arithmetic is reproduced incrementally
 import torch
 
 from . import ops
+from .commons import MODEL_RATE
 from .dac_model import FUSED_RU_CHANNELS, DecoderBlock, EncoderBlock
 from .layers import ConvWeights
 from .quantize import check_codes
@@ -807,3 +808,145 @@ class StreamingDecoder:
             for o, d in zip(self._counters, delta):
                 o.c[:] = [ci + di for ci, di in zip(o.c, d)]
             return wave
+
+
+class StreamingResampler:
+    """ops.resample one block at a time, over B parallel streams:
+
+        rs = StreamingResampler(B, 48000, 24000)             # quality "fast" (W = 16) unless asked otherwise
+        y = rs.push(block)                                   # (B, 1, k) at rate_in, k n % o == 0  ->  (B, 1, k n / o) at rate_out
+        tail = rs.finish()                                   # the last rs.delay samples
+
+    An output needs the inputs up to ceil(W o / base) samples to its right, so the stream runs `delay` = ceil(ceil(W o / base) n / o)
+    output samples (`latency` seconds) behind the offline call: the pushes and finish(), concatenated, are `delay` zeros followed
+    by ops.resample of the whole signal -- bit for bit and for any split into admissible blocks, because the kernel's per-output
+    arithmetic depends on the output's phase alone.  The state is the last `n_hist` input samples a later output can still reach,
+    in two buffers that swap roles: the launch that resamples a block also writes the next block's history (fac_resample
+    hist_out), so a push is ONE launch, reads nothing back to the host and allocates nothing but its output.  Equal rates pass
+    the blocks through (delay 0)."""
+
+    def __init__(self, B, rate_in, rate_out, quality="fast", device="cuda"):
+        geo = ops.resample_table(rate_in, rate_out, quality)
+        self.B, self.rate_in, self.rate_out, self.quality = int(B), int(rate_in), int(rate_out), quality
+        self.o, self.n = geo["o"], geo["n"]
+        self.device = torch.device(device)
+        self.samples = 0                                      # input samples taken so far
+        self.identity = self.rate_in == self.rate_out
+        if self.identity:
+            self.delay, self.latency, self.n_hist = 0, 0.0, 0
+            return
+        half = geo["half"]
+        self.delay = -(-half * self.n // self.o)
+        self.latency = self.delay / self.rate_out
+        # the earliest output of a block lies `delay` outputs = up to ceil(delay o / n) inputs before it and reaches `half` further back
+        self.n_hist = -(-self.delay * self.o // self.n) + half + 1
+        self._geo, self._table, self._offs = ops._resample_device_table(rate_in, rate_out, quality, self.device)
+        self._hist = [torch.zeros(self.B, self.n_hist, device=self.device) for _ in range(2)]
+        self._cur = 0
+
+    def _launch(self, x, n_out, carry, T=None):
+        y = torch.empty(self.B, 1, n_out, device=self.device)
+        hist = self._hist[self._cur]
+        d = ops.resample_desc(self._geo, self._table, self._offs, x, y.view(self.B, n_out), n_out, hist=hist,
+                              hist_out=self._hist[1 - self._cur] if carry else None, q0=self.samples,
+                              m_lo=self.samples * self.n // self.o - self.delay, T=T)
+        ops._lib.check(ops._lib.load().fac_resample(ops.C.byref(d), ops._stream()), "fac_resample")
+        return y
+
+    def push(self, block):
+        if not isinstance(block, torch.Tensor) or block.dim() != 3 or block.shape[0] != self.B or block.shape[1] != 1:
+            raise ValueError(f"push() takes (B = {self.B}, 1, k), got {tuple(block.shape) if isinstance(block, torch.Tensor) else type(block)}")
+        k = block.shape[-1]
+        if k < 1 or k * self.n % self.o:
+            raise ValueError(f"a block of {k} samples at {self.rate_in} Hz is no whole number of samples at {self.rate_out} Hz "
+                             f"(k must be a positive multiple of {self.o})")
+        if not block.is_cuda or block.dtype != torch.float32:
+            raise ops._lib.FacodecHipError(f"block must be float32 on the GPU (got {block.dtype} on {block.device}); there is no CPU path")
+        if self.identity:
+            self.samples += k
+            return block
+        # rows of any pitch are taken as they are (fac_resample_desc.x_bs): a slice wave[:, :, t:t + k] of a longer buffer is not copied
+        x = block[:, 0, :]
+        if k > 1 and x.stride(1) != 1:
+            x = x.contiguous()
+        y = self._launch(x, k * self.n // self.o, carry=True)
+        self._cur ^= 1
+        self.samples += k
+        return y
+
+    def finish(self):
+        """The `delay` output samples the stream was still holding back (the signal ends where the last block ended)."""
+        if self.identity:
+            return torch.empty(self.B, 1, 0, device=self.device)
+        # an empty block: x only has to be a valid pointer (an empty tensor has none), none of its columns is read
+        return self._launch(self._hist[self._cur], self.delay, carry=False, T=0)
+
+
+class ResampledSession:
+    """A StreamingCodec / StreamingConverter / StreamingDecoder that takes its audio at `in_rate` and gives it at `out_rate`:
+
+        vc = ResampledSession(StreamingConverter(codec, redecoder, timbre), in_rate=48000, out_rate=48000)
+        out = vc.prime(wave48[:, :, :9600])              # prime_samples * in_rate / 24000 samples
+        out = vc.push(wave48[:, :, t:t + 960])           # 480 * in_rate / 24000 samples per hop
+        out = vc.finish()
+
+    Same surface and the same dicts as the wrapped session (a StreamingDecoder's calls take codes and return the wave alone), with
+    `wave` at out_rate and the codes untouched; finish() appends what the output resampler was holding back.  Each side is one
+    StreamingResampler launch run eagerly around the session's captured graphs, and adds that resampler's `latency`
+    (`latency_in`, `latency_out`; a rate of None or 24000 adds nothing).  The session sees `delay_in` zeros and then the
+    resampled input, cut off where the pushed audio ends."""
+
+    def __init__(self, session, in_rate=None, out_rate=None, quality="fast"):
+        in_rate = MODEL_RATE if in_rate is None else in_rate
+        out_rate = MODEL_RATE if out_rate is None else out_rate
+        ops.resample_table(in_rate, MODEL_RATE, quality)                   # ValueError: rates, ratio, quality
+        ops.resample_table(MODEL_RATE, out_rate, quality)
+        takes_audio = hasattr(session, "prime_samples")
+        if not takes_audio and in_rate != MODEL_RATE:
+            raise ValueError("in_rate: this session takes codes, not audio")
+        if HOP * in_rate % MODEL_RATE:
+            raise ValueError(f"in_rate {in_rate}: a hop of {HOP} samples at {MODEL_RATE} Hz is no whole number of samples there")
+        if FRAME * out_rate % MODEL_RATE:
+            raise ValueError(f"out_rate {out_rate}: a frame of {FRAME} samples at {MODEL_RATE} Hz is no whole number of samples there")
+        self.session = session
+        self.in_rate, self.out_rate = int(in_rate), int(out_rate)
+        self.hop_samples = HOP * self.in_rate // MODEL_RATE
+        self.prime_samples = session.prime_samples * self.in_rate // MODEL_RATE if takes_audio else None
+        B, dev = session.B, session.device
+        self.rs_in = StreamingResampler(B, self.in_rate, MODEL_RATE, quality, dev) if self.in_rate != MODEL_RATE else None
+        self.rs_out = StreamingResampler(B, MODEL_RATE, self.out_rate, quality, dev) if self.out_rate != MODEL_RATE else None
+        self.delay_in = self.rs_in.delay if self.rs_in else 0
+        self.delay_out = self.rs_out.delay if self.rs_out else 0
+        self.latency_in = self.rs_in.latency if self.rs_in else 0.0
+        self.latency_out = self.rs_out.latency if self.rs_out else 0.0
+
+    def _in(self, wave, want):
+        if self.rs_in is None:
+            return wave
+        if wave.shape[-1] != want:
+            raise ValueError(f"this call wants exactly {want} samples at {self.in_rate} Hz, got {wave.shape[-1]}")
+        return self.rs_in.push(wave)
+
+    def _out(self, r, final=False):
+        if self.rs_out is None:
+            return r
+        wave = r["wave"] if isinstance(r, dict) else r
+        parts = [self.rs_out.push(wave)] if wave is not None else []
+        if final:
+            parts.append(self.rs_out.finish())
+        wave = None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+        return dict(r, wave=wave) if isinstance(r, dict) else wave
+
+    def prime(self, first):
+        return self._out(self.session.prime(self._in(first, self.prime_samples) if self.prime_samples else first))
+
+    def push(self, hop):
+        return self._out(self.session.push(self._in(hop, self.hop_samples) if self.prime_samples else hop))
+
+    def finish(self):
+        if hasattr(self.session, "finish"):
+            return self._out(self.session.finish(), final=True)
+        return self.rs_out.finish() if self.rs_out is not None else None
+
+    def set_target(self, timbre):
+        return self.session.set_target(timbre)

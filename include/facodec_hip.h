@@ -706,6 +706,41 @@ int fac_logdiff_rms(const float* a, const float* b, float* out, float* scratch, 
 int fac_logdiff_rms_bwd(const float* a, const float* b, float* db, int B, int M, int T, float eps, float scale,
                         int accumulate, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sample-rate conversion by a rational ratio: polyphase windowed-sinc filter, o = rate_in / g input samples per
+ * n = rate_out / g output samples.  table (n, taps) fp32 and offs (n,) int32 come from the host (facodec_amd/dsp.py
+ * resample_table): output m = k n + p reads the inputs k o + offs[p] + j, j = 0 .. taps - 1, and is
+ *     y[m] = sum_j table[p][j] * x[k o + offs[p] + j]     accumulated in ascending j with one fma per tap,
+ * so the order of an output's additions depends on its phase p alone.
+ *
+ * Row b's signal, in ABSOLUTE sample indices q (int64: a stream may run longer than 2^31 samples), is
+ *     hist[b * hist_bs + (q - (q0 - n_hist))]   for q0 - n_hist <= q < q0       (carried history; NULL with n_hist = 0)
+ *     x[b * x_bs + (q - q0)]                    for q0 <= q < q0 + L_b,         L_b = lens ? clamp(lens[b], 0, T) : T
+ * and 0 everywhere else, below q = 0 included: nothing behind lens[b] is read.  The launch writes y[b * y_bs + i] for
+ * i = 0 .. n_out - 1, the output of absolute index m = m_lo + i; it is 0 for m < 0 and for m >= ceil((q0 + L_b) n / o).
+ * The offline call is n_hist = 0, q0 = 0, m_lo = 0, n_out = ceil(T n / o).
+ * hist_out (or NULL; needs lens == NULL; must not overlap hist or x): hist_out[b * hist_bs + j] = the sample of absolute index
+ * q0 + T - n_hist + j, j = 0 .. n_hist - 1 -- the history the next block of the stream is resampled with, written by the same
+ * launch.  o, n <= 640; |q0 - m_lo o / n| + n_hist + T must fit 31 bits. */
+typedef struct fac_resample_desc {
+  const float* hist;
+  const float* x;
+  const int32_t* lens;
+  float* y;
+  float* hist_out;
+  const float* table;
+  const int32_t* offs;
+  int64_t hist_bs, x_bs, y_bs;
+  int64_t q0, m_lo;
+  int32_t B, n_hist, T, n_out;
+  int32_t o, n, taps;
+} fac_resample_desc;
+int fac_resample(const fac_resample_desc* d, fac_stream_t stream);
+/* Which form of the kernel fac_resample launches for the descriptor (host logic only, nothing is launched):
+ * 0 = coefficient table and input span in LDS, 1 = table read from global memory, span in LDS, 2 = both read from global memory
+ * (a span too long for LDS: extreme ratios); -1 on error.  out4 (or NULL) = {outputs per tile, threads, LDS bytes, grid x}. */
+int fac_resample_form(const fac_resample_desc* d, int32_t* out4);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
