@@ -57,10 +57,15 @@ int prep_launch_bwd(const PrepJob* jobs, const int* first, int njobs, int total,
   return check_launch("bwd_batch");
 }
 
-// dx[b][c][j] = dxpad[pad_left + j] (+ the gradients of the padded positions that mirror sample j)
+// dx[b][c][j] = dxpad[pad_left + j] (+ the gradients of the padded positions that mirror sample j).  A signal not longer than
+// its pad is reflected about the ends of pad1d's zero extension of length Text = max(pad) + 1 (reflect_index of the forward): the
+// left edge still mirrors about sample 0, the right edge about sample Text - 1, and only the padded positions that exist
+// (< Tp) and land on a real sample (< T) carry a gradient.  Text == T for every longer signal.
 __global__ void pad_fold_bwd_kernel(const float* __restrict__ dxpad, float* __restrict__ dx, int T, int Tp,
                                     int pad_left, int mode, long long n) {
   const int pad_right = Tp - pad_left - T;
+  const int max_pad = pad_left > pad_right ? pad_left : pad_right;
+  const int Text = T > max_pad ? T : max_pad + 1;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int j = (int)(i % T);
     const long long row = i / T;
@@ -68,8 +73,8 @@ __global__ void pad_fold_bwd_kernel(const float* __restrict__ dxpad, float* __re
     float g = p[pad_left + j];
     if (mode == FAC_PAD_REFLECT) {
       if (j >= 1 && j <= pad_left) g += p[pad_left - j];                       // xpad[pad_left - j] = x[j]
-      const int m = T - 1 - j;                                                 // xpad[pad_left + T-1 + m] = x[T-1-m]
-      if (m >= 1 && m <= pad_right) g += p[pad_left + T - 1 + m];
+      const int m = Text - 1 - j;                                              // xpad[pad_left + Text-1 + m] = x[Text-1-m]
+      if (m >= 1 && m <= pad_right - (Text - T)) g += p[pad_left + Text - 1 + m];
     }
     dx[i] = g;
   }
@@ -491,8 +496,6 @@ extern "C" int fac_pad_fold_bwd(const float* dxpad, float* dx, int B, int C, int
                                 fac_stream_t stream) {
   using namespace fac;
   FAC_REQUIRE(dxpad && dx && B > 0 && C > 0 && T > 0 && pad_left >= 0 && Tp >= pad_left + T, "pad_fold_bwd: bad arguments");
-  FAC_REQUIRE(pad_mode != FAC_PAD_REFLECT || (T > pad_left && T > Tp - pad_left - T),
-              "pad_fold_bwd: reflect padding needs a signal longer than the pad");
   const long long n = (long long)B * C * T;
   const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
   hipLaunchKernelGGL(pad_fold_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dxpad, dx, T, Tp, pad_left,

@@ -471,7 +471,8 @@ int fac_prep_free(int plan);
  * (taps flipped, channels transposed; C_out becomes the input-channel axis: rows up to fac_cin_pad(C_out),
  * columns C_in_pad = pad32(C_in), zero-filled by the caller), pad_left = (K-1)*dilation, zero padding,
  * T_out = padded input length; then fac_pad_fold_bwd maps the gradient of the padded signal back to x
- * (reflection: a padded position's gradient is added to the sample it mirrors).  Strided convs (K = 2*stride):
+ * (reflection: a padded position's gradient is added to the sample it mirrors; a signal not longer than its pad mirrors
+ * about the ends of pad1d's zero extension, as the forward reads it).  Strided convs (K = 2*stride):
  * the transposed-conv launch on the forward weights (fac_pack_convtr_w), then the same fold.
  * ---------------------------------------------------------------------------------------- */
 int fac_pack_conv_w_bwd(const float* v, const float* scale, float* packed, int C_out, int C_in, int K, int C_in_pad,
