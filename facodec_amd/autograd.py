@@ -25,6 +25,22 @@ def _wn(w):
     return (w.weight_v, w.weight_g) if w.weight_norm else (w.weight, None)
 
 
+def plan_conv_fwd(c_out, c_in, k, stride, dilation, B, T, plain, causal_reflect):
+    """_Conv.forward's planner call for B clips of T columns, from shapes and flags alone."""
+    return ops.plan_conv(c_out, c_in, k, stride, dilation, B, T, -(-T // stride), plain=plain, causal_reflect=causal_reflect,
+                         flat_train="reflect")
+
+
+def plan_convtr_fwd(c_in, c_out, stride, B, T, causal):
+    """_ConvTr.forward's planner call: a training site flattens clips of T columns plus their zero column."""
+    return ops.plan_convtr(c_in, c_out, stride, B, T, causal=causal, flat_train_cols=T + 1)
+
+
+def plan_res_unit(c, c_in, dilation, B, T):
+    """_ResUnit.forward's two planner calls, (k = 7 conv c_in -> c, k = 1 tail c -> c): stride 1, so T columns throughout."""
+    return ops.plan_conv(c, c_in, 7, 1, dilation, B, T, T), ops.plan_conv(c, c, 1, 1, 1, B, T, T)
+
+
 class _Conv(Function):
     @staticmethod
     def forward(ctx, x, v, g, bias, cfg):
@@ -32,8 +48,8 @@ class _Conv(Function):
         vd, gd = v.detach(), (g.detach() if g is not None else None)
         sc = ops.wn_scale(vd, gd) if gd is not None else None          # g / ||v||: once per forward, re-used by the backward
         B, _, T = x.shape
-        plan = ops.plan_conv(v.shape[0], v.shape[1], k, stride, dilation, B, T, -(-T // stride), plain=act == ops.ACT_NONE,
-                             causal_reflect=causal and pad_mode == ops.PAD_REFLECT, flat_train="reflect")
+        plan = plan_conv_fwd(v.shape[0], v.shape[1], k, stride, dilation, B, T, act == ops.ACT_NONE,
+                             causal and pad_mode == ops.PAD_REFLECT)
         wp, ws = ops.pack_conv_for(plan.layout, vd, gd, stride, scale=sc)
         ctx.scale = sc
         xin = x.detach()
@@ -82,7 +98,7 @@ class _ConvTr(Function):
         # kernel's phase_shift -- so train and eval forwards agree)
         B, _, T = x.shape
         bd = bias.detach() if bias is not None else None
-        plan = ops.plan_convtr(v.shape[0], v.shape[1], stride, B, T, causal=causal, flat_train_cols=T + 1)
+        plan = plan_convtr_fwd(v.shape[0], v.shape[1], stride, B, T, causal)
         wt = ops.pack_convtr_for(plan.layout, vd, gd, stride)
         if plan.layout == ops.TR_FLAT:
             # short clips: a zero column in front of every clip (the x[t - 1] of its first frame), one flattened signal; the s output
@@ -159,10 +175,11 @@ class _ResUnit(Function):
         v7d, g7d, v1d, g1d = v7.detach(), g7.detach(), v1.detach(), g1.detach()
         s7, s1 = ops.wn_scale(v7d, g7d), ops.wn_scale(v1d, g1d)      # once per forward, re-used by the backward
         B, _, T = xad.shape
-        wp, ws = ops.pack_conv_for(ops.plan_conv(c, v7.shape[1], 7, 1, dilation, B, T, T).layout, v7d, g7d, scale=s7)
+        plan7, plan1 = plan_res_unit(c, v7.shape[1], dilation, B, T)
+        wp, ws = ops.pack_conv_for(plan7.layout, v7d, g7d, scale=s7)
         h, ha = ops.conv1d(xad, wp, c, 7, bias=b7.detach(), dilation=dilation, pad_mode=pad_mode, causal=causal,
                            alpha_y2=a2.detach().reshape(-1), w_split=ws)
-        wp1, ws1 = ops.pack_conv_for(ops.plan_conv(c, c, 1, 1, 1, B, ha.shape[-1], ha.shape[-1]).layout, v1d, g1d, scale=s1)
+        wp1, ws1 = ops.pack_conv_for(plan1.layout, v1d, g1d, scale=s1)
         y, ya = ops.conv1d(ha, wp1, c, 1, bias=b1.detach(), pad_mode=pad_mode, causal=causal, res=xd,
                            alpha_y2=a_next.detach().reshape(-1), w_split=ws1)
         ctx.cfg = cfg
@@ -236,17 +253,13 @@ class _LSTM(Function):
         for l in range(L):
             w_ih, w_hh, b_ih, b_hh = (p.detach() for p in params[4 * l: 4 * l + 4])
             with ops.flop_scale(B / BP):
-                plan = ops.plan_gemm(4 * H, H, T * BP)
-                sig = ops.p8_prepass(inp.view(1, H, T * BP), plan.p8)
-                pre = ops.conv1d(sig, ops.pack_conv_weight(w_ih) if plan.layout == ops.W_FP32 else None, 4 * H, 1,
-                                 bias=ops.add(b_ih, b_hh), pad_left=0, t_out=T * BP, pad_mode=ops.PAD_ZERO,
-                                 w_split=ops.pack_gemm_weight_split(w_ih) if plan.layout == ops.W_GEMM else None)
+                pre = ops.lstm_input_proj(inp, w_ih, ops.add(b_ih, b_hh))
                 gates = torch.empty(4 * H, T, BP, device=x.device)
                 cs = torch.empty(H, T, BP, device=x.device)
                 if ops.lstm_persist_ok(H, B):      # whole layer in one launch, W_hh resident in registers
-                    yT = ops.lstm_layer_persist(pre.view(4 * H, T, BP), w_hh, H, B, save=(gates, cs))
+                    yT = ops.lstm_layer_persist(pre, w_hh, H, B, save=(gates, cs))
                 else:
-                    yT = ops.lstm_layer(pre.view(4 * H, T, BP), ops.pack_lstm_whh(w_hh), H, save=(gates, cs))
+                    yT = ops.lstm_layer(pre, ops.pack_lstm_whh(w_hh), H, save=(gates, cs))
             saved.append((inp, yT, gates, cs))
             inp = yT
         ctx.saved = saved
@@ -284,7 +297,7 @@ class _LSTM(Function):
             db = ops.bias_grad(dg_flat)
             grads[4 * l + 2], grads[4 * l + 3] = db, db.clone()
             # gradient w.r.t. this layer's input sequence: W_ih^T dgates, one GEMM over every (t, b)
-            if ops.plan_gemm(H, 4 * H, T * BP).layout == ops.W_GEMM:
+            if ops.plan_lstm_proj_bwd(H, T * BP).layout == ops.W_GEMM:
                 d_out = ops.conv1d(dg_flat, None, H, 1, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=T * BP,
                                    w_split=ops.pack_gemm_weight_split_t(w_ih)).view(H, T, BP)
             else:

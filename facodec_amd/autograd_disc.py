@@ -20,6 +20,27 @@ def _plan(c_out, c_in, k, stride, batch, t_in, t_out, k1):
                          split2=True)
 
 
+def tap_span(k, k1=0, dil2=0):
+    """Largest tap offset of a conv with k taps (PlainConv's `taps`: k1 per level, the levels dil2 apart; plain: k - 1)."""
+    return (k // k1 - 1) * dil2 + (k1 - 1) if k1 else k - 1
+
+
+def plan_bwd_transposed(c_out, c_in, stride, batch, t_ext):
+    """PlainConv.backward, strided conv with at most two taps per output phase: the transposed conv over dy and its zero column
+    (t_ext columns per clip)."""
+    return ops.plan_convtr(c_out, c_in, stride, batch, t_ext)
+
+
+def plan_bwd_stride1(c_out, c_in, k, k1, dil2, pad, batch, t_up, t_in):
+    """PlainConv.backward's stride-1 flipped-weight conv over the (zero-inserted) gradient of t_up columns, from shapes alone:
+    (plan, max_off, pl, tp, shift).  The conv is launched with its left padding max_off reduced by `pad` (pl) and exactly
+    tp = t_in outputs; a padding larger than the taps' span (pl < 0, no layer of the model) keeps the full padding and is sliced."""
+    max_off = tap_span(k, k1, dil2)
+    pl = max_off - pad
+    tp, shift = (t_in, pl) if pl >= 0 else (t_up + max_off, max_off)
+    return _plan(c_in, c_out, k, 1, batch, t_up, tp, k1), max_off, pl, tp, shift      # the forward rule with the channels swapped
+
+
 class PlainConv(Function):
     """torch-semantics Conv1d (zero padding `pad` both sides, stride) with optional weight-norm gain g (C_out,1,1).
     taps = (k1, dilation2): two-level taps -- tap k = k2 * k1 + k1' reads offset k2 * dilation2 + k1' (a (K2, k1) Conv2d over
@@ -29,8 +50,7 @@ class PlainConv(Function):
     def forward(ctx, x, v, g, bias, k, stride, pad, taps=None):
         B, c_in, t_in = x.shape
         k1, dil2 = taps if taps is not None else (0, 0)
-        max_off = (k // k1 - 1) * dil2 + (k1 - 1) if k1 else k - 1
-        t_out = (t_in + 2 * pad - max_off - 1) // stride + 1
+        t_out = (t_in + 2 * pad - tap_span(k, k1, dil2) - 1) // stride + 1
         vd, gd = v.detach().contiguous(), (g.detach().contiguous() if g is not None else None)
         sc = ops.wn_scale(vd, gd) if gd is not None else None           # once per forward, re-used by the backward
         # 32-channel (3, 9) / (3, 3) stacks: conv1d_bsplit2.hip; (5, 1) stride-3 convs: split GEMM over 3 phases; k = 5 / 7: split taps
@@ -40,14 +60,14 @@ class PlainConv(Function):
         xin = ops.p8_prepass(x.detach(), plan.p8)       # (5, 1) stride-3 convs on the split GEMM kernel
         y = ops.conv1d(xin, wp, v.shape[0], k, bias=bias.detach() if bias is not None else None,
                        stride=stride, pad_left=pad, pad_mode=ops.PAD_ZERO, t_out=t_out, w_split=ws, k1=k1, dilation2=dil2)
-        ctx.cfg = (k, stride, pad, t_in, t_out, k1, dil2, max_off)
+        ctx.cfg = (k, stride, pad, t_in, t_out, k1, dil2)
         ctx.save_for_backward(x, v, g, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, v, g, bias = ctx.saved_tensors
-        k, stride, pad, t_in, t_out, k1, dil2, max_off = ctx.cfg
+        k, stride, pad, t_in, t_out, k1, dil2 = ctx.cfg
         dy = dy.contiguous()
         B, c_out, _ = dy.shape
         c_in = v.shape[1]
@@ -60,7 +80,7 @@ class PlainConv(Function):
                 # polyphase transposed conv (no zero-inserted columns: 1.2x the useful flops for k = 5, s = 3 instead of 3x)
                 v6 = torch.cat([vd, vd.new_zeros(c_out, c_in, 2 * stride - k)], dim=2) if k < 2 * stride else vd
                 dy_ext = torch.cat([dy, dy.new_zeros(B, c_out, 1)], dim=2)
-                tplan = ops.plan_convtr(c_out, c_in, stride, B, dy_ext.shape[-1])
+                tplan = plan_bwd_transposed(c_out, c_in, stride, B, dy_ext.shape[-1])
                 wt = ops.pack_convtr_for(tplan.layout, v6, gd, stride)
                 dy_ext = ops.p8_prepass(dy_ext, tplan.p8)
                 with ops.flop_scale(k / (2.0 * stride)):      # the zero taps that pad k to 2 * stride are not algorithmic work
@@ -76,12 +96,8 @@ class PlainConv(Function):
             if up is not None:
                 # dx[j] = dxpad[j + pad], dxpad[i] = sum_k wflip[k] up[i - max_off + off'_k]: the conv is launched with its left padding
                 # reduced by `pad` and exactly t_in outputs (columns past `up` read zeros), so no padded tensor is sliced or extended
-                pl = max_off - pad
-                if pl >= 0:
-                    tp, shift = t_in, pl
-                else:                     # (not reached by the model's layers: padding larger than the taps' span)
-                    tp, shift = up.shape[-1] + max_off, max_off
-                layout = _plan(c_in, c_out, k, 1, B, up.shape[-1], tp, k1).layout      # the forward rule with the channels swapped
+                plan, _, pl, tp, shift = plan_bwd_stride1(c_out, c_in, k, k1, dil2, pad, B, up.shape[-1], t_in)
+                layout = plan.layout
                 wp, ws = ((ops.pack_conv_weight_bwd(vd, gd, ctx.scale), None) if layout == ops.W_FP32
                           else ops.pack_conv_for(layout, ops.flipped_weight(vd, gd, ctx.scale), None, k1=k1))
                 # zero-inserted columns (stride > 1) are not algorithmic work (the split-taps launch has always counted them)

@@ -227,23 +227,16 @@ class SLSTM(nn.Module):
         for l in range(self.num_layers):
             p = self.lstm
             w_raw = getattr(p, f"weight_ih_l{l}").detach()
-            plan = ops.plan_gemm(4 * H, H, inp.shape[1] * inp.shape[2])
-            w_ih = ops.pack_conv_weight(w_raw) if plan.layout == ops.W_FP32 else None
-            w_ih_split = ops.pack_gemm_weight_split(w_raw) if plan.layout == ops.W_GEMM else None
             bias = ops.add(getattr(p, f"bias_ih_l{l}").detach(), getattr(p, f"bias_hh_l{l}").detach())
             w_hh = getattr(p, f"weight_hh_l{l}").detach()
             persist = ops.lstm_persist_ok(H, B)
             T_, BP = inp.shape[1], inp.shape[2]
-            # one GEMM over every (t, b): the channel-major buffer is a (1, H, T*BP) "signal"
-            sig = inp.view(1, H, T_ * BP)
-            sig = ops.p8_prepass(sig, plan.p8)
             with ops.flop_scale(B / BP):
-                pre = ops.conv1d(sig, w_ih, 4 * H, 1, bias=bias, pad_left=0, t_out=T_ * BP,
-                                 pad_mode=ops.PAD_ZERO, w_split=w_ih_split)
+                pre = ops.lstm_input_proj(inp, w_raw, bias)
                 if ops.lstm_persist_split_ok(H, B, T_):      # 17 .. 32 columns: resident, W_hh . h on the bf16 matrix pipe
-                    inp = ops.lstm_layer_persist_split(pre.view(4 * H, T_, BP), w_hh, H, B)
+                    inp = ops.lstm_layer_persist_split(pre, w_hh, H, B)
                 elif persist:     # whole layer in one launch, W_hh resident in registers (lstm_persist.hip)
-                    inp = ops.lstm_layer_persist(pre.view(4 * H, T_, BP), w_hh, H, B)
+                    inp = ops.lstm_layer_persist(pre, w_hh, H, B)
                 else:
-                    inp = ops.lstm_layer(pre.view(4 * H, T_, BP), ops.pack_lstm_whh(w_hh), H)
+                    inp = ops.lstm_layer(pre, ops.pack_lstm_whh(w_hh), H)
         return ops.lstm_from_time_major(inp, x if self.skip else None, B, alpha_out)

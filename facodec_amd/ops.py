@@ -548,6 +548,36 @@ def p8_prepass(x, flop_per_in_byte):
     return to_p8(x)
 
 
+def conv_y_channels(c_out, act):
+    """Channels of a conv's output tensor: the gated epilogues write c_out / 2."""
+    return c_out // 2 if act in (ACT_GATE, ACT_WN_RES_SKIP) else c_out
+
+
+def conv_desc(B, c_in, t_in, c_out, k, stride=1, dilation=1, pad_left=None, pad_mode=PAD_REFLECT, t_out=None, act=ACT_NONE, causal=True,
+              k1=0, dilation2=0, c_out_pad=None, split_rows=0):
+    """The launch descriptor of conv1d from shapes and flags alone (no tensor, no GPU): every non-pointer field of fac_conv_desc --
+    the fields this function does not name stay the zeros of a fresh ConvDesc.  With pad_left=None the SConv1d padding rule gives
+    pad_left and T_out (causal: everything on the left; non-causal: asymmetric split).  The strides are those of contiguous
+    (B, c_in, t_in) / (B, conv_y_channels, T_out) tensors; conv1d overrides them for views and fills in the pointers.
+    c_out_pad: padded row count of the fp32 pack (None: pad32); split_rows: co-tile size a split-taps buffer was packed for."""
+    if pad_left is None:
+        t_o, padding_total, _ = conv_out_len(t_in, k, stride, dilation)
+        pad_left = padding_total if causal else padding_total - padding_total // 2
+        if t_out is None:
+            t_out = t_o
+    if t_out is None:
+        raise ValueError("t_out required with explicit pad_left")
+    d = ConvDesc()
+    d.x_bs, d.x_cs = c_in * t_in, t_in
+    d.y_bs, d.y_cs = conv_y_channels(c_out, act) * t_out, t_out
+    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in, c_out, (pad32(c_out) if c_out_pad is None else c_out_pad), t_out
+    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = k, stride, dilation, pad_left, pad_mode
+    d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = 1, 1, act, 0, 0
+    d.K1, d.dilation2, d.split_rows = k1, dilation2, split_rows
+    d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and (k == 1 or (PW_TAPS and k == 4 and stride == 2))) else 0
+    return d
+
+
 def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None, pad_mode=PAD_REFLECT,
            t_out=None, alpha_in=None, alpha_out=None, res=None, act=ACT_NONE, out=None, causal=True,
            alpha_y2=None, want_y=True, w_k1=None, bias_k1=None, w_split=None, k1=0, dilation2=0, skip_acc=None, gate_cond=None):
@@ -559,7 +589,8 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
     act=ACT_GATE / ACT_WN_RES_SKIP (streaming hops only, facodec_hip.h): the output has c_out / 2 channels; ACT_WN_RES_SKIP adds
     the first half of the channels to `res` (-> out, which may be res itself) and the second half onto `skip_acc` in place.
     gate_cond (act=ACT_GATE only): (B, c_out) conditioning rows added to the pre-activations before the gate, as
-    gate_tanh_sigmoid(a, g) adds them (bit-identical to that pair of launches); may be a column slice of a wider (B, n) tensor."""
+    gate_tanh_sigmoid(a, g) adds them (bit-identical to that pair of launches); may be a column slice of a wider (B, n) tensor.
+    The shape-only part of the launch is conv_desc; this function adds what needs the tensors."""
     x_p8 = x if isinstance(x, P8) else None
     if x_p8 is not None:
         B, c_in, t_in = x_p8.shape
@@ -568,15 +599,10 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
             x = _dev(x, "x")     # channel-sliced views (time contiguous) are consumed in place
         B, c_in, t_in = x.shape
     dev_ = x_p8.planes.device if x_p8 is not None else x.device
-    if pad_left is None:
-        t_o, padding_total, _ = conv_out_len(t_in, k, stride, dilation)
-        pad_left = padding_total if causal else padding_total - padding_total // 2
-        if t_out is None:
-            t_out = t_o
-    if t_out is None:
-        raise ValueError("t_out required with explicit pad_left")
-    cp = w_packed.shape[-1] if w_packed is not None else pad32(c_out)
-    c_y = c_out // 2 if act in (ACT_GATE, ACT_WN_RES_SKIP) else c_out
+    d = conv_desc(B, c_in, t_in, c_out, k, stride, dilation, pad_left, pad_mode, t_out, act, causal, k1, dilation2,
+                  w_packed.shape[-1] if w_packed is not None else None,
+                  getattr(w_split, "split_rows", 0))         # co-tile size the buffer was packed for (pack_conv_weight_split)
+    t_out, c_y = d.T_out, conv_y_channels(c_out, act)
     if out is None and want_y:
         out = torch.empty(B, c_y, t_out, device=dev_, dtype=torch.float32)
     y2 = torch.empty(B, c_out, t_out, device=dev_, dtype=torch.float32) if alpha_y2 is not None else None
@@ -584,12 +610,12 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
         assert skip_acc is not None and skip_acc.is_contiguous() and skip_acc.shape == out.shape and alpha_y2 is None
         y2 = skip_acc
     res = _dev(res, "res")
-    d = ConvDesc()
     d.bias = bias.data_ptr() if bias is not None else None
     if x_p8 is not None:
         d.x, d.x_p8, d.x_p8_plane_bytes = None, x_p8.planes.data_ptr(), x_p8.plane_bytes
     else:
         d.x = x.data_ptr()
+        d.x_bs, d.x_cs = x.stride(0), x.stride(1)
     d.w = w_packed.data_ptr() if w_packed is not None else w_split.data_ptr()   # split-only launch: see fac_conv_desc.w_split
     d.alpha_in = alpha_in.data_ptr() if alpha_in is not None else None
     d.alpha_out = alpha_out.data_ptr() if alpha_out is not None else None
@@ -600,24 +626,16 @@ def conv1d(x, w_packed, c_out, k, bias=None, stride=1, dilation=1, pad_left=None
     d.w_k1 = w_k1.data_ptr() if w_k1 is not None else None
     d.bias_k1 = bias_k1.data_ptr() if bias_k1 is not None else None
     d.w_split = w_split.data_ptr() if w_split is not None else None
-    d.split_rows = getattr(w_split, "split_rows", 0)         # co-tile size the buffer was packed for (pack_conv_weight_split)
-    d.x_bs, d.x_cs = (x.stride(0), x.stride(1)) if x_p8 is None else (c_in * t_in, t_in)
-    d.y_bs, d.y_cs = c_y * t_out, t_out
     if out is not None and (out.stride(0), out.stride(1)) != (d.y_bs, d.y_cs) and out.shape[0] * out.shape[1] > 1:
         # a time-contiguous view of a wider buffer as the output (streaming: the LSTM pre-activations of the real batch columns)
         assert out.stride(2) == 1 and y2 is None and res is None and out.shape == (B, c_y, t_out)
         d.y_bs, d.y_cs = out.stride(0), out.stride(1)
-    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in, c_out, cp, t_out
-    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = k, stride, dilation, pad_left, pad_mode
-    d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = 1, 1, act, 0, 0
-    d.K1, d.dilation2 = k1, dilation2
     if gate_cond is not None:
         if not (gate_cond.is_cuda and gate_cond.dtype == torch.float32 and gate_cond.dim() == 2 and gate_cond.shape == (B, c_out)
                 and (gate_cond.stride(1) == 1 or c_out == 1)):
             raise ValueError(f"gate_cond must be a float32 GPU tensor (B={B}, c_out={c_out}) with contiguous rows, "
                              f"got {tuple(gate_cond.shape)} {gate_cond.dtype} {gate_cond.device}")
         d.gate_cond, d.gate_cond_bs = gate_cond.data_ptr(), gate_cond.stride(0)
-    d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and (k == 1 or (PW_TAPS and k == 4 and stride == 2))) else 0
     _launch_conv(d, "fac_conv1d_fwd")
     return (out, y2) if alpha_y2 is not None else out
 
@@ -628,38 +646,57 @@ STREAM_FOLD = True
 SKINNY_MAX_COLS = 640
 
 
+def convtr_desc(B, c_in, t_in, c_out, stride, c_out_pad, causal=True, has_history=False, rows=False, split=False):
+    """The launch descriptor of conv_transpose1d from shapes and flags alone, as conv_desc is conv1d's.  t_in: columns of x, the
+    history column included.  c_out_pad: padded rows of the weights (pad32(c_out) polyphase, convtr_rows_pad for the rows layouts).
+    rows: one of the rows layouts (all phases per workgroup, contiguous stores); split: its split GEMM form (no fp32 weights)."""
+    t_cols = t_in - 1 if has_history else t_in
+    t_total = t_cols * stride
+    d = ConvDesc()
+    d.x_bs, d.x_cs = c_in * t_in, t_in
+    d.y_bs, d.y_cs = c_out * t_total, t_total
+    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in, c_out, c_out_pad, t_cols
+    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = 2, 1, 1, (0 if has_history else 1), PAD_ZERO
+    d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = stride, stride, ACT_NONE, 0, 0
+    # non-causal: trim ceil(s/2) on the left, floor(s/2) on the right (dac/model/encodec.py:265-269)
+    d.phase_shift = 0 if causal else stride - stride // 2
+    if rows or split:
+        if not causal or has_history:
+            raise _lib.FacodecHipError("the all-phases ConvTranspose1d launch is causal and offline only")
+        d.n_phase, d.y_tstride, d.phase_shift, d.row_phases = 1, 1, 0, stride
+        d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and PW_TAPS and not split and stride == 2) else 0
+    return d
+
+
 def conv_transpose1d(x, w_packed, c_out, stride, bias=None, alpha_in=None, out=None, alpha_y2=None, causal=True,
                      has_history=False):
     """Causal SConvTranspose1d (kernel 2*stride, right trim k-stride: dac/model/encodec.py:248-270)
     as `stride` polyphase 2-tap convs: y[., t*s+p] = W[p] x[t] + W[p+s] x[t-1].
     has_history (streaming): x's first column is x[t0-1] of an earlier chunk (instead of the zero of
-    the start of the signal); x may then be a time-contiguous view of a wider buffer."""
+    the start of the signal); x may then be a time-contiguous view of a wider buffer.
+    The shape-only part of the launch is convtr_desc."""
     x_p8 = x if isinstance(x, P8) else None
     if x_p8 is not None:       # all-phases split-GEMM launch only (fac_conv1d_fwd rejects P8 operands anywhere else)
         assert not has_history
         B, c_in, t_in = x_p8.shape
-        x_bs, x_cs = c_in * t_in, t_in
     else:
         if not (has_history and x.is_cuda and x.dtype == torch.float32 and x.stride(2) == 1):
             x = _dev(x, "x")
         B, c_in, t_in = x.shape
-        x_bs, x_cs = x.stride(0), x.stride(1)
     dev_ = x_p8.planes.device if x_p8 is not None else x.device
-    t_in_full = t_in
     if has_history:
         assert causal
-        t_in -= 1
-    t_total = t_in * stride
     split_rows = isinstance(w_packed, tuple)       # (split GEMM buffer, rows) from pack_convtr_weight_rows_split
-    cp = w_packed[1] if split_rows else w_packed.shape[-1]
+    d = convtr_desc(B, c_in, t_in, c_out, stride, w_packed[1] if split_rows else w_packed.shape[-1], causal, has_history,
+                    not split_rows and w_packed.dim() == 3, split_rows)
     if out is None:
-        out = torch.empty(B, c_out, t_total, device=dev_, dtype=torch.float32)
-    d = ConvDesc()
+        out = torch.empty(B, c_out, d.T_out * stride, device=dev_, dtype=torch.float32)
     d.bias = bias.data_ptr() if bias is not None else None
     if x_p8 is not None:
         d.x, d.x_p8, d.x_p8_plane_bytes = None, x_p8.planes.data_ptr(), x_p8.plane_bytes
     else:
         d.x = x.data_ptr()
+        d.x_bs, d.x_cs = x.stride(0), x.stride(1)
     if split_rows:
         d.w, d.w_split = None, w_packed[0].data_ptr()
     else:
@@ -669,18 +706,6 @@ def conv_transpose1d(x, w_packed, c_out, stride, bias=None, alpha_in=None, out=N
     y2 = torch.empty_like(out) if alpha_y2 is not None else None
     d.y2 = y2.data_ptr() if y2 is not None else None
     d.alpha_y2 = alpha_y2.data_ptr() if alpha_y2 is not None else None
-    d.x_bs, d.x_cs = x_bs, x_cs
-    d.y_bs, d.y_cs = c_out * t_total, t_total
-    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in_full, c_out, cp, t_in
-    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = 2, 1, 1, (0 if has_history else 1), PAD_ZERO
-    d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = stride, stride, ACT_NONE, 0, 0
-    # non-causal: trim ceil(s/2) on the left, floor(s/2) on the right (dac/model/encodec.py:265-269)
-    d.phase_shift = 0 if causal else stride - stride // 2
-    if split_rows or w_packed.dim() == 3:          # rows layouts: all phases per workgroup, contiguous stores
-        if not causal or has_history:
-            raise _lib.FacodecHipError("the all-phases ConvTranspose1d launch is causal and offline only")
-        d.n_phase, d.y_tstride, d.phase_shift, d.row_phases = 1, 1, 0, stride
-        d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and PW_TAPS and not split_rows and stride == 2) else 0
     _launch_conv(d, "fac_conv1d_fwd(convtr)")
     return (out, y2) if alpha_y2 is not None else out
 
@@ -719,6 +744,17 @@ def convtr_weight_for(v, g, stride, t_in, causal=True, batch=1, alpha_in=None):
                            v, g, stride)
 
 
+def flat_conv_cols(B, L, s, n):
+    """(pitch, t_in, t_out) of conv1d_flat's one signal: B clips padded to L columns each, n outputs kept per clip."""
+    pitch = L // s
+    return pitch, B * L, B * pitch - (pitch - n)
+
+
+def flat_convtr_cols(B, T1):
+    """Columns of conv_transpose1d_flat's one signal: B clips of T1 columns, their zero column included."""
+    return B * T1
+
+
 def conv1d_flat(xp, w_split, c_out, k, s, n, dilation=1, bias=None, p8=None, alpha_out=None, act=ACT_NONE, alpha_y2=None, want_y=True):
     """Short clips as ONE signal.  xp (B, C_in, L): every clip already padded to length L -- reflected on the left by k - s = s
     samples (causal strided conv, L = (n + 1) s) or by (k - 1) d samples (causal stride-1 conv, L = n + (k - 1) d), or zeros
@@ -727,9 +763,8 @@ def conv1d_flat(xp, w_split, c_out, k, s, n, dilation=1, bias=None, p8=None, alp
     the per-clip launch, so the same bits -- and the pitch - n columns where the window straddles two clips are dropped on the way
     back -> (B, C_out, n); t_out = B pitch - (pitch - n).  p8: the plan's figure for ops.p8_prepass.  Returns what conv1d returns."""
     B, c_in, L = xp.shape
-    pitch = L // s
-    xf = p8_prepass(xp.permute(1, 0, 2).reshape(1, c_in, B * L), p8)                # data movement only
-    t_out = B * pitch - (pitch - n)
+    pitch, t_in, t_out = flat_conv_cols(B, L, s, n)
+    xf = p8_prepass(xp.permute(1, 0, 2).reshape(1, c_in, t_in), p8)                 # data movement only
     got = conv1d(xf, None, c_out, k, bias=bias, stride=s, dilation=dilation, pad_left=0, pad_mode=PAD_ZERO, t_out=t_out,
                  alpha_out=alpha_out, act=act, alpha_y2=alpha_y2, want_y=want_y, w_split=w_split)
 
@@ -749,7 +784,7 @@ def conv_transpose1d_flat(xz, w_rows_split, c_out, s, trim=0, bias=None, alpha_y
     it is the next clip's x[t - 1] as well; nothing to trim).  One signal of B T' columns through the all-phases split-GEMM launch
     -> (B, C_out, T' s - trim): per clip exactly the per-clip launch's output (y[t s + p] = W[p] x[t] + W[p + s] x[t - 1])."""
     B, c_in, T1 = xz.shape
-    xf = p8_prepass(xz.permute(1, 0, 2).reshape(1, c_in, B * T1), p8)
+    xf = p8_prepass(xz.permute(1, 0, 2).reshape(1, c_in, flat_convtr_cols(B, T1)), p8)
     got = conv_transpose1d(xf, w_rows_split, c_out, s, bias=bias, alpha_y2=alpha_y2, causal=True)
     back = lambda y: y.reshape(c_out, B, T1 * s)[:, :, trim:].permute(1, 0, 2).contiguous()   # noqa: E731
     return (back(got[0]), back(got[1])) if alpha_y2 is not None else back(got)
@@ -779,6 +814,27 @@ def lstm_from_time_major(yT, skip, B, alpha=None):
     _lib.check(_lib.load().fac_lstm_from_time_major(_ptr(yT), _ptr(skip), _ptr(alpha), _ptr(out), B, H, T, _stream()),
                "fac_lstm_from_time_major")
     return out
+
+
+def plan_lstm_proj(H, cols):
+    """An LSTM layer's input projection W_ih (4H, H) over the cols = T * BP columns of the time-major buffer, as one 1x1 conv."""
+    return plan_gemm(4 * H, H, cols)
+
+
+def plan_lstm_proj_bwd(H, cols):
+    """Its data gradient W_ih^T dgates over the same columns."""
+    return plan_gemm(H, 4 * H, cols)
+
+
+def lstm_input_proj(inp, w_ih, bias):
+    """inp (H, T, BP) time-major, raw w_ih (4H, H), bias = b_ih + b_hh -> the pre-activations (4H, T, BP): one GEMM over every
+    (t, b), the channel-major buffer as a (1, H, T * BP) "signal" (plan, pre-pass, pack, conv1d)."""
+    H, T, BP = inp.shape
+    plan = plan_lstm_proj(H, T * BP)
+    sig = p8_prepass(inp.view(1, H, T * BP), plan.p8)
+    pre = conv1d(sig, pack_conv_weight(w_ih) if plan.layout == W_FP32 else None, 4 * H, 1, bias=bias, pad_left=0, t_out=T * BP,
+                 pad_mode=PAD_ZERO, w_split=pack_gemm_weight_split(w_ih) if plan.layout == W_GEMM else None)
+    return pre.view(4 * H, T, BP)
 
 
 def pack_lstm_whh(w_hh, out=None):
@@ -1347,6 +1403,23 @@ def pack_conv_weight_bwd(v, g=None, scale=None, out=None):
     return packed
 
 
+def plan_bwd_data(c_out, c_in, k, stride, dilation, B, t_in, causal=True):
+    """What conv1d_bwd_data launches for the SConv1d c_in -> c_out over B clips of t_in columns, from shapes alone:
+    (plan, t_out, pad_left, pad_right, tp) with tp = pad_left + t_in + pad_right the columns of the padded gradient.
+    Stride 1: the forward plan of the conv with the channels swapped (a ConvPlan).  Strided (k = 2 s): the transposed conv over
+    dy and its zero column (a ConvTrPlan); its p8 is None off the flattened form, whose per-clip launch takes no pre-pass."""
+    t_out, padding_total, extra = conv_out_len(t_in, k, stride, dilation)
+    pad_left = padding_total if causal else padding_total - padding_total // 2
+    pad_right = (padding_total - pad_left) + extra
+    tp = pad_left + t_in + pad_right
+    if stride == 1:
+        return plan_conv(c_in, c_out, k, 1, dilation, B, t_out, tp), t_out, pad_left, pad_right, tp
+    if k != 2 * stride or dilation != 1:
+        raise NotImplementedError("strided bwd_data is built for the model's k = 2*stride convs")
+    plan = plan_convtr(c_out, c_in, stride, B, t_out + 1, flat_train_cols=t_out + 1)
+    return plan._replace(p8=plan.p8 if plan.layout == TR_FLAT else None), t_out, pad_left, pad_right, tp
+
+
 def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, causal=True, scale=None, allow_view=False):
     """Gradient w.r.t. the input of SConv1d (dac/model/encodec.py:212-228) given dy (B, C_out, T_out).
     scale: the weight-norm scale g / ||v|| if the caller already has it (the forward computed it).
@@ -1358,13 +1431,10 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
         scale = wn_scale(v, g)
     c_out, c_in, k = v.shape
     B, _, t_out = dy.shape
-    t_o, padding_total, extra = conv_out_len(t_in, k, stride, dilation)
+    plan, t_o, pad_left, pad_right, tp = plan_bwd_data(c_out, c_in, k, stride, dilation, B, t_in, causal)
     assert t_o == t_out, (t_o, t_out)
-    pad_left = padding_total if causal else padding_total - padding_total // 2
-    pad_right = (padding_total - pad_left) + extra
-    tp = pad_left + t_in + pad_right
+    layout = plan.layout
     if stride == 1:
-        layout = plan_conv(c_in, c_out, k, 1, dilation, B, t_out, tp).layout       # the forward plan of the conv with the channels swapped
         if layout == W_TAPS:
             # the flipped / transposed conv on the bf16 pipe too: materialise w = g v/||v||, swap channels, flip taps
             wt = flipped_weight(v, g, scale)                                   # (C_in, C_out, K) = weights of the bwd conv
@@ -1377,12 +1447,9 @@ def conv1d_bwd_data(dy, v, g, t_in, stride=1, dilation=1, pad_mode=PAD_REFLECT, 
             dxpad = conv1d(dy, pack_conv_weight_bwd(v, g, scale), c_in, k, dilation=dilation, pad_left=(k - 1) * dilation,
                            pad_mode=PAD_ZERO, t_out=tp)
     else:
-        if k != 2 * stride or dilation != 1:
-            raise NotImplementedError("strided bwd_data is built for the model's k = 2*stride convs")
         dy_ext = torch.cat([dy, torch.zeros(B, c_out, 1, device=dy.device)], dim=2)
-        plan = plan_convtr(c_out, c_in, stride, B, t_out + 1, flat_train_cols=t_out + 1)
-        wt = pack_convtr_for(plan.layout, v, g, stride)
-        if plan.layout == TR_FLAT:       # short clips: one flattened signal (the trailing zero column of a clip is the x[t - 1] of
+        wt = pack_convtr_for(layout, v, g, stride)
+        if layout == TR_FLAT:            # short clips: one flattened signal (the trailing zero column of a clip is the x[t - 1] of
             dxpad = conv_transpose1d_flat(dy_ext, wt, c_in, stride, p8=plan.p8)      # the next clip's first frame)
         else:
             dxpad = conv_transpose1d(dy_ext, wt, c_in, stride)
@@ -1570,6 +1637,13 @@ def bias_grad(dy):
     return db
 
 
+def plan_convtr_bwd(c_in, c_out, stride, B, t_in):
+    """The dx launch of conv_transpose1d_bwd, from shapes alone: the strided forward conv of dy (B clips of t_in * stride columns)
+    on the transposed conv's own weights.  p8 is None off the flattened form: the per-clip launch takes no pre-pass."""
+    plan = plan_conv(c_in, c_out, 2 * stride, stride, 1, B, t_in * stride, t_in, flat_train="zero")
+    return plan._replace(p8=plan.p8 if plan.form == FLAT_STRIDED else None)
+
+
 def conv_transpose1d_bwd(x, dy, v, g, stride, causal=True):
     """SConvTranspose1d (kernel 2*stride): -> (dx, dW (C_in, C_out, K)).  dx is the strided forward conv of dy
     on the same weights; dW the weight-gradient kernel with the roles of input and output swapped.
@@ -1582,7 +1656,7 @@ def conv_transpose1d_bwd(x, dy, v, g, stride, causal=True):
     c_out, k = v.shape[1], v.shape[2]
     assert k == 2 * stride and dy.shape == (B, c_out, t_in * stride)
     shift = 0 if causal else stride - stride // 2
-    plan = plan_conv(c_in, c_out, k, stride, 1, B, t_in * stride, t_in, flat_train="zero")     # the strided forward conv of dy
+    plan = plan_convtr_bwd(c_in, c_out, stride, B, t_in)
     wp, ws = pack_conv_for(plan.layout, v, g, stride)
     if plan.form == FLAT_STRIDED:
         # short clips: every clip gets its s columns of zeros (shift in front, s - shift behind) and the clips run as one flattened

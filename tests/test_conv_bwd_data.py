@@ -31,14 +31,14 @@ A lost low plane hides under 4 sqrt(n): every split case runs again with ops.BF1
 #   the forward of the short reflect cases 0.015; wn_scale 0.132
 # Split against fp32 route (max error / max |ref64|), worst pair: 4.8e-7 against 3.9e-7 (all-phases split GEMM, s = 2); over the
 # 31 split cases the split route's error is 1.4e-7 .. 7.5e-7, the fp32 route's 1.7e-7 .. 9.2e-7.
-import ctypes
 from collections import namedtuple
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from facodec_amd import _lib, convplan, ops
+from facodec_amd import convplan, ops
+from test_conv_plan_cpu import assert_same_launch, bwd_data_launch, convtr_bwd_launch
 from test_train_kernels_gen import CANARY, _check_adjoint, _record, _sum_bound
 from test_wgrad_split import _pad
 
@@ -152,69 +152,24 @@ BY_NAME = {c.name: c for c in CASES}
 
 # ------------------------------------------------------------------------------------------------ geometry, plan, descriptor
 def _geometry(c):
-    """(t_out, pad_left, pad_right, tp) of the SConv1d whose data gradient the case takes."""
-    t_out, total, extra = ops.conv_out_len(c.T, c.k, c.s, c.d)
-    pl = total if c.causal else total - total // 2
-    pr = total - pl + extra
-    return t_out, pl, pr, pl + c.T + pr
+    """(t_out, pad_left, pad_right, tp) of the SConv1d whose data gradient the case takes, as ops.conv1d_bwd_data derives them."""
+    return ops.plan_bwd_data(c.co, c.ci, c.k, c.s, c.d, c.B, c.T, c.causal)[1:]
 
 
 def _plan(c):
-    """The planner call of the site, as ops.conv1d_bwd_data / ops.conv_transpose1d_bwd make it: (layout, form)."""
-    if c.kind == "s1":
-        t_out, _, _, tp = _geometry(c)
-        p = convplan.plan_conv(c.ci, c.co, c.k, 1, c.d, c.B, t_out, tp)
+    """The site's own planner call (ops.plan_bwd_data / ops.plan_convtr_bwd): (layout, form)."""
+    if c.kind == "tr":
+        p = ops.plan_convtr_bwd(c.ci, c.co, c.s, c.B, c.T)
         return p.layout, p.form
-    if c.kind == "st":
-        t_out = _geometry(c)[0]
-        return convplan.plan_convtr(c.co, c.ci, c.s, c.B, t_out + 1, flat_train_cols=t_out + 1).layout, None
-    p = convplan.plan_conv(c.ci, c.co, c.k, c.s, 1, c.B, c.T * c.s, c.T, flat_train="zero")
-    return p.layout, p.form
+    p = ops.plan_bwd_data(c.co, c.ci, c.k, c.s, c.d, c.B, c.T, c.causal)[0]
+    return p.layout, (p.form if c.kind == "s1" else None)
 
 
 def _desc(c):
-    """The launch descriptor of the case's gradient conv with pointers that are never dereferenced (fac_conv1d_variant reads the
-    descriptor only): what ops.conv1d / ops.conv_transpose1d fill in for the plan `_plan` returns."""
-    layout, form = _plan(c)
-    fake = ctypes.c_void_p(0x10000)
-    d = _lib.ConvDesc()
-    d.x = d.y = fake
-    d.ws, d.ws_bytes = fake, ops.CONV_WS_BYTES
-    d.n_phase, d.y_tstride, d.stride, d.dilation, d.pad_mode = 1, 1, 1, 1, ZERO
-    pw = ops.BF16_SPLIT and ops.PW_SPLIT
-    if c.kind == "s1":
-        t_out, _, _, tp = _geometry(c)
-        split = layout in (TAPS, GEMM)
-        B, c_in, t_in, c_out, t_o, cp = c.B, c.co, t_out, c.ci, tp, ops.pad32(c.ci)
-        d.K, d.dilation, d.pad_left = c.k, c.d, (0 if layout == GEMM else (c.k - 1) * c.d)
-        d.split_rows = 64 if layout == TAPS else 0
-        d.pw_split = 1 if pw and c.k == 1 else 0
-    elif c.kind == "st":
-        t1 = _geometry(c)[0] + 1
-        split = layout in (RSPLIT, TFLAT)
-        B, t_in = (1, c.B * t1) if layout == TFLAT else (c.B, t1)
-        c_in, c_out, t_o = c.co, c.ci, t_in
-        d.K, d.pad_left = 2, 1
-        if layout == POLY:
-            cp, d.n_phase, d.y_tstride = ops.pad32(c_out), c.s, c.s
-        else:
-            cp, d.row_phases = ops.convtr_rows_pad(c_out, c.s), c.s
-            d.pw_split = 1 if pw and ops.PW_TAPS and not split and c.s == 2 else 0
-    else:
-        split = layout == GSTR
-        c_in, c_out, cp = c.co, c.ci, ops.pad32(c.ci)
-        d.K, d.stride = c.k, c.s
-        if form == convplan.FLAT_STRIDED:
-            B, t_in, t_o = 1, c.B * (c.T + 1) * c.s, c.B * (c.T + 1) - 1
-        else:
-            B, t_in, t_o, d.pad_left = c.B, c.T * c.s, c.T, (0 if c.causal else c.s - c.s // 2)
-        d.pw_split = 1 if pw and ops.PW_TAPS and c.k == 4 and c.s == 2 else 0
-    d.w, d.w_split = (None, fake) if split else (fake, None)
-    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in, c_out, cp, t_o
-    d.x_bs, d.x_cs = c_in * t_in, t_in
-    rows_t = t_o * (c.s if c.kind == "st" else 1)          # a transposed launch writes s samples per input column
-    d.y_bs, d.y_cs = c_out * rows_t, rows_t
-    return d
+    """The launch descriptor of the case's gradient conv, from the product's builders, with pointers that are never dereferenced."""
+    if c.kind == "tr":
+        return convtr_bwd_launch(c.ci, c.co, c.s, c.B, c.T, c.causal)
+    return bwd_data_launch(c.co, c.ci, c.k, c.s, c.d, c.B, c.T, c.causal)
 
 
 # ------------------------------------------------------------------------------------------------ reference
@@ -334,14 +289,14 @@ def test_reference_is_autograd_through_the_oracle_padding(name):
 
 # ------------------------------------------------------------------------------------------------ the GPU test
 class _Spy:
-    """Records (batch, kernel name) of every conv launch, as test_short_clip_training_convs_run_flattened does."""
+    """Records (batch, kernel name, descriptor) of every conv launch, as test_short_clip_training_convs_run_flattened does."""
 
     def __enter__(self):
         self.launches, self.orig = [], ops._launch_conv
 
         def spy(d, what):
             self.orig(d, what)               # first: the launch hands the descriptor its workspace, which the selection reads
-            self.launches.append((d.B, ops.conv_variant(d)[1]))
+            self.launches.append((d.B, ops.conv_variant(d)[1], d))
 
         ops._launch_conv = spy
         return self
@@ -382,7 +337,8 @@ def test_conv_bwd_data_route_against_fp64(name, cuda):
         torch.cuda.synchronize()
     # the route: one conv launch, the kernel the table names, flattened launches as one signal
     assert len(spy.launches) == 1, spy.launches
-    b_launch, kernel = spy.launches[0]
+    b_launch, kernel, launched = spy.launches[0]
+    assert_same_launch(launched, _desc(c), c.name)           # the descriptor the CPU tests of the table judge is the one launched
     assert c.kern in kernel and ("bf16x3" in kernel) == c.split, (kernel, c.kern)
     assert (b_launch == 1) == (c.flat or c.B == 1), (b_launch, kernel)
     assert dx.shape == (c.B, c.ci, c.T) and dx.is_contiguous()

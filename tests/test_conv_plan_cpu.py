@@ -6,7 +6,9 @@
    if / elif chains the planner replaced (the commit before it), evaluated on the rows this module enumerates -- not from the
    planner -- so it pins the policy across the move: one row per distinct (site, shape).
 2. Every row's launch descriptor goes through fac_conv1d_variant (host only): the C++ planner must pick the kernel family the
-   Python plan packed weights for.
+   Python plan packed weights for.  The plan is asked of the site's own shape-only function and the descriptor is built by the
+   product's builders (ops.conv_desc / ops.convtr_desc and the flat-geometry functions): `launch_desc` below.  The GPU tests
+   (tests/test_conv_launch_desc.py, tests/test_conv_bwd_data.py) hold a real launch's descriptor to the same `launch_desc`.
 3. The data-gradient plan of a stride-1 conv is the forward plan of the conv with the channels swapped.
 """
 import ctypes
@@ -81,6 +83,7 @@ def _stack_rows(net, T, units, tanh_last=False, frames=None):
 def _disc_rows(disc):
     """PlainConv launches of the period / resolution discriminators on B_TRAIN clips: (c_out, c_in, k, k1, stride, pad, t_in) of
     the single row-concatenated signal (batch 1)."""
+    from facodec_amd import autograd_disc
     from facodec_amd.discriminator import MPD, MRD
     rows = []
     for m in disc.modules():
@@ -106,7 +109,7 @@ def _disc_rows(disc):
             rows.append((1, 32, 9, 3, 1, Pp + 1, R * Pp, Pp))
     out = []
     for co, ci, k, k1, s, pad, t_in, dil2 in rows:
-        max_off = (k // k1 - 1) * dil2 + (k1 - 1) if k1 else k - 1
+        max_off = autograd_disc.tap_span(k, k1, dil2)
         t_out = (t_in + 2 * pad - max_off - 1) // s + 1
         out.append(("autograd_disc.PlainConv.forward", (co, ci, k, k1, s, 1, t_in, t_out, pad, dil2)))
         if s > 1 and not k1 and k <= 2 * s:
@@ -122,9 +125,9 @@ def _stub(**kw):
 
 
 def plan(site, a):
-    """What the site asks the planner, as plain lists (JSON).  The inference modules, _PlainConv and the discriminators are asked
-    through their own plan methods (on stubs that carry only the attributes those read), so their flags are the sites' own."""
-    from facodec_amd import autograd_disc
+    """What the site asks the planner, as plain lists (JSON): every site is asked through its own shape-only function -- the one
+    its launch code calls -- or, for the modules, its plan method on a stub that carries only the attributes that method reads."""
+    from facodec_amd import autograd, autograd_disc
     from facodec_amd.quantize import _PlainConv
     if site == "layers.SConv1d.run":
         co, ci, k, s, d, B, T, alpha, plain, res, cr, grad = a
@@ -135,41 +138,45 @@ def plan(site, a):
         co, ci, k, B, T = a
         p = _PlainConv.plan(_stub(c_out=co, c_in=ci, k=k), B, T)
     elif site == "autograd._Conv.forward":
-        co, ci, k, s, d, B, T, plain, cr = a
-        p = convplan.plan_conv(co, ci, k, s, d, B, T, -(-T // s), plain=plain, causal_reflect=cr, flat_train="reflect")
+        p = autograd.plan_conv_fwd(*a)
     elif site == "autograd._ResUnit.forward":
         co, ci, k, d, B, T = a
-        p = convplan.plan_conv(co, ci, k, 1, d, B, T, T)
+        p = autograd.plan_res_unit(co, ci, d, B, T)[0 if k == 7 else 1]
     elif site == "ops.conv1d_bwd_data(stride 1)":
         co, ci, k, d, B, T, causal = a
-        p = convplan.plan_conv(ci, co, k, 1, d, B, T, T + (k - 1) * d)
+        p = ops.plan_bwd_data(co, ci, k, 1, d, B, T, causal)[0]
     elif site == "ops.conv1d_bwd_data(strided)":
         co, ci, s, B, t_out = a
-        p = convplan.plan_convtr(co, ci, s, B, t_out + 1, flat_train_cols=t_out + 1)
-        p = p._replace(p8=p.p8 if p.layout == convplan.TR_FLAT else None)       # this site's per-clip launch takes no pre-pass
+        p, t_o = ops.plan_bwd_data(co, ci, 2 * s, s, 1, B, t_out * s)[:2]
+        assert t_o == t_out
     elif site == "ops.conv_transpose1d_bwd":
-        ci, co, s, B, T = a
-        p = convplan.plan_conv(ci, co, 2 * s, s, 1, B, T * s, T, flat_train="zero")
-        p = p._replace(p8=p.p8 if p.form == convplan.FLAT_STRIDED else None)    # this site's per-clip launch takes no pre-pass
+        p = ops.plan_convtr_bwd(*a)
     elif site == "layers.SConvTranspose1d.run":
         ci, co, s, B, T, causal, alpha, grad = a
         with torch.set_grad_enabled(grad):
             p = layers.SConvTranspose1d.plan(_stub(w=_stub(c_in=ci, c_out=co), stride=s, causal=causal), B, T, alpha)
     elif site == "autograd._ConvTr.forward":
-        ci, co, s, B, T, causal = a
-        p = convplan.plan_convtr(ci, co, s, B, T, causal=causal, flat_train_cols=T + 1)
+        p = autograd.plan_convtr_fwd(*a)
     elif site == "autograd_disc.PlainConv.forward":
         co, ci, k, k1, s, B, t_in, t_out = a[:8]
         p = autograd_disc._plan(co, ci, k, s, B, t_in, t_out, k1)
     elif site == "autograd_disc.PlainConv.backward(stride-1 conv)":
-        co, ci, k, k1, B, tu, tp = a[:7]
-        p = autograd_disc._plan(ci, co, k, 1, B, tu, tp, k1)
+        p = _disc_bwd_stride1(a)[0]
     elif site == "autograd_disc.PlainConv.backward(transposed)":
-        co, ci, s, B, T = a
-        p = convplan.plan_convtr(co, ci, s, B, T)
-    else:
-        p = convplan.plan_gemm(*a)
+        p = autograd_disc.plan_bwd_transposed(*a)
+    else:                                    # plan_gemm rows: the LSTM input projection (4H, H) and its data gradient (H, 4H)
+        co, ci, cols = a
+        p = ops.plan_lstm_proj(ci, cols) if co == 4 * ci else ops.plan_lstm_proj_bwd(co, cols)
     return list(p)
+
+
+def _disc_bwd_stride1(a):
+    """PlainConv.backward's own (plan, max_off, pl, tp, shift) for a table row, whose tp and shift columns it must reproduce."""
+    from facodec_amd import autograd_disc
+    co, ci, k, k1, B, tu, tp, shift, dil2 = a
+    got = autograd_disc.plan_bwd_stride1(co, ci, k, k1, dil2, autograd_disc.tap_span(k, k1, dil2) - shift, B, tu, tp)
+    assert got[3:] == (tp, shift), (a, got)
+    return got
 
 
 def all_rows():
@@ -209,44 +216,130 @@ def test_plans_match_the_recorded_decision_table(rows):
 
 FAMILY = {"split_taps": 11, "split_gemm": 15, "split_gemm_strided": 15, "split2": 16, "fp32_pw_taps": 18,
           "rows_split": 15, "flat_rows_split": 15, "rows_pw_taps": 18}
+ROWS96 = 19         # a split_taps plan that convplan.tile_rows completes with 96: the 96 x 256 form of the same kernel has an id of its own
 SPLIT_ONLY = ("split_taps", "split_gemm", "split_gemm_strided", "split2", "rows_split", "flat_rows_split")
 
 
-def _variant(layout, B, c_in, t_in, c_out, t_out, k, stride=1, dil=1, pad_left=0, k1=0, dil2=0, res=False, alpha_out=False, y2=False,
-             row_phases=0, c_out_pad=None):
-    d = _lib.ConvDesc()
-    fake = ctypes.c_void_p(0x10000)          # never dereferenced: fac_conv1d_variant only reads the descriptor
-    d.x, d.y, d.bias = fake, fake, fake
-    d.w = None if layout in SPLIT_ONLY else fake           # split-only launch: the plan packed no fp32 weights
-    d.w_split = fake if layout in SPLIT_ONLY else None
-    d.res = fake if res else None
-    d.alpha_out = fake if alpha_out else None
-    d.y2 = d.alpha_y2 = fake if y2 else None
-    d.ws, d.ws_bytes = fake, ops.CONV_WS_BYTES
-    d.x_bs, d.x_cs, d.y_bs, d.y_cs = c_in * t_in, t_in, c_out * t_out * max(1, row_phases), t_out * max(1, row_phases)
-    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, t_in, c_out, c_out_pad or ops.pad32(c_out), t_out
-    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = k, stride, dil, pad_left, ops.PAD_ZERO
-    d.n_phase, d.y_tstride, d.phase_shift, d.act, d.w_batched, d.w_bs = 1, 1, 0, 0, 0, 0
-    d.K1, d.dilation2, d.row_phases = k1, dil2, row_phases
-    if row_phases:                           # ops.conv_transpose1d
-        d.pw_split = 1 if (ops.BF16_SPLIT and ops.PW_SPLIT and ops.PW_TAPS and layout not in SPLIT_ONLY and row_phases == 2) else 0
-    else:                                    # ops.conv1d
-        d.pw_split = 1 if (ops.BF16_SPLIT and ops.PW_SPLIT and (k == 1 or (ops.PW_TAPS and k == 4 and stride == 2))) else 0
-    return ops.conv_variant(d)
+def fake_operands(d, *names, gate_cond_bs=0):
+    """Non-null pointers for x, y, the workspace and the operands named (w, w_split, bias, res, alpha_out, y2, alpha_y2, gate_cond,
+    ...) on a descriptor from ops.conv_desc / ops.convtr_desc.  Never dereferenced: fac_conv1d_variant only reads the descriptor."""
+    fake = ctypes.c_void_p(0x10000)
+    d.x = d.y = d.ws = fake
+    d.ws_bytes = ops.CONV_WS_BYTES
+    for n in names:
+        setattr(d, n, fake)
+    if "gate_cond" in names:
+        d.gate_cond_bs = gate_cond_bs
+    return d
 
 
-def _conv_desc(p, co, ci, k, s, d, B, T, causal=True, **kw):
-    """An SConv1d launch as the site makes it: per clip with the layer's left padding, or (causal) flattened without padding."""
-    P = (k - 1) * d + 1 - s
-    if p[1] == "per_clip":
-        return _variant(p[0], B, ci, T, co, -(-T // s), k, s, d, pad_left=P if causal else P - P // 2, **kw)
-    pitch, n = (T + P) // s, T // s
-    return _variant(p[0], 1, ci, B * (T + P), co, B * pitch - (pitch - n), k, s, d, **kw)
+def assert_same_launch(got, want, what=""):
+    """A launched descriptor against a CPU-built one: every non-pointer field equal, every pointer null in both or in neither
+    (the workspace, which the launch itself hands over, aside)."""
+    bad = []
+    for name, ctype in _lib.ConvDesc._fields_:
+        if name in ("ws", "ws_bytes"):
+            continue
+        g, w = getattr(got, name), getattr(want, name)
+        if ctype is ctypes.c_void_p:
+            g, w = bool(g), bool(w)
+        if g != w:
+            bad.append((name, g, w))
+    assert not bad, (what, bad)
 
 
-def _convtr_desc(layout, ci, co, s, B, T):
-    rows = -(-co // (128 // s)) * 128        # ops.convtr_rows_pad
-    return _variant(layout, B, ci, T, co, T, 2, pad_left=1, row_phases=s, c_out_pad=rows)
+def conv_launch(layout, *shape, rows=64, operands=(), **kw):
+    """ops.conv1d's descriptor for a plan layout: conv_desc(*shape, **kw) with the co-tile figure of a split-taps buffer (rows: 64
+    at the training sites, convplan.tile_rows at the inference sites) and the weights the layout packs -- a split-only launch hands
+    its buffer over as `w` too."""
+    d = ops.conv_desc(*shape, split_rows=rows if layout == convplan.W_TAPS else 0, **kw)
+    return fake_operands(d, "w", *(("w_split",) if layout in SPLIT_ONLY else ()), *operands)
+
+
+def convtr_launch(layout, B, c_in, T, c_out, s, causal=True, operands=()):
+    """ops.conv_transpose1d's descriptor for a transposed plan layout over B clips of T columns (flattened: as one signal)."""
+    split = layout in (convplan.TR_ROWS_SPLIT, convplan.TR_FLAT)
+    cp = ops.pad32(c_out) if layout == convplan.TR_POLYPHASE else ops.convtr_rows_pad(c_out, s)
+    if layout == convplan.TR_FLAT:
+        B, T = 1, ops.flat_convtr_cols(B, T)
+    d = ops.convtr_desc(B, c_in, T, c_out, s, cp, causal, False, layout in (convplan.TR_ROWS, convplan.TR_ROWS_PW_TAPS), split)
+    return fake_operands(d, "w_split" if split else "w", *operands)
+
+
+def flat_conv_launch(layout, B, c_in, L, c_out, k, s, n, dilation=1, **kw):
+    """ops.conv1d_flat's descriptor: B clips padded to L columns as one unpadded signal, n outputs kept per clip."""
+    _, t_in, t_out = ops.flat_conv_cols(B, L, s, n)
+    return conv_launch(layout, 1, c_in, t_in, c_out, k, s, dilation, 0, ops.PAD_ZERO, t_out, **kw)
+
+
+def bwd_data_launch(co, ci, k, s, d, B, T, causal=True):
+    """The gradient launch of ops.conv1d_bwd_data for the SConv1d ci -> co over B clips of T columns."""
+    p, t_out, _, _, tp = ops.plan_bwd_data(co, ci, k, s, d, B, T, causal)
+    if s > 1:
+        return convtr_launch(p.layout, B, co, t_out + 1, ci, s)
+    if p.layout == convplan.W_GEMM:
+        return conv_launch(p.layout, B, co, t_out, ci, 1, 1, 1, 0, ops.PAD_ZERO, tp)
+    return conv_launch(p.layout, B, co, t_out, ci, k, 1, d, (k - 1) * d, ops.PAD_ZERO, tp)
+
+
+def convtr_bwd_launch(ci, co, s, B, T, causal=True):
+    """The dx launch of ops.conv_transpose1d_bwd for the transposed conv ci -> co over B clips of T columns."""
+    p = ops.plan_convtr_bwd(ci, co, s, B, T)
+    if p.form == convplan.FLAT_STRIDED:
+        return flat_conv_launch(p.layout, B, co, (T + 1) * s, ci, 2 * s, s, T)
+    return conv_launch(p.layout, B, co, T * s, ci, 2 * s, s, 1, 0 if causal else s - s // 2, ops.PAD_ZERO, T)
+
+
+def sconv_launch(p, co, ci, k, s, d, B, T, causal, pad_mode=ops.PAD_REFLECT, act=ops.ACT_NONE, rows=64, operands=("bias",)):
+    """An SConv1d launch as layers.SConv1d.run / autograd._Conv.forward make it: per clip with the layer's padding rule, or the
+    clips reflect-padded on the left by the causal padding and flattened."""
+    if p[1] == convplan.PER_CLIP:
+        return conv_launch(p[0], B, ci, T, co, k, s, d, None, pad_mode, None, act, causal, rows=rows, operands=operands)
+    return flat_conv_launch(p[0], B, ci, T + ops.conv_out_len(T, k, s, d)[1], co, k, s, T // s, d, act=act, rows=rows, operands=operands)
+
+
+def launch_desc(site, a, operands=None):
+    """The descriptor of the conv the site launches for the table row (site, a), built by the product's own builders from the
+    site's own plan.  operands: the optional operands the launch carries (default: what the model's layers hand that site)."""
+    p = plan(site, a)
+    Y2 = ("y2", "alpha_y2")
+    if site == "layers.SConv1d.run":
+        co, ci, k, s, d, B, T, _, plain, res, cr, _ = a
+        if operands is None:
+            operands = ("bias",) + (("res",) if res else ()) + (("alpha_out",) if not plain and not res else ()) + Y2
+        return sconv_launch(p, co, ci, k, s, d, B, T, cr, rows=ops.tile_rows(co, ci, k), operands=operands)
+    if site == "autograd._Conv.forward":
+        co, ci, k, s, d, B, T, plain, cr = a
+        return sconv_launch(p, co, ci, k, s, d, B, T, cr, ops.PAD_REFLECT if cr else ops.PAD_ZERO, ops.ACT_NONE if plain else ops.ACT_TANH)
+    if site == "quantize._PlainConv.run":
+        co, ci, k, B, T = a
+        return conv_launch(p[0], B, ci, T, co, k, 1, 1, (k - 1) // 2, ops.PAD_ZERO, T, rows=ops.tile_rows(co, ci, k), operands=("bias",))
+    if site == "autograd._ResUnit.forward":
+        co, ci, k, d, B, T = a
+        return conv_launch(p[0], B, ci, T, co, k, 1, d, operands=("bias",) + (("res",) if k == 1 else ()) + Y2)
+    if site == "ops.conv1d_bwd_data(stride 1)":
+        co, ci, k, d, B, T, causal = a
+        return bwd_data_launch(co, ci, k, 1, d, B, T, causal)
+    if site == "ops.conv1d_bwd_data(strided)":
+        co, ci, s, B, t_out = a
+        return bwd_data_launch(co, ci, 2 * s, s, 1, B, t_out * s)
+    if site == "ops.conv_transpose1d_bwd":
+        return convtr_bwd_launch(*a)
+    if site in ("layers.SConvTranspose1d.run", "autograd._ConvTr.forward"):
+        ci, co, s, B, T, causal = a[:6]               # flattened: a zero column in front of every clip
+        return convtr_launch(p[0], B, ci, T + (p[0] == convplan.TR_FLAT), co, s, causal, ("bias",) if operands is None else operands)
+    if site == "autograd_disc.PlainConv.forward":
+        co, ci, k, k1, s, B, t_in, t_out, pad, dil2 = a
+        return conv_launch(p[0], B, ci, t_in, co, k, s, 1, pad, ops.PAD_ZERO, t_out, k1=k1, dilation2=dil2, operands=("bias",))
+    if site == "autograd_disc.PlainConv.backward(stride-1 conv)":
+        co, ci, k, k1, B, tu = a[:6]
+        _, _, _, tp, shift = _disc_bwd_stride1(a)
+        return conv_launch(p[0], B, co, tu, ci, k, 1, 1, shift, ops.PAD_ZERO, tp, k1=k1, dilation2=a[8])
+    if site == "autograd_disc.PlainConv.backward(transposed)":
+        co, ci, s, B, T = a
+        return convtr_launch(p[0], B, co, T, ci, s)
+    co, ci, cols = a                         # plan_gemm rows: one signal of `cols` columns
+    return conv_launch(p[0], 1, ci, cols, co, 1, 1, 1, 0, ops.PAD_ZERO, cols, operands=("bias",) if co == 4 * ci else ())
 
 
 def test_cpp_planner_picks_the_family_the_python_plan_packed_for(rows):
@@ -257,43 +350,10 @@ def test_cpp_planner_picks_the_family_the_python_plan_packed_for(rows):
         p = plan(site, a)
         if p[0] not in FAMILY:
             continue
-        if site == "layers.SConv1d.run":
-            co, ci, k, s, d, B, T, _, plain, res, _, _ = a
-            got = _conv_desc(p, co, ci, k, s, d, B, T, causal=a[10], res=res, alpha_out=not plain and not res, y2=True)
-        elif site == "autograd._Conv.forward":
-            got = _conv_desc(p, *a[:7], causal=a[8])
-        elif site == "quantize._PlainConv.run":
-            co, ci, k, B, T = a
-            got = _variant(p[0], B, ci, T, co, T, k, pad_left=(k - 1) // 2)
-        elif site == "autograd._ResUnit.forward":
-            co, ci, k, d, B, T = a
-            got = _conv_desc(p, co, ci, k, 1, d, B, T, res=k == 1, y2=True)
-        elif site == "ops.conv1d_bwd_data(stride 1)":
-            co, ci, k, d, B, T, _ = a
-            got = _variant(p[0], B, co, T, ci, T + (k - 1) * d, k, 1, d, pad_left=(k - 1) * d)
-        elif site == "ops.conv_transpose1d_bwd":
-            ci, co, s, B, T = a
-            if p[1] == "per_clip":
-                got = _variant(p[0], B, co, T * s, ci, T, 2 * s, s)
-            else:
-                got = _variant(p[0], 1, co, B * (T + 1) * s, ci, B * (T + 1) - 1, 2 * s, s)
-        elif site == "autograd_disc.PlainConv.forward":
-            co, ci, k, k1, s, B, t_in, t_out, pad, dil2 = a
-            got = _variant(p[0], B, ci, t_in, co, t_out, k, s, pad_left=pad, k1=k1, dil2=dil2)
-        elif site == "autograd_disc.PlainConv.backward(stride-1 conv)":
-            co, ci, k, k1, B, tu, tp, shift, dil2 = a
-            got = _variant(p[0], B, co, tu, ci, tp, k, pad_left=shift, k1=k1, dil2=dil2)
-        elif site in ("layers.SConvTranspose1d.run", "autograd._ConvTr.forward"):
-            ci, co, s, B, T = a[:5]
-            got = _convtr_desc(p[0], ci, co, s, B, T) if p[0] != "flat_rows_split" else _convtr_desc(p[0], ci, co, s, 1, B * (T + 1))
-        elif site in ("ops.conv1d_bwd_data(strided)", "autograd_disc.PlainConv.backward(transposed)"):
-            co, ci, s, B, T1 = a[0], a[1], a[2], a[3], a[4] + (1 if site.startswith("ops") else 0)
-            got = _convtr_desc(p[0], co, ci, s, B, T1) if p[0] != "flat_rows_split" else _convtr_desc(p[0], co, ci, s, 1, B * T1)
-        else:                                # plan_gemm: one signal of `cols` columns
-            co, ci, cols = a
-            got = _variant(p[0], 1, ci, cols, co, cols, 1)
+        d = launch_desc(site, a)
+        got = ops.conv_variant(d)
         checked += 1
-        if got[0] != FAMILY[p[0]]:
+        if got[0] != (ROWS96 if d.split_rows == 96 else FAMILY[p[0]]):
             bad.append((site, a, p, got))
     assert checked > 40 and not bad, bad[:5]
 
@@ -305,8 +365,8 @@ def test_data_gradient_plan_is_the_forward_plan_with_channels_swapped():
         for ci in (16, 32, 48, 64, 256, 384, 1024):
             for k in (1, 3, 5, 7):
                 for B, T in ((1, 640), (1, 641), (16, 4800), (32, 160)):
-                    tp = T + (k - 1)
-                    grad = convplan.plan_conv(ci, co, k, 1, 1, B, T, tp)              # the call of ops.conv1d_bwd_data
+                    grad, _, _, _, tp = ops.plan_bwd_data(co, ci, k, 1, 1, B, T)      # the site's own call
+                    assert tp == T + (k - 1)
                     fwd = convplan.plan_conv(c_out=ci, c_in=co, k=k, stride=1, dilation=1, batch=B, t_in=T, t_out=tp)
                     assert grad == fwd
                     if k in (3, 5) and grad.layout == convplan.W_TAPS:

@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-from facodec_amd import _lib, synth
+from facodec_amd import _lib, ops, synth
+from test_conv_plan_cpu import fake_operands
 
 gpu = pytest.mark.gpu
 E2E_TOL = 1e-4           # tests/test_gpu_parity.py: end-to-end fp32 noise of the project's paths against each other / the reference
@@ -63,25 +64,9 @@ def test_converter_refuses_on_the_host():
         StreamingConverter(codec, mixed, torch.zeros(2, 1024))
 
 
-def _gate_desc(B, c_in, c_out, T_out, K, cond=True, act=4):
-    d = _lib.ConvDesc()
-    fake = ctypes.c_void_p(0x10000)          # never dereferenced: fac_conv1d_variant only reads the descriptor
-    T_in = T_out + K - 1
-    d.x, d.w, d.y, d.bias = fake, fake, fake, fake
-    d.ws, d.ws_bytes = fake, 32 << 20
-    c_y = c_out // 2 if act == 4 else c_out
-    d.x_bs, d.x_cs, d.y_bs, d.y_cs = c_in * T_in, T_in, c_y * T_out, T_out
-    d.B, d.C_in, d.T_in, d.C_out, d.C_out_pad, d.T_out = B, c_in, T_in, c_out, (c_out + 31) // 32 * 32, T_out
-    d.K, d.stride, d.dilation, d.pad_left, d.pad_mode = K, 1, 1, 0, 0
-    d.n_phase, d.y_tstride, d.act = 1, 1, act
-    if cond:
-        d.gate_cond, d.gate_cond_bs = fake, 16 * c_out
-    return d
-
-
-def _variant(d):
-    buf = ctypes.create_string_buffer(96)
-    return _lib.load().fac_conv1d_variant(ctypes.byref(d), buf, 96), buf.value.decode()
+def _gate_desc(B, c_in, c_out, T_out, K, cond=True, act=ops.ACT_GATE):
+    d = ops.conv_desc(B, c_in, T_out + K - 1, c_out, K, pad_left=0, pad_mode=ops.PAD_ZERO, t_out=T_out, act=act)
+    return fake_operands(d, "w", "bias", *(("gate_cond",) if cond else ()), gate_cond_bs=16 * c_out)
 
 
 def test_planner_takes_gate_cond_with_the_gate_only():
@@ -89,17 +74,17 @@ def test_planner_takes_gate_cond_with_the_gate_only():
     epilogue with it is refused on the host, by the planner and by the launch entry alike."""
     lib = _lib.load()
     assert ctypes.sizeof(_lib.ConvDesc) >= _lib.ConvDesc.gate_cond_bs.offset + 8
-    assert _variant(_gate_desc(1, 512, 1024, 2, 5)) == (10, GEMV_NAME)
-    assert _variant(_gate_desc(2, 512, 1024, 13, 5)) == (10, SKINNY_NAME)
+    assert ops.conv_variant(_gate_desc(1, 512, 1024, 2, 5)) == (10, GEMV_NAME)
+    assert ops.conv_variant(_gate_desc(2, 512, 1024, 13, 5)) == (10, SKINNY_NAME)
     for act in (0, 1, 5):
         d = _gate_desc(2, 512, 1024, 13, 5, act=act)
         d.res = d.y2 = d.x                                   # what FAC_ACT_WN_RES_SKIP needs; ignored by the others' check
         d.alpha_y2 = d.x if act != 5 else None
-        assert _variant(d)[0] == -1 and b"gate_cond" in lib.fac_last_error(), act
+        assert ops.conv_variant(d)[0] == -1 and b"gate_cond" in lib.fac_last_error(), act
         assert lib.fac_conv1d_fwd(ctypes.byref(d), None) == -1 and b"gate_cond" in lib.fac_last_error(), act
     d = _gate_desc(2, 512, 1024, 13, 5)
     d.gate_cond_bs = -1
-    assert _variant(d)[0] == -1 and b"gate_cond" in lib.fac_last_error()
+    assert ops.conv_variant(d)[0] == -1 and b"gate_cond" in lib.fac_last_error()
 
 
 def test_oracle_causal_redecoder_against_reference_fixture(golden_dir):
