@@ -205,6 +205,13 @@ SIGNATURES = {
     "fac_reduce_pair": (_i, [_p, _p, _p, _p, _i64, _i, _f, _f, _i, _p]),
     "fac_aa_snakebeta_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fac_logdiff_rms": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _i, _p]),
+    "fac_jdc_affine_lrelu_pool": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "fac_jdc_layout_in": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "fac_jdc_to_time_major": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fac_jdc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fac_jdc_head": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fac_f0_normalize": (_i, [_p, _p, _p, _i, _i, _p]),
+    "fac_mel_log_norm": (_i, [_p, _p, _i, _i, _i, _p]),
 }
 
 _lib = None

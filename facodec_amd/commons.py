@@ -319,3 +319,25 @@ def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_module
         optimizer.load_state_dict(state["optimizer"])
         optimizer.load_scheduler_state_dict(state["scheduler"])
     return model, optimizer, epoch, iters
+
+
+def load_F0_models(path):
+    """modules/commons.py:183-191: JDCNet(num_class=1, seq_len=192) with the checkpoint's ['net'] loaded (strict).  The reference
+    then leaves the model in .train(); ours computes eval arithmetic in either mode (see jdc.py).  Returned on the CPU like the
+    reference's: move it with .to(device)."""
+    from .jdc import JDCNet
+    model = JDCNet(num_class=1, seq_len=192)
+    params = torch.load(path, map_location="cpu")["net"]
+    model.load_state_dict(params)
+    return model
+
+
+def extract_f0(pitch_extractor, waves):
+    """Equal-length clips (B, T) at 24 kHz on the GPU -> the extractor's F0 track (B, 1 + T // 300), one value per 12.5 ms frame:
+    meldataset.preprocess (the features the extractor was trained on) then JDCNet.  The value is whatever the checkpoint was trained
+    to emit (Hz for the reference's bst.t7; train.py:226 calls a frame voiced where it exceeds 5)."""
+    from . import meldataset
+    waves = torch.as_tensor(waves)
+    if waves.dim() != 2:
+        raise ValueError(f"extract_f0 takes equal-length clips (B, T), got {tuple(waves.shape)}")
+    return pitch_extractor(meldataset.preprocess(waves).unsqueeze(1))[0]

@@ -1768,3 +1768,89 @@ def rows_fma(a, w=None, c=None, sign=1.0):
     _lib.check(_lib.load().fac_rows_fma(_ptr(a), _ptr(w), _ptr(_dev(c)), _ptr(out), B, a.numel() // B, sign, _stream()),
                "fac_rows_fma")
     return out
+
+
+# --------------------------------------------------------------------------------- pitch: JDC glue and the predictor targets (jdc.hip)
+def leaky_relu_rows(x, slope, pitch, valid, rows_per_group, valid_rows):
+    """LeakyReLU over a row-concatenated signal (1, C, rows * pitch); gap columns and separator rows come out zero (fac_leaky_relu)."""
+    x = _dev(x, "x")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().fac_leaky_relu(_ptr(x), _ptr(None), _ptr(y), x.numel(), C.c_float(slope), x.shape[-1], pitch, valid,
+                                          rows_per_group, valid_rows, _stream()), "fac_leaky_relu")
+    return y
+
+
+def jdc_affine_lrelu_pool(x, scale, shift, rows, rows_per_group, w_in, p_in, pool, slope):
+    """x (1, C, rows * p_in) -> (1, C, rows * p_in / pool): eval BatchNorm (scale / shift (C,), or None for identity) -> LeakyReLU ->
+    max over `pool` neighbouring bins; exact zeros in the gaps and separator rows (fac_jdc_affine_lrelu_pool)."""
+    x, scale, shift = _dev(x, "x"), _dev(scale, "scale"), _dev(shift, "shift")
+    c = x.shape[-2]
+    if x.shape[-1] != rows * p_in or p_in % pool:
+        raise ValueError(f"jdc_affine_lrelu_pool: signal of {x.shape[-1]} columns is not {rows} rows of pitch {p_in} (pool {pool})")
+    p_out = p_in // pool
+    y = torch.empty(1, c, rows * p_out, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_jdc_affine_lrelu_pool(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), c, rows, rows_per_group, w_in, p_in,
+                                                     pool, p_out, C.c_float(slope), _stream()), "fac_jdc_affine_lrelu_pool")
+    return y
+
+
+def jdc_layout_in(mel, pitch):
+    """mel (B, 1, W, T) -> the stage-0 signal (1, 1, B * (T + 1) * pitch)."""
+    mel = _dev(mel, "mel")
+    B, _, W, T = mel.shape
+    out = torch.empty(1, 1, B * (T + 1) * pitch, device=mel.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_jdc_layout_in(_ptr(mel), _ptr(out), B, W, T, pitch, _stream()), "fac_jdc_layout_in")
+    return out
+
+
+def jdc_to_time_major(x, B, T, W, pitch, reverse=False):
+    """Stage signal (1, C, B * (T + 1) * pitch) -> time-major LSTM input (C * W, T, pad32(B)); reverse: time flipped."""
+    x = _dev(x, "x")
+    c, BP = x.shape[-2], pad32(B)
+    out = torch.empty(c * W, T, BP, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_jdc_to_time_major(_ptr(x), _ptr(out), B, c, T, W, pitch, BP, 1 if reverse else 0, _stream()),
+               "fac_jdc_to_time_major")
+    return out
+
+
+def jdc_to_nchw(x, B, T, W, pitch, transposed=False):
+    """Stage signal (1, C, B * (T + 1) * pitch) -> (B, C, T, W), or (B, C, W, T) with transposed."""
+    x = _dev(x, "x")
+    c = x.shape[-2]
+    out = torch.empty((B, c, W, T) if transposed else (B, c, T, W), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_jdc_to_nchw(_ptr(x), _ptr(out), B, c, T, W, pitch, 1 if transposed else 0, _stream()), "fac_jdc_to_nchw")
+    return out
+
+
+def jdc_head(h_fwd, h_bwd, w, bias, B):
+    """|Linear(2H -> 1)| over [h_fwd(t) | h_bwd(T - 1 - t)], both (H, T, BP) time-major -> (B, T)."""
+    h_fwd, h_bwd, w, bias = _dev(h_fwd, "h_fwd"), _dev(h_bwd, "h_bwd"), _dev(w, "weight"), _dev(bias, "bias")
+    H, T, BP = h_fwd.shape
+    if h_bwd.shape != h_fwd.shape or w.numel() != 2 * H or bias.numel() != 1:
+        raise ValueError("jdc_head: the two directions must have one shape (H, T, BP), the weight 2H entries, the bias one")
+    out = torch.empty(B, T, device=h_fwd.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_jdc_head(_ptr(h_fwd), _ptr(h_bwd), _ptr(w), _ptr(bias), _ptr(out), B, T, H, BP, _stream()), "fac_jdc_head")
+    return out
+
+
+def f0_normalize(f0, want_mean=False):
+    """f0 (B, T) -> the normalised log-F0 targets of train.py:224-256 (fac_f0_normalize) [, per-clip means (B,)]."""
+    f0 = _dev(f0, "f0")
+    if f0.dim() != 2:
+        raise ValueError(f"f0 must be (B, T), got {tuple(f0.shape)}")
+    B, T = f0.shape
+    out = torch.empty_like(f0)
+    mean = torch.empty(B, device=f0.device, dtype=torch.float32) if want_mean else None
+    _lib.check(_lib.load().fac_f0_normalize(_ptr(f0), _ptr(out), _ptr(mean), B, T, _stream()), "fac_f0_normalize")
+    return (out, mean) if want_mean else out
+
+
+def mel_log_norm(mel):
+    """mel (B, n_mels, T) -> (B, T): log of the L2 norm over the bins of exp(4 mel - 4) (fac_mel_log_norm)."""
+    mel = _dev(mel, "mel")
+    if mel.dim() != 3:
+        raise ValueError(f"mel must be (B, n_mels, T), got {tuple(mel.shape)}")
+    B, M, T = mel.shape
+    out = torch.empty(B, T, device=mel.device, dtype=torch.float32)
+    _lib.check(_lib.load().fac_mel_log_norm(_ptr(mel), _ptr(out), B, M, T, _stream()), "fac_mel_log_norm")
+    return out

@@ -90,3 +90,28 @@ def synth_clips(batch, n_samples=48000, seed=0, rank=0, step=0):
     w = g.standard_normal((batch, n_samples))
     w = w / np.abs(w).max(axis=1, keepdims=True)
     return torch.from_numpy(w.astype(np.float32)).unsqueeze(1)
+
+
+def synth_jdc_state_dict(seed=0, shapes=None):
+    """A full state dict for jdc.JDCNet(num_class=1, seq_len=192) (and the reference class: same keys).  Conv / LSTM / Linear tensors
+    go through synth_tensor; BatchNorm weight = 0.75 + 0.5 u, bias = 0.1 n, running_mean = 0.2 n, running_var = 0.5 + 1.5 u (u uniform
+    in [0, 1), n standard normal), num_batches_tracked = 0.  shapes: {key: (shape, dtype)} (default: the module's own)."""
+    if shapes is None:
+        from .jdc import JDCNet
+        shapes = {k: (tuple(v.shape), v.dtype) for k, v in JDCNet(num_class=1, seq_len=192).state_dict().items()}
+    bn = {k[: -len("running_mean")] for k in shapes if k.endswith(".running_mean")}
+    sd = {}
+    for k, (shp, dtype) in shapes.items():
+        stem, leaf = k.rsplit(".", 1)
+        if stem + "." not in bn:
+            sd[k] = synth_tensor("jdc." + k, shp, seed, dtype)
+            continue
+        g = _rng("jdc." + k, seed)
+        n = int(np.prod(shp)) if shp else 1
+        if leaf == "num_batches_tracked":
+            sd[k] = torch.zeros(tuple(shp), dtype=dtype)
+            continue
+        v = {"weight": lambda: 0.75 + 0.5 * g.random(n), "bias": lambda: 0.1 * g.standard_normal(n),
+             "running_mean": lambda: 0.2 * g.standard_normal(n), "running_var": lambda: 0.5 + 1.5 * g.random(n)}[leaf]()
+        sd[k] = torch.from_numpy(np.asarray(v, dtype=np.float64).reshape(tuple(shp))).to(dtype)
+    return sd

@@ -742,6 +742,40 @@ int fac_resample(const fac_resample_desc* d, fac_stream_t stream);
  * (a span too long for LDS: extreme ratios); -1 on error.  out4 (or NULL) = {outputs per tile, threads, LDS bytes, grid x}. */
 int fac_resample_form(const fac_resample_desc* d, int32_t* out4);
 
+/* ------------------------------------------------------------------------------------------
+ * Pitch: the glue of the JDC F0 extractor (modules/JDC/model.py) and the predictor heads' targets (train.py:215-256).
+ * The extractor's 3 x 3 Conv2ds run on fac_conv1d_fwd over the row-concatenated layout of the spectrogram discriminator
+ * (see fac_spec_to_cat) at stride 1: every channel is one signal of rows * P floats, rows = B * (T + 1), row b * (T + 1) + t
+ * holds the W valid frequency bins of frame t then zeros up to the pitch P, row t = T of every clip is all zero; the conv is
+ * K = 9, K1 = 3, dilation2 = P, pad_left = P + 1, zero padding.
+ *   jdc_affine_lrelu_pool  y[c, r, j] = max_{i < pool} lrelu(scale[c] * x[c, r, j * pool + i] + shift[c]), j < W_in / pool (the
+ *                          floor drops trailing bins like MaxPool2d): eval BatchNorm (scale = gamma / sqrt(var + eps), shift =
+ *                          beta - mean * scale, both NULL: identity) -> LeakyReLU -> MaxPool along frequency.  x (C, rows, P_in)
+ *                          is a conv output: only valid columns of valid rows enter the result; y (C, rows, P_out) with
+ *                          P_out * pool == P_in gets exact zeros in every gap column and separator row (row % rows_per_group ==
+ *                          rows_per_group - 1).  The maximum starts from the first element.  pool = 1: no pooling.
+ *   jdc_layout_in          mel (B, 1, W, T) -> the stage-0 signal (1, B * (T + 1) * P)
+ *   jdc_to_time_major      stage signal (C channels of valid width W) -> LSTM input (C * W, T, BP), feature c * W + w (the
+ *                          reference's permute(0, 2, 1, 3).view(-1, T, C * W)), batch padding zero; reverse: time flipped
+ *   jdc_to_nchw            stage signal -> (B, C, T, W), or (B, C, W, T) with transposed != 0
+ *   jdc_head               out[b, t] = |w . [h_fwd[:, t, b] | h_bwd[:, T - 1 - t, b]] + bias[0]|: h_fwd, h_bwd (H, T, BP) the two
+ *                          directions' outputs (the backward one on flipped time), w (2H), out (B, T)
+ *   f0_normalize           train.py:224-256, one workgroup per clip, fixed-order sums: voiced = f0 > 5; l = log2(f0) over the
+ *                          voiced frames, out = (l - mean) / std (unbiased) there and -10 on unvoiced frames; any NaN / inf
+ *                          result becomes -10 (one voiced frame, all voiced frames equal); mean_out (B) or NULL: the per-clip
+ *                          mean of l, 0 without a voiced frame
+ *   mel_log_norm           modules/commons.py:176-181 with its defaults: out[b, t] = log(sqrt(sum_m exp(4 mel[b, m, t] - 4)^2))
+ * ---------------------------------------------------------------------------------------- */
+int fac_jdc_affine_lrelu_pool(const float* x, const float* scale, const float* shift, float* y, int C, int rows,
+                              int rows_per_group, int W_in, int P_in, int pool, int P_out, float slope, fac_stream_t stream);
+int fac_jdc_layout_in(const float* mel, float* out, int B, int W, int T, int P, fac_stream_t stream);
+int fac_jdc_to_time_major(const float* x, float* xT, int B, int C, int T, int W, int P, int BP, int reverse, fac_stream_t stream);
+int fac_jdc_to_nchw(const float* x, float* out, int B, int C, int T, int W, int P, int transposed, fac_stream_t stream);
+int fac_jdc_head(const float* h_fwd, const float* h_bwd, const float* w, const float* bias, float* out, int B, int T, int H, int BP,
+                 fac_stream_t stream);
+int fac_f0_normalize(const float* f0, float* out, float* mean_out, int B, int T, fac_stream_t stream);
+int fac_mel_log_norm(const float* mel, float* out, int B, int n_mels, int T, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
