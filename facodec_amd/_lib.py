@@ -95,6 +95,7 @@ SIGNATURES = {
     "fac_conv1d_bwd_weight_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "fac_conv1d_bwd_weight": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fac_conv1d_bwd_weight_split_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "fac_conv1d_bwd_weight_split_form": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "fac_conv1d_bwd_weight_k1_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "fac_conv1d_bwd_weight_k1_ws_bytes_for": (_i64, [_p, _p, _i, _i, _i, _i]),
     "fac_conv1d_bwd_weight_taps_tx": (_i64, [_i, _i, _i, _i, _i]),

@@ -1025,24 +1025,104 @@ static void ws_launch(const WsArgs& a, dim3 grid, size_t lds, hipStream_t stream
 
 static long long ws_align(long long v) { return (v + 255) & ~255ll; }
 
+// FAC_WGRAD_NARROW=0 (a child process of tests/test_wgrad_split.py): the 64 x 64 layout on duplicate rows, the bit-identity reference
+static bool wgrad_narrow_on() {
+  static const bool on = !(getenv("FAC_WGRAD_NARROW") && getenv("FAC_WGRAD_NARROW")[0] == '0');
+  return on;
+}
+
+// Everything the split entry decides from the shape, in one host function: fac_conv1d_bwd_weight_split_ws_bytes,
+// fac_conv1d_bwd_weight_split_form and the launch all read this plan, so a query cannot drift from the launch.
+enum WgradSplitKernel {      // the values fac_conv1d_bwd_weight_split_form reports (include/facodec_hip.h)
+  WSK_KMAJOR = 0, WSK_KMAJOR_KSPLIT = 1, WSK_PLANES_10_3 = 2, WSK_PLANES_14_3 = 3, WSK_PLANES_19_2 = 4
+};
+
+struct WgradSplitPlan {
+  int kernel;                // WgradSplitKernel
+  int S;                     // (b, t) slices
+  int tiles_per_slice, last_slice_tiles;
+  bool xcd_order;            // k-major: workgroups numbered so that each XCD works on whole slices
+  int row_tiles, narrow_row_tiles;      // 128-row tiles of dW; those with <= 96 real rows on the column-split wave layouts
+  bool db_fused;             // a requested bias gradient rides on the dy split pass
+  long long part_bytes;      // aligned size of the partial sums at the head of the workspace
+  long long need_bytes;      // what the launch touches
+  long long ws_bytes;        // what the query reports (the row sums of the fused bias gradient included)
+  WkArgs k;                  // k-major kernels
+  WsArgs a;                  // planes kernels
+  size_t lds;
+};
+
+// Returns 0 and fills *p when the shape runs on the split entry.
+static int wgrad_split_plan(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride, int dilation, int K1, int dilation2,
+                            bool want_db, WgradSplitPlan* p) {
+  p->row_tiles = (C_out + 127) / 128;
+  p->narrow_row_tiles = 0;
+  p->xcd_order = false;
+  p->db_fused = false;
+  p->lds = 0;
+  int S;
+  if (wk_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &p->k, &S) == 0) {
+    WkArgs& k = p->k;
+    p->S = S;
+    p->tiles_per_slice = k.tiles_per_split;
+    p->last_slice_tiles = (int)((long long)B * k.n_tt - (long long)(S - 1) * k.tiles_per_split);
+    p->part_bytes = ws_align((long long)S * C_out * k.NBk * 32 * 4);
+    p->ws_bytes = p->need_bytes = p->part_bytes + ws_align(3 * k.a_plane_bytes) + ws_align(3 * k.b_plane_bytes) +
+                                  ws_align((long long)B * C_out * ((k.UA + 2047) / 2048) * 4);
+    const long long gx = (C_out + 127) / 128, gy = (k.NBk + 3) / 4;
+    // Measured policy (profiles/r05_wgrad_xcd_ksplit.log, same box, B = 16 training shapes):
+    //  * XCD-aware order when the launch has at least 5 (b, t) slices: +4 .. +20 % on the ResidualUnit / strided / transposed
+    //    layers (each XCD then works on whole slices); with 2 - 4 slices (LSTM input projections, the 1024 -> 1536 conv at
+    //    T = 160) an XCD gets a fraction of a slice and the plain order measured 3 - 9 % faster;
+    //  * k-split wave layout for the k = 7 stride-1 layers whose slice is at most one round of workgroups: +2 .. +5 % there,
+    //    -2 .. -8 % on 1-tap / strided / wide layers (their loops are short: the end-of-loop exchange shows).
+    p->xcd_order = S >= 5;
+    const bool ksplit = k.K == 7 && k.K2 == 1 && stride == 1 && gx * gy <= 256 && S >= 4;
+    p->kernel = ksplit ? WSK_KMAJOR_KSPLIT : WSK_KMAJOR;
+    k.narrow_rows = wgrad_narrow_on() ? 3 : 0;      // bit 0: column-split layouts; bit 1: their duplicate rows are not staged
+    const int last_rows = C_out - (p->row_tiles - 1) * 128;
+    p->narrow_row_tiles = (k.narrow_rows && last_rows <= 96) ? 1 : 0;          // only the last row tile can be partial
+    k.gx = (int)gx; k.gy = (int)gy; k.gz = S; k.per_xcd = 0;
+    p->db_fused = want_db && (long long)B * C_out <= 65535;
+    return 0;
+  }
+  WsArgs& a = p->a;
+  if (ws_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &a, &S, &p->lds)) return -1;
+  p->S = S;
+  p->tiles_per_slice = a.tiles_per_split;
+  p->last_slice_tiles = (int)((long long)B * a.n_tt - (long long)(S - 1) * a.tiles_per_split);
+  p->part_bytes = ws_align((long long)S * C_out * C_in * K * 4);
+  p->need_bytes = p->part_bytes + ws_align(3 * a.a_plane_bytes) + ws_align(3 * a.b_plane_bytes);
+  p->ws_bytes = p->need_bytes + ws_align((long long)B * C_out * ((a.UA + 2047) / 2048) * 4);
+  a.B = B; a.C_in = C_in * a.K2; a.C_out = C_out; a.K = K / a.K2; a.stride = stride; a.dil = dilation;
+  const int nb8 = (a.NCP * 3 * a.R * a.nq + 255) / 256;          // 8-byte B pieces per staging lane and stage
+  p->kernel = nb8 <= 10 ? WSK_PLANES_10_3 : (nb8 <= 14 ? WSK_PLANES_14_3 : WSK_PLANES_19_2);
+  return 0;
+}
+
 }  // namespace fac
 
-// workspace = [partials | dy planes | x planes]
+// workspace = [partials | dy planes | x planes | row sums of the fused bias gradient]
 extern "C" int64_t fac_conv1d_bwd_weight_split_ws_bytes(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride,
                                                         int dilation, int K1, int dilation2) {
-  {
-    fac::WkArgs k;
-    int S;
-    if (fac::wk_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &k, &S) == 0)
-      return fac::ws_align((int64_t)S * C_out * k.NBk * 32 * 4) + fac::ws_align(3 * k.a_plane_bytes) + fac::ws_align(3 * k.b_plane_bytes) +
-             fac::ws_align((int64_t)B * C_out * ((k.UA + 2047) / 2048) * 4);
-  }
-  fac::WsArgs a;
-  int S;
-  size_t lds;
-  if (fac::ws_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &a, &S, &lds)) return -1;
-  return fac::ws_align((int64_t)S * C_out * C_in * K * 4) + fac::ws_align(3 * a.a_plane_bytes) + fac::ws_align(3 * a.b_plane_bytes) +
-         fac::ws_align((int64_t)B * C_out * ((a.UA + 2047) / 2048) * 4);
+  fac::WgradSplitPlan p;
+  if (fac::wgrad_split_plan(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, false, &p)) return -1;
+  return p.ws_bytes;
+}
+
+extern "C" int fac_conv1d_bwd_weight_split_form(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride, int dilation, int K1,
+                                                int dilation2, int want_db, int* form) {
+  fac::WgradSplitPlan p;
+  if (form == nullptr || fac::wgrad_split_plan(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, want_db != 0, &p)) return -1;
+  form[0] = p.kernel;
+  form[1] = p.S;
+  form[2] = p.tiles_per_slice;
+  form[3] = p.last_slice_tiles;
+  form[4] = p.xcd_order ? 1 : 0;
+  form[5] = p.row_tiles;
+  form[6] = p.narrow_row_tiles;
+  form[7] = p.db_fused ? 1 : 0;
+  return 0;
 }
 
 static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int B, int C_in,
@@ -1051,9 +1131,8 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
 
 extern "C" int fac_conv1d_bwd_weight_split_db_ok(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride, int dilation, int K1,
                                                  int dilation2) {
-  fac::WkArgs k;
-  int S;
-  return fac::wk_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &k, &S) == 0 && (long long)B * C_out <= 65535;
+  fac::WgradSplitPlan p;
+  return fac::wgrad_split_plan(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, true, &p) == 0 && p.db_fused;
 }
 
 extern "C" int fac_conv1d_bwd_weight_split(const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes, int B,
@@ -1077,88 +1156,66 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
   FAC_REQUIRE(x && dy && dw && ws && B > 0 && C_in > 0 && C_out > 0 && T_in > 0 && T_out > 0 && K > 0 && stride > 0 &&
                   dilation > 0 && pad_left >= 0,
               "conv1d_bwd_weight_split: bad arguments");
-  {
-    WkArgs k;
-    int S;
-    if (wk_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &k, &S) == 0) {
-      const long long part_bytes = ws_align((long long)S * C_out * k.NBk * 32 * 4);
-      FAC_REQUIRE(ws_bytes >= part_bytes + ws_align(3 * k.a_plane_bytes) + ws_align(3 * k.b_plane_bytes) +
-                                  ws_align((long long)B * C_out * ((k.UA + 2047) / 2048) * 4),
-                  "conv1d_bwd_weight_split: workspace too small");
-      unsigned char* wsb = reinterpret_cast<unsigned char*>(ws);
-      k.part = reinterpret_cast<float*>(ws);
-      unsigned char* ap = wsb + part_bytes;
-      unsigned char* bp = ap + ws_align(3 * k.a_plane_bytes);
-      k.ap = ap; k.bp = bp;
-      const hipStream_t st = (hipStream_t)stream;
-      const int K2 = k.K2, K1e = k.K;
-      long long last = (long long)(T_out - 1) * stride + (long long)(K2 - 1) * (K2 > 1 ? dilation2 : 0) + (long long)(K1e - 1) * dilation - pad_left;
-      const int pad_right = last >= T_in ? (int)(last - T_in + 1) : 0;
-      const int max_pad = pad_left > pad_right ? pad_left : pad_right;
-      const int T_ext = T_in > max_pad ? T_in : max_pad + 1;
-      const int T_pad = (int)(pad_left + (last + 1 > T_in ? last + 1 : T_in));
-      const long long na = (long long)B * C_out * (k.UA / 8), nb = (long long)B * C_in * stride * (k.UB / 8);
-      const int ga = (int)((na + 255) / 256 < 65535 * 16 ? (na + 255) / 256 : 65535 * 16);
-      const int gb = (int)((nb + 255) / 256 < 65535 * 16 ? (nb + 255) / 256 : 65535 * 16);
-      if (db != nullptr && (long long)B * C_out <= 65535) {
-        const int n_chunks = (k.UA + 2047) / 2048;
-        float* rs = reinterpret_cast<float*>(bp + ws_align(3 * k.b_plane_bytes));
-        // short rows (the 160-frame layers: 20 pieces of 8 steps per row) get one wave per row instead of 256 threads of which 236 idle
-        hipLaunchKernelGGL(split_planes_rowsum_kernel, dim3(n_chunks, B * C_out), dim3(k.UA <= 512 ? 64 : 256), 0, st, dy, ap, rs, T_out, k.UA,
-                           n_chunks, k.a_plane_bytes);
-        hipLaunchKernelGGL(bias_from_rowsums_kernel, dim3((C_out + 255) / 256), dim3(256), 0, st, rs, db, B, C_out, n_chunks);
-        db = nullptr;
-      } else {
-        hipLaunchKernelGGL(split_planes_kernel, dim3(ga), dim3(256), 0, st, dy, ap, (long long)B * C_out, T_out, T_out, T_out, 1, k.UA, 0,
-                           FAC_PAD_ZERO, k.a_plane_bytes);
-      }
-      FAC_REQUIRE(db == nullptr, "conv1d_bwd_weight_split_db: too many rows for the fused bias gradient (B * C_out > 65535)");
-      hipLaunchKernelGGL(split_planes_kernel, dim3(gb), dim3(256), 0, st, x, bp, (long long)B * C_in, T_in, T_ext, T_pad, stride, k.UB,
-                         pad_left, pad_mode, k.b_plane_bytes);
-      allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<false>>();
-      allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<true>>();
-      dim3 grid((C_out + 127) / 128, (k.NBk + 3) / 4, S);
-      // Measured policy (profiles/r05_wgrad_xcd_ksplit.log, same box, B = 16 training shapes):
-      //  * XCD-aware order when the launch has at least 5 (b, t) slices: +4 .. +20 % on the ResidualUnit / strided / transposed
-      //    layers (each XCD then works on whole slices); with 2 - 4 slices (LSTM input projections, the 1024 -> 1536 conv at
-      //    T = 160) an XCD gets a fraction of a slice and the plain order measured 3 - 9 % faster;
-      //  * k-split wave layout for the k = 7 stride-1 layers whose slice is at most one round of workgroups: +2 .. +5 % there,
-      //    -2 .. -8 % on 1-tap / strided / wide layers (their loops are short: the end-of-loop exchange shows).
-      const bool xcd_order = S >= 5;
-      const bool ksplit = k.K == 7 && k.K2 == 1 && stride == 1 && (long long)grid.x * grid.y <= 256 && S >= 4;
-      // FAC_WGRAD_NARROW=0 (a child process of tests/test_wgrad_split.py): the 64 x 64 layout on duplicate rows, the bit-identity reference
-      static const bool narrow_on = !(getenv("FAC_WGRAD_NARROW") && getenv("FAC_WGRAD_NARROW")[0] == '0');
-      k.narrow_rows = narrow_on ? 3 : 0;      // bit 0: column-split layouts; bit 1: their duplicate rows are not staged
-      k.gx = (int)grid.x; k.gy = (int)grid.y; k.gz = (int)grid.z; k.per_xcd = 0;
-      if (xcd_order) {
-        const XcdGrid xg = xcd_padded_grid((long long)grid.x * grid.y * grid.z);
-        k.per_xcd = xg.per_xcd;
-        grid = dim3(xg.grid, 1, 1);
-      }
-      if (ksplit) hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<true>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
-      else hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<false>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
-      const long long n = (long long)C_out * k.NBk * 32;
-      const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
-      hipLaunchKernelGGL(wgrad_kmajor_reduce_kernel, dim3(blocks), dim3(256), 0, st, k.part, dw, S, C_out, k.NBk, k.K, k.CV);
-      return check_launch("conv1d_bwd_weight_split(k-major)");
-    }
-  }
-  FAC_REQUIRE(db == nullptr, "conv1d_bwd_weight_split_db: the fused bias gradient needs the k-major kernel's shapes (>= 16 input channels)");
-  WsArgs a;
-  int S;
-  size_t lds;
-  FAC_REQUIRE(ws_geometry(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, &a, &S, &lds) == 0,
+  WgradSplitPlan plan;
+  FAC_REQUIRE(wgrad_split_plan(B, C_in, T_in, C_out, T_out, K, stride, dilation, K1, dilation2, db != nullptr, &plan) == 0,
               "conv1d_bwd_weight_split: shape not supported (K=%d stride=%d dilation=%d)", K, stride, dilation);
-  const long long part_bytes = ws_align((long long)S * C_out * C_in * K * 4);
-  FAC_REQUIRE(ws_bytes >= part_bytes + ws_align(3 * a.a_plane_bytes) + ws_align(3 * a.b_plane_bytes),
-              "conv1d_bwd_weight_split: workspace too small");
+  const bool kmajor = plan.kernel == WSK_KMAJOR || plan.kernel == WSK_KMAJOR_KSPLIT;
+  FAC_REQUIRE(db == nullptr || plan.db_fused || !kmajor,
+              "conv1d_bwd_weight_split_db: too many rows for the fused bias gradient (B * C_out > 65535)");
+  FAC_REQUIRE(db == nullptr || plan.db_fused,
+              "conv1d_bwd_weight_split_db: the fused bias gradient needs the k-major kernel's shapes (>= 16 input channels)");
+  FAC_REQUIRE(ws_bytes >= plan.need_bytes, "conv1d_bwd_weight_split: workspace too small");
+  const int S = plan.S;
+  const hipStream_t st = (hipStream_t)stream;
   unsigned char* wsb = reinterpret_cast<unsigned char*>(ws);
+  if (kmajor) {
+    WkArgs& k = plan.k;
+    k.part = reinterpret_cast<float*>(ws);
+    unsigned char* ap = wsb + plan.part_bytes;
+    unsigned char* bp = ap + ws_align(3 * k.a_plane_bytes);
+    k.ap = ap; k.bp = bp;
+    const int K2 = k.K2, K1e = k.K;
+    long long last = (long long)(T_out - 1) * stride + (long long)(K2 - 1) * (K2 > 1 ? dilation2 : 0) + (long long)(K1e - 1) * dilation - pad_left;
+    const int pad_right = last >= T_in ? (int)(last - T_in + 1) : 0;
+    const int max_pad = pad_left > pad_right ? pad_left : pad_right;
+    const int T_ext = T_in > max_pad ? T_in : max_pad + 1;
+    const int T_pad = (int)(pad_left + (last + 1 > T_in ? last + 1 : T_in));
+    const long long na = (long long)B * C_out * (k.UA / 8), nb = (long long)B * C_in * stride * (k.UB / 8);
+    const int ga = (int)((na + 255) / 256 < 65535 * 16 ? (na + 255) / 256 : 65535 * 16);
+    const int gb = (int)((nb + 255) / 256 < 65535 * 16 ? (nb + 255) / 256 : 65535 * 16);
+    if (plan.db_fused) {
+      const int n_chunks = (k.UA + 2047) / 2048;
+      float* rs = reinterpret_cast<float*>(bp + ws_align(3 * k.b_plane_bytes));
+      // short rows (the 160-frame layers: 20 pieces of 8 steps per row) get one wave per row instead of 256 threads of which 236 idle
+      hipLaunchKernelGGL(split_planes_rowsum_kernel, dim3(n_chunks, B * C_out), dim3(k.UA <= 512 ? 64 : 256), 0, st, dy, ap, rs, T_out, k.UA,
+                         n_chunks, k.a_plane_bytes);
+      hipLaunchKernelGGL(bias_from_rowsums_kernel, dim3((C_out + 255) / 256), dim3(256), 0, st, rs, db, B, C_out, n_chunks);
+    } else {
+      hipLaunchKernelGGL(split_planes_kernel, dim3(ga), dim3(256), 0, st, dy, ap, (long long)B * C_out, T_out, T_out, T_out, 1, k.UA, 0,
+                         FAC_PAD_ZERO, k.a_plane_bytes);
+    }
+    hipLaunchKernelGGL(split_planes_kernel, dim3(gb), dim3(256), 0, st, x, bp, (long long)B * C_in, T_in, T_ext, T_pad, stride, k.UB,
+                       pad_left, pad_mode, k.b_plane_bytes);
+    allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<false>>();
+    allow_dynamic_lds<conv1d_wgrad_kmajor_kernel<true>>();
+    dim3 grid(k.gx, k.gy, S);
+    if (plan.xcd_order) {
+      const XcdGrid xg = xcd_padded_grid((long long)grid.x * grid.y * grid.z);
+      k.per_xcd = xg.per_xcd;
+      grid = dim3(xg.grid, 1, 1);
+    }
+    if (plan.kernel == WSK_KMAJOR_KSPLIT) hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<true>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
+    else hipLaunchKernelGGL(conv1d_wgrad_kmajor_kernel<false>, grid, dim3(512), (size_t)WK_NST * WK_STAGE, st, k);
+    const long long n = (long long)C_out * k.NBk * 32;
+    const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
+    hipLaunchKernelGGL(wgrad_kmajor_reduce_kernel, dim3(blocks), dim3(256), 0, st, k.part, dw, S, C_out, k.NBk, k.K, k.CV);
+    return check_launch("conv1d_bwd_weight_split(k-major)");
+  }
+  WsArgs& a = plan.a;
   a.part = reinterpret_cast<float*>(ws);
-  unsigned char* ap = wsb + part_bytes;
+  unsigned char* ap = wsb + plan.part_bytes;
   unsigned char* bp = ap + ws_align(3 * a.a_plane_bytes);
   a.ap = ap; a.bp = bp;
-  a.B = B; a.C_in = C_in * a.K2; a.C_out = C_out; a.K = K / a.K2; a.stride = stride; a.dil = dilation;
-  const hipStream_t st = (hipStream_t)stream;
   int T_ext;
   long long last = (long long)(T_out - 1) * stride + (long long)(a.K2 - 1) * (a.K2 > 1 ? dilation2 : 0) + (long long)(a.K - 1) * dilation - pad_left;
   {
@@ -1177,10 +1234,9 @@ static int bwd_weight_split_impl(const float* x, const float* dy, float* dw, flo
                        pad_left, pad_mode, a.b_plane_bytes);
   }
   dim3 grid((C_out + WS_CO - 1) / WS_CO, (a.C_in + a.cit - 1) / a.cit, S);
-  const int nb8 = (a.NCP * 3 * a.R * a.nq + 255) / 256;
-  if (nb8 <= 10) ws_launch<10, 3>(a, grid, lds, st);
-  else if (nb8 <= 14) ws_launch<14, 3>(a, grid, lds, st);
-  else ws_launch<19, 2>(a, grid, lds, st);
+  if (plan.kernel == WSK_PLANES_10_3) ws_launch<10, 3>(a, grid, plan.lds, st);
+  else if (plan.kernel == WSK_PLANES_14_3) ws_launch<14, 3>(a, grid, plan.lds, st);
+  else ws_launch<19, 2>(a, grid, plan.lds, st);
   const long long n = (long long)C_out * C_in * K;
   const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
   hipLaunchKernelGGL(wgrad_split_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.part, dw, S, n);

@@ -5,6 +5,7 @@ happens in Python / ATen here -- every op below is one or more kernels of libfac
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import torch
 
@@ -1528,21 +1529,45 @@ def _bwd_weight_launch(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilati
     if _FLOPS is not None:
         _FLOPS.add("wgrad", flops)
     if _PROFILE is None:
-        return _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1, dilation2, db)
+        return _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1, dilation2, db)[0]
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    r = _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1, dilation2, db)
+    r, entry = _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1, dilation2, db)
     e1.record()
-    split = BF16_SPLIT and _lib.load().fac_conv1d_bwd_weight_split_ws_bytes(B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2) > 0
-    _PROFILE.records.append(("weight gradient: split_planes + conv1d_wgrad_split/kmajor + reduce (bf16x3 split)" if split
-                             else "weight gradient: conv1d_wgrad_kernel (fp32 MFMA) + reduce", flops, e0, e1))
+    _PROFILE.records.append((wgrad_profile_label(entry, B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2, db is not None),
+                             flops, e0, e1))
     return r
+
+
+WgradSplitForm = namedtuple("WgradSplitForm", "kernel slices tiles_per_slice last_slice_tiles xcd_order row_tiles narrow_row_tiles db_fused")
+WGRAD_SPLIT_KERNELS = ("kmajor", "kmajor_ksplit", "planes<10,3>", "planes<14,3>", "planes<19,2>")
+
+
+def wgrad_split_form(B, c_in, t_in, c_out, t_out, k, stride=1, dilation=1, k1=0, dilation2=0, want_db=False):
+    """What the split weight-gradient entry does for this shape (fac_conv1d_bwd_weight_split_form: host only, the launch reads the
+    same plan), or None where its workspace query answers -1."""
+    out = (C.c_int * 8)()
+    if _lib.load().fac_conv1d_bwd_weight_split_form(B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2, int(want_db), out) != 0:
+        return None
+    return WgradSplitForm(WGRAD_SPLIT_KERNELS[out[0]], out[1], out[2], out[3], bool(out[4]), out[5], out[6], bool(out[7]))
+
+
+def wgrad_profile_label(entry, B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2, want_db):
+    """The profile record's name for the C entry _bwd_weight_launch_inner called; the split entry's kernel form appended."""
+    if entry == "fac_conv1d_bwd_weight_k1":
+        return "weight gradient: wgrad_k1_kernel (k = 1 streaming, fp32 MFMA) + reduce"
+    if entry == "fac_conv1d_bwd_weight_taps":
+        return "weight gradient: wgrad_k1_kernel (virtual-row taps, fp32 MFMA) + reduce"
+    if entry == "fac_conv1d_bwd_weight":
+        return "weight gradient: conv1d_wgrad_kernel (fp32 MFMA) + reduce"
+    form = wgrad_split_form(B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2, want_db)
+    return "weight gradient: split_planes + conv1d_wgrad_split/%s + reduce (bf16x3 split)" % form.kernel
 
 
 def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, dilation, pad_left, pad_mode, k1=0, dilation2=0, db=None):
     """dW on the bf16 matrix pipe with fp32-grade splitting (conv1d_wgrad_split.hip) when the shape qualifies and
     BF16_SPLIT is on, else on the fp32 MFMA kernel.  db: optional (C_out) buffer for the bias gradient; returns True when the
-    launch filled it."""
+    launch filled it, and with it the name of the C entry called."""
     lib = _lib.load()
     if WGRAD_K1_STREAM and BF16_SPLIT and k == 1 and stride == 1 and pad_left == 0 and t_in == t_out and k1 in (0, 1):
         # few channels, long signal (the ResidualUnit tails at C = 64 / 96 / 192): both tensors once through the fp32 matrix pipe
@@ -1552,7 +1577,7 @@ def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, 
             ws = _wgrad_workspace(x.device, nb)
             _lib.check(lib.fac_conv1d_bwd_weight_k1(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nb, B, c_in, c_out, t_in, _stream()),
                        "fac_conv1d_bwd_weight_k1")
-            return db is not None
+            return db is not None, "fac_conv1d_bwd_weight_k1"
     if WGRAD_K1_STREAM and BF16_SPLIT and k > 1 and stride == 1 and c_in * k <= 64 and c_out in (32, 64) and t_out >= 4096:
         # first layers (1 -> 64 k = 7 of the encoder, 2 -> 32 (3, 9) of the multi-resolution discriminator): the C_in * K columns of dW
         # are shifted views of one or two input rows -- the same kernel with virtual rows (fac_conv1d_bwd_weight_taps) on the padded input
@@ -1572,7 +1597,7 @@ def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, 
             ws = _wgrad_workspace(x.device, nb)
             _lib.check(lib.fac_conv1d_bwd_weight_taps(_ptr(xp), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nb, B, c_in, xp.shape[-1], c_out,
                                                       t_out, k, kk1, dilation, d2, _stream()), "fac_conv1d_bwd_weight_taps")
-            return db is not None
+            return db is not None, "fac_conv1d_bwd_weight_taps"
     nbytes = lib.fac_conv1d_bwd_weight_split_ws_bytes(B, c_in, t_in, c_out, t_out, k, stride, dilation, k1, dilation2) if BF16_SPLIT else -1
     if nbytes > WGRAD_WS_CAP:       # beyond the workspace budget: the fp32 kernel (no operand planes) takes the layer
         nbytes = -1
@@ -1582,17 +1607,17 @@ def _bwd_weight_launch_inner(x, dy, dw, B, c_in, t_in, c_out, t_out, k, stride, 
             _lib.check(lib.fac_conv1d_bwd_weight_split_db(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nbytes, B, c_in, t_in, c_out,
                                                           t_out, k, stride, dilation, pad_left, pad_mode, k1, dilation2, _stream()),
                        "fac_conv1d_bwd_weight_split_db")
-            return True
+            return True, "fac_conv1d_bwd_weight_split_db"
         _lib.check(lib.fac_conv1d_bwd_weight_split(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), nbytes, B, c_in, t_in, c_out, t_out, k,
                                                    stride, dilation, pad_left, pad_mode, k1, dilation2, _stream()),
                    "fac_conv1d_bwd_weight_split")
-        return False
+        return False, "fac_conv1d_bwd_weight_split"
     kk1 = k1 if 0 < k1 < k else k                      # the fp32 kernel sees k / kk1 virtual channels per input channel
     nbytes = lib.fac_conv1d_bwd_weight_ws_bytes(B, c_in * (k // kk1), c_out, t_out, kk1)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     _lib.check(lib.fac_conv1d_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), nbytes, B, c_in, t_in, c_out, t_out, k,
                                          stride, dilation, pad_left, pad_mode, k1, dilation2, _stream()), "fac_conv1d_bwd_weight")
-    return False
+    return False, "fac_conv1d_bwd_weight"
 
 
 def weight_norm_bwd(v, g, dw):

@@ -520,6 +520,15 @@ int fac_conv1d_bwd_weight_taps(const float* xpad, const float* dy, float* dw, fl
  * holds the pre-split bf16 planes of both operands. */
 int64_t fac_conv1d_bwd_weight_split_ws_bytes(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride, int dilation,
                                              int K1, int dilation2);
+/* What fac_conv1d_bwd_weight_split / _split_db will do for this shape, from the host function the launch itself reads (no device
+ * call).  Returns 0 and fills form[0..7], or -1 where the workspace query returns -1.  want_db: a bias gradient is requested.
+ *   form[0] kernel: 0 kmajor, 1 kmajor_ksplit (k = 7 wave layout), 2 planes<10,3>, 3 planes<14,3>, 4 planes<19,2>
+ *   form[1] slices S of the (b, t) range      form[2] 32-step tiles per slice      form[3] tiles of the last slice
+ *   form[4] XCD-aware workgroup order         form[5] 128-row tiles of dW
+ *   form[6] row tiles with <= 96 real rows on the column-split wave layouts (0 with FAC_WGRAD_NARROW=0 and on the planes kernels)
+ *   form[7] the requested bias gradient is folded into the dy split pass (fac_conv1d_bwd_weight_split_db_ok) */
+int fac_conv1d_bwd_weight_split_form(int B, int C_in, int T_in, int C_out, int T_out, int K, int stride, int dilation, int K1,
+                                     int dilation2, int want_db, int* form);
 int fac_conv1d_bwd_weight_split(const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes, int B, int C_in, int T_in,
                                 int C_out, int T_out, int K, int stride, int dilation, int pad_left, int pad_mode, int K1,
                                 int dilation2, fac_stream_t stream);
