@@ -193,6 +193,9 @@ SIGNATURES = {
     "fac_mul_mask": (_i, [_p, _p, _i, _i, _i, _p]),
     "fac_wn_res_skip": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fac_attention_stream": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fac_attention_route": (_i, [_i, _i]),
+    "fac_attention_stream_tile": (_i, [_i]),
     "fac_masked_mean": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_layernorm_c_affine": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_stft_frames": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -302,6 +302,115 @@ def reconstruct_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES, 
                         sample_rate=sample_rate, quality=quality)
 
 
+# ------------------------------------------------------------------------------------ recordings of any length
+LONG_CHUNK_SECONDS = 30      # default chunk of the *_long calls: the fastest of 2 / 10 / 30 s measured
+
+
+def plan_long(T, chunk_samples, hop=300):
+    """Chunk plan of the *_long calls for a T-sample recording: -> (cropped length 300 (T // 300), [(start, end)] or None).
+    None: the cropped signal fits one chunk and goes through the whole-clip path.  Otherwise the first chunk is exactly
+    chunk_samples (ChunkedCodec.prime), the others up to chunk_samples (push), the last one what is left (a multiple of 300)."""
+    chunk_samples = int(chunk_samples)
+    if chunk_samples % 2400 or chunk_samples < 4800:
+        raise ValueError(f"a chunk must be a multiple of 2400 samples and at least 4800, got {chunk_samples}")
+    Tc = hop * (int(T) // hop)
+    if Tc <= chunk_samples:
+        return Tc, None
+    return Tc, [(s, min(s + chunk_samples, Tc)) for s in range(0, Tc, chunk_samples)]
+
+
+def _chunk_samples(chunk_seconds):
+    n = chunk_seconds * MODEL_RATE
+    if abs(n - round(n)) > 1e-6:                          # 0.2 s is 4800 samples, whatever 0.2 * 24000 rounds to
+        raise ValueError(f"chunk_seconds = {chunk_seconds} is no whole number of samples at {MODEL_RATE} Hz")
+    return int(round(n))
+
+
+def _long_wave(model, wave, what):
+    from .streaming import _first_non_causal
+    _need_gpu([wave], what)
+    if wave.dim() != 3 or wave.shape[1] != 1 or wave.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32 (B, 1, T), got {wave.dtype} {tuple(wave.shape)}")
+    bad = _first_non_causal(model, ("encoder", "decoder"), "model")
+    if bad is not None:
+        raise NotImplementedError(f"{bad} is not causal: the chunked calls need the causal configuration "
+                                  "(a chunk cannot wait for the samples to the right of it)")
+
+
+@torch.no_grad()
+def encode_long(model, wave, n_c=2, chunk_seconds=LONG_CHUNK_SECONDS, timbre=None, timbre_seconds=None):
+    """A recording of any length -> codes and timbre in the memory of one chunk (plus the frame-rate tensors of the timbre):
+
+        enc = encode_long(model, wave)                  # wave (B, 1, T) float32 on the GPU, 24 kHz, equal lengths
+        enc == dict(codes=[p (B, 1, F), c (B, n_c, F), r (B, 3, F)] int64, timbre=(B, 1024)),  F = T // 300
+
+    The signal is cropped to 300 F samples first; the codes are those of `model.encoder` -> `model.quantizer` on the cropped
+    signal, produced chunk_seconds at a time by streaming.ChunkedCodec (encode_only).  For T not a multiple of 300 the last four
+    prosody frames can therefore differ from the single-clip call on the uncropped signal, which reflects at the uncropped end.
+    timbre: taken as given (B, 1024), else FAquantizer.timbre_long over the whole recording, or over its first timbre_seconds.
+    The codes do not depend on the timbre.  A cropped signal of at most one chunk goes through the whole-clip calls."""
+    from .streaming import ChunkedCodec
+    _long_wave(model, wave, "wave")
+    Tc, plan = plan_long(wave.shape[-1], _chunk_samples(chunk_seconds), model.quantizer.hop_length)
+    if Tc < wave.shape[-1]:
+        wave = wave[:, :, :Tc]
+    q = model.quantizer
+    if plan is None:
+        wave = wave.contiguous()
+        out = q(model.encoder(wave), wave, n_c=n_c, return_codes=True)
+        own, codes = out[4], out[5]
+    else:
+        own = None
+        sess = ChunkedCodec(model, torch.zeros(wave.shape[0], q.in_dim, device=wave.device), n_c=n_c,
+                            chunk_samples=plan[0][1], encode_only=True)
+        parts = [sess.prime(wave[:, :, plan[0][0]:plan[0][1]])]
+        parts += [sess.push(wave[:, :, s:e]) for s, e in plan[1:]]
+        parts.append(sess.finish())
+        codes = [torch.cat([p["codes"][r] for p in parts if p["codes"] is not None], dim=-1) for r in range(3)]
+    if timbre is None:
+        if timbre_seconds is not None:
+            n = min(Tc, _chunk_samples(timbre_seconds))
+            timbre = q.timbre_long(wave[:, :, :n])
+        elif own is not None:
+            timbre = own
+        else:
+            timbre = q.timbre_long(wave)
+    return dict(codes=codes, timbre=timbre)
+
+
+@torch.no_grad()
+def decode_long(model, codes, timbre, chunk_seconds=LONG_CHUNK_SECONDS):
+    """Codes of any length + timbre -> (B, 1, 300 F), decode_codes within fp32 noise, chunk_seconds of frames at a time through
+    streaming.StreamingDecoder (no graphs).  At most one chunk of frames goes through decode_codes itself."""
+    from .streaming import StreamingDecoder, _first_non_causal
+    hop = model.quantizer.hop_length
+    chunk = _chunk_samples(chunk_seconds)
+    plan_long(chunk, chunk, hop)                                            # the chunk rule
+    bad = _first_non_causal(model, ("decoder",), "model")
+    if bad is not None:
+        raise NotImplementedError(f"{bad} is not causal: the chunked calls need the causal configuration")
+    model.quantizer._check_decode_inputs(codes, timbre)
+    F, k = codes[0].shape[-1], chunk // hop
+    if F <= k:
+        return decode_codes(model, codes, timbre)
+    rx = StreamingDecoder(model, timbre, use_graphs=False, max_frames=k)
+    if k < rx.min_prime:
+        raise ValueError(f"a chunk of {k} frames is below the decoder's first chunk of {rx.min_prime} frames")
+    out = torch.empty(codes[0].shape[0], 1, hop * F, device=timbre.device, dtype=torch.float32)
+    for f0 in range(0, F, k):
+        f1 = min(F, f0 + k)
+        part = [c[:, :, f0:f1] for c in codes]
+        out[:, :, hop * f0:hop * f1] = rx.prime(part) if f0 == 0 else rx.push(part)
+    return out
+
+
+@torch.no_grad()
+def reconstruct_long(model, wave, n_c=2, chunk_seconds=LONG_CHUNK_SECONDS, timbre=None, timbre_seconds=None):
+    """encode_long then decode_long: (B, 1, T) -> (B, 1, 300 (T // 300)); timbre: another speaker's for a timbre swap."""
+    enc = encode_long(model, wave, n_c=n_c, chunk_seconds=chunk_seconds, timbre=timbre, timbre_seconds=timbre_seconds)
+    return decode_long(model, enc["codes"], enc["timbre"], chunk_seconds=chunk_seconds)
+
+
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):
     """modules/commons.py:446-471: {'net': {key: state_dict}, ...}; strips DDP's 'module.' prefix."""
     state = torch.load(path, map_location="cpu")

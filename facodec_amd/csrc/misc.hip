@@ -730,11 +730,17 @@ extern "C" int fac_wn_res_skip(const float* rs, float* x, float* out, int B, int
   return check_launch("wn_res_skip");
 }
 
+// Which kernel fac_attention launches: attention_kernel while its queries (dk x 16) and its 16 x T score tile fit the LDS, the
+// running-max kernel of attention_stream.hip past that.  Shapes only; ops.attention_route and the tests ask this same function.
+extern "C" int fac_attention_route(int dk, int T) {
+  return ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float) <= FAC_LDS_MAX ? FAC_ATTN_LDS : FAC_ATTN_STREAM;
+}
+
 extern "C" int fac_attention(const float* q, const float* k, const float* v, const float* mask,
                              float* out, int B, int n_heads, int dk, int T, fac_stream_t stream) {
   FAC_REQUIRE(q && k && v && out && B > 0 && n_heads > 0 && dk > 0 && T > 0, "attention: bad arguments");
+  if (fac_attention_route(dk, T) == FAC_ATTN_STREAM) return fac_attention_stream(q, k, v, mask, out, B, n_heads, dk, T, stream);
   size_t lds = ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float);
-  FAC_REQUIRE(lds <= FAC_LDS_MAX, "attention: T=%d too long for the LDS score tile", T);
   const size_t lds_v = lds + (size_t)16 * (T + 1) * sizeof(float);       // + 16 rows of V per pass
   const int stage_v = lds_v <= FAC_LDS_MAX ? 1 : 0;
   if (stage_v) lds = lds_v;

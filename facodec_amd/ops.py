@@ -1186,12 +1186,32 @@ def wn_res_skip_(rs, x, out, last):
                "fac_wn_res_skip")
 
 
-def attention(q, k, v, mask, n_heads):
+def attention_route(dk, T):
+    """The kernel fac_attention launches for (dk, T), from the shapes alone (the C entry decides with this same function): "lds"
+    (16 queries x T scores in LDS, csrc/misc.hip) while (16 dk + 16 T) * 4 bytes fit 160 KiB, "stream" (running max and sum over
+    key tiles, csrc/attention_stream.hip: any T) past that."""
+    return ("lds", "stream")[_lib.load().fac_attention_route(int(dk), int(T))]
+
+
+def attention_stream_tiles():
+    """(queries per workgroup, keys per LDS tile) of the "stream" attention kernel."""
+    lib = _lib.load()
+    return lib.fac_attention_stream_tile(0), lib.fac_attention_stream_tile(1)
+
+
+def attention(q, k, v, mask, n_heads, kernel=None):
+    """kernel: None (attention_route decides), or "lds" / "stream" to force a route (tests, A/B runs; "lds" past its LDS limit is
+    an error)."""
+    if kernel not in (None, "lds", "stream"):
+        raise ValueError(f"attention: kernel={kernel!r} (None, 'lds' or 'stream')")
     q, k, v = _dev(q), _dev(k), _dev(v)
     B, c, T = q.shape
+    dk = c // n_heads
     out = torch.empty_like(q)
-    _lib.check(_lib.load().fac_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(out), B, n_heads, c // n_heads, T,
-                                         _stream()), "fac_attention")
+    if kernel == "lds" and attention_route(dk, T) != "lds":
+        raise _lib.FacodecHipError(f"attention: T={T} too long for the LDS score tile at dk={dk}")
+    name = "fac_attention_stream" if kernel == "stream" else "fac_attention"
+    _lib.check(getattr(_lib.load(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(out), B, n_heads, dk, T, _stream()), name)
     return out
 
 

@@ -407,6 +407,20 @@ def sequence_mask(length, max_length=None):
     return x.unsqueeze(0) < length.unsqueeze(1)
 
 
+def mel_chunk_plan(T, chunk_frames, hop=300, n_fft=2048):
+    """Chunks of the centred STFT of a T-sample signal, T // hop frames: -> [(f0, f1, s_lo, s_hi, pad)]: frames [f0, f1) are
+    ops.stft_frames of wave[s_lo:s_hi] with `pad` samples of reflect padding on the left.  Frame f reads the samples
+    [hop f - n_fft / 2, hop f + n_fft / 2): the slice is what the chunk's frames reach, cut at the signal's two ends, where --
+    and only where -- the call reflects (pad > 0 only with s_lo = 0; the right reflection only with s_hi = T)."""
+    half = n_fft // 2
+    plan = []
+    for f0 in range(0, T // hop, chunk_frames):
+        f1 = min(T // hop, f0 + chunk_frames)
+        lo, hi = hop * f0 - half, hop * (f1 - 1) + half
+        plan.append((f0, f1, max(lo, 0), min(hi, T), max(-lo, 0)))
+    return plan
+
+
 QUANT_STREAMS = int(os.environ.get("FAC_QUANT_STREAMS", "3"))     # concurrent chains of FAquantizer's eval forward (1 = serial)
 
 
@@ -584,6 +598,48 @@ class FAquantizer(nn.Module):
         ops.mask_tail_(outs, lens, hop)
         codes = [ops.mask_tail_(c, lens, hop) for c in (codes_p, codes_c, codes_r)]
         return outs, codes, timbre, frame_lens
+
+    @torch.no_grad()
+    def log_mel_chunked(self, wave, chunk_frames=4096):
+        """`to_mel(wave)` (B, 80, T // hop) with the STFT in chunks of `chunk_frames` frames: the (n_win, F) frame tensor and the
+        (2050, F) spectrum exist per chunk only.  A chunk is framed from the samples its frames reach, so the reflect padding
+        applies at the two ends of the signal and nowhere else (the explicit-pad call of streaming._QuantizerStream._mel)."""
+        fe = self.to_mel
+        w = wave.reshape(wave.shape[0], wave.shape[-1])
+        B, T = w.shape
+        F = T // fe.hop
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError(f"chunk_frames = {chunk_frames}")
+        if T <= fe.n_fft // 2:
+            raise ValueError(f"{T} samples: the log-mel front-end reflects n_fft / 2 = {fe.n_fft // 2} samples at either end")
+        off = fe._consts(w.device)[2]
+        mel = torch.empty(B, fe.n_mels, F, device=w.device, dtype=torch.float32)
+        for f0, f1, s_lo, s_hi, pad in mel_chunk_plan(T, chunk_frames, fe.hop, fe.n_fft):
+            view = w[:, s_lo:s_hi].contiguous()
+            mel[:, :, f0:f1] = fe._from_frames(ops.stft_frames(view, fe.win, f1 - f0, fe.hop, pad, off))
+        return mel
+
+    @torch.no_grad()
+    def timbre_long(self, wave, lens=None, chunk_frames=4096):
+        """The timbre vector (B, 1024) of recordings of any length: wave (B, 1, T) or (B, T) fp32 on the GPU -> what
+        `forward(z, wave)[4]` gives, within fp32 noise, in memory that grows with T only through frame-rate tensors of 80 to 1024
+        rows: the log-mel front-end runs in chunks (log_mel_chunked), the style encoder over all frames, its attention on whichever
+        kernel ops.attention_route names (past 2304 frames the running-max kernel: no T x T tensor, no score row).
+        lens: per-row sample counts (a sequence of ints, or a tensor that is read back once); every row is then run on its own
+        samples alone, one after the other."""
+        if self.training:
+            raise RuntimeError("FAquantizer.timbre_long is an eval-mode call (call .eval() first)")
+        if not isinstance(wave, torch.Tensor) or not wave.is_cuda:
+            from ._lib import FacodecHipError
+            raise FacodecHipError(f"wave must live on the GPU (got {getattr(wave, 'device', type(wave))}); there is no CPU path")
+        w = wave.reshape(wave.shape[0], 1, wave.shape[-1])
+        if lens is not None:
+            lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            if len(lens) != w.shape[0] or any(n < 1 or n > w.shape[-1] for n in lens):
+                raise ValueError(f"lens must give {w.shape[0]} sample counts in [1, {w.shape[-1]}]")
+            return torch.cat([self.timbre_long(w[b:b + 1, :, :n], None, chunk_frames) for b, n in enumerate(lens)])
+        return self.timbre_encoder(self.log_mel_chunked(w, chunk_frames), None)
 
     def decode_weights(self):
         """Per RVQ (prosody, content, residual) the decode_weights() of every quantizer."""

@@ -524,6 +524,93 @@ class StreamingCodec(_HopSession):
         return codes, self.dec.run(outs)
 
 
+class ChunkedCodec:
+    """Offline counterpart of StreamingCodec for recordings of any length: the same encoder / quantizer / decoder streams
+    (left-context taps, carried LSTM state, the prosody front-end's 1 024 samples of look-ahead), fed chunks of seconds instead
+    of 480-sample hops.  Memory is that of one chunk, whatever the recording's length; throughput is the offline kernels'.
+
+        sess = ChunkedCodec(model, timbre, chunk_samples=240000)       # model = build_model(...) (causal), timbre (B, 1024)
+        out = sess.prime(wave[:, :, :240000])           # exactly chunk_samples (a multiple of 2 400, at least 4 800)
+        out = sess.push(wave[:, :, t:t + n])            # any multiple of 300 up to chunk_samples
+        out = sess.finish()                             # the frames that were waiting for look-ahead
+
+    Each call returns dict(frame0, codes=[p, c, r] | None, wave=(B, 1, 300 n) | None) for the frames it completed, as
+    StreamingCodec does, and they concatenate to the offline model's output on the whole signal (codes equal, waveform within fp32
+    noise).  No phase graphs and no side stream: every call runs eagerly on the caller's stream, and the returned tensors are
+    the caller's.  encode_only=True builds no decoder and returns wave=None."""
+
+    def __init__(self, model, timbre, n_c=2, chunk_samples=240000, encode_only=False):
+        chunk_samples = int(chunk_samples)
+        if chunk_samples % PERIOD or chunk_samples < 2 * PERIOD:
+            raise ValueError(f"chunk_samples must be a multiple of {PERIOD} and at least {2 * PERIOD}, got {chunk_samples}")
+        bad = _first_non_causal(model, ("encoder",) if encode_only else ("encoder", "decoder"), "model")
+        if bad is None and not model.quantizer.melspec_encoder.in_layers[0].causal:
+            bad = "model.quantizer.melspec_encoder"
+        if bad is not None:
+            raise NotImplementedError(f"{bad} is not causal: a chunk cannot wait for the samples to the right of it")
+        enc, q = model.encoder, model.quantizer
+        _check_timbre(timbre, None, q.in_dim, "timbre")
+        self.device, self.B = timbre.device, timbre.shape[0]
+        self.chunk_samples, self.n_c, self.encode_only = chunk_samples, int(n_c), bool(encode_only)
+        self._counters = []
+        self.n_samples = 0
+        self._closed = False
+        mods = list(enc.modules()) + list(q.modules()) + ([] if encode_only else list(model.decoder.modules()))
+        for m in mods:
+            if isinstance(m, ConvWeights):
+                m.freeze_packed = True               # inference: materialise w = g v/||v|| once
+        max_frames = chunk_samples // FRAME
+        with torch.no_grad():
+            self.enc = _EncoderStream(self, enc, self.B, chunk_samples)
+            self.qs = _QuantizerStream(self, q, self.B, timbre, max_frames, chunk_samples)
+            self.dec = None if encode_only else _DecoderStream(self, model.decoder, self.B, max_frames)
+
+    def _check_wave(self, wave):
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 3 or wave.shape[0] != self.B or wave.shape[1] != 1:
+            got = tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__
+            raise ValueError(f"a chunk is (B = {self.B}, 1, n) float32, got {got}")
+        if not wave.is_cuda or wave.dtype != torch.float32:
+            raise ops._lib.FacodecHipError(f"a chunk must be float32 on the GPU (got {wave.dtype} on {wave.device}); there is no CPU path")
+
+    @torch.no_grad()
+    def _step(self, wave_new, final=False):
+        first = self.qs.c[0]
+        if wave_new is not None:
+            self.qs.push(wave_new, self.enc.run(wave_new))
+        r = self.qs.run(self.n_c, final)
+        if r is None:
+            return dict(frame0=first, codes=None, wave=None)
+        outs, codes = r
+        return dict(frame0=first, codes=codes, wave=None if self.dec is None else self.dec.run(outs))
+
+    def prime(self, chunk):
+        if self.n_samples:
+            raise RuntimeError("prime() must be the first call")
+        self._check_wave(chunk)
+        if chunk.shape[-1] != self.chunk_samples:
+            raise ValueError(f"prime() wants exactly {self.chunk_samples} samples, got {chunk.shape[-1]}")
+        self.n_samples = chunk.shape[-1]
+        return self._step(chunk.contiguous())
+
+    def push(self, chunk):
+        if not self.n_samples or self._closed:
+            raise RuntimeError("call prime() first" if not self.n_samples else "the session is finished")
+        self._check_wave(chunk)
+        n = chunk.shape[-1]
+        if n < FRAME or n % FRAME or n > self.chunk_samples:
+            raise ValueError(f"push() wants a multiple of {FRAME} samples up to {self.chunk_samples}, got {n}")
+        self.n_samples += n
+        return self._step(chunk.contiguous())
+
+    def finish(self):
+        """End of the signal: emits the frames that were waiting for look-ahead, framed with the reflect padding of the signal's
+        end, and closes the session."""
+        if not self.n_samples or self._closed:
+            raise RuntimeError("call prime() first" if not self.n_samples else "the session is finished")
+        self._closed = True
+        return self._step(None, final=True)
+
+
 def _first_non_causal(model, keys, prefix):
     """Name of the first conv under model[key], in execution order, that looks to the right of its output column, or None.
     (A k = 1 conv pads nothing, whatever its `causal` flag says: the WaveNet's cond_layer.)"""

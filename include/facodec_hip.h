@@ -652,6 +652,18 @@ int fac_wn_res_skip(const float* rs, float* x, float* out, int B, int C, int T, 
  * scores = (q/sqrt(dk))^T k, masked_fill(mask==0,-1e4), softmax over keys, out = p v. */
 int fac_attention(const float* q, const float* k, const float* v, const float* mask, float* out,
                   int B, int n_heads, int dk, int T, fac_stream_t stream);
+/* The same attention with a running max and sum over key tiles (csrc/attention_stream.hip): no score row is ever held, LDS use
+ * does not depend on T.  Semantics as fac_attention (a masked pair's score is REPLACED by -1e4; keys past T weigh exactly 0);
+ * dk <= 256.  fac_attention takes this route by itself where fac_attention_route says so. */
+int fac_attention_stream(const float* q, const float* k, const float* v, const float* mask, float* out,
+                         int B, int n_heads, int dk, int T, fac_stream_t stream);
+/* The kernel fac_attention launches for (dk, T), from the shapes alone: FAC_ATTN_LDS while (16 dk + 16 T) * 4 bytes fit the
+ * 160 KiB of LDS, FAC_ATTN_STREAM past that. */
+#define FAC_ATTN_LDS 0
+#define FAC_ATTN_STREAM 1
+int fac_attention_route(int dk, int T);
+/* Tile sizes of fac_attention_stream: which = 0 queries per workgroup, 1 keys per LDS tile. */
+int fac_attention_stream_tile(int which);
 /* masked temporal average pool (modules/style_encoder.py:83-91): out[b,c] = sum_t x / sum_t mask */
 int fac_masked_mean(const float* x, const float* mask, float* out, int B, int C, int T,
                     fac_stream_t stream);
