@@ -169,7 +169,9 @@ typedef struct fac_conv_desc {
    *   x_p8  : the INPUT in P8 (then `x` may be NULL); taken by the K = 3 / 5 / 7 split kernel (C_in % 16 == 0) and by the 1- / 2-tap
    *           split GEMM kernel (plain, strided and all-phases transposed launches; C_in % 8 == 0), where both operands then move by
    *           LDS-DMA.
-   *   y2_p8 : the pre-activated second output snake(y, alpha_y2) written in P8 instead of (or beside) fp32 `y2`. */
+   *   y2_p8 : reserved -- the pre-activated second output snake(y, alpha_y2) in P8 instead of (or beside) fp32 `y2`.  No kernel
+   *           writes it: fac_conv1d_fwd / fac_conv1d_variant refuse every descriptor that sets it (FAC_ERR_ARG, "P8 operands given
+   *           but the launch does not run on a kernel that takes them"; without alpha_y2, "y2_p8 needs alpha_y2").  Leave it NULL. */
   const void* x_p8;
   int64_t x_p8_plane_bytes;
   void* y2_p8;
