@@ -280,8 +280,8 @@ __global__ __launch_bounds__(256) void vq_fwd_small_t_kernel(VqArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* cbn = sm;                              // [Kc][8]
   float* cc = cbn + a.Kc * VQ_CD;               // [Kc]
-  float* xs = cc + a.Kc;                        // [D]
-  float* wsm = xs + a.D;                        // [D][8]
+  float* xs = cc + ((a.Kc + 3) & ~3);           // [D]; cc and xs are rounded up to whole float4s so that wsm, which is stored as
+  float* wsm = xs + ((a.D + 3) & ~3);           // [D][8] float4, stays 16-byte aligned for any Kc and D (as in vq_fwd_kernel)
   float* part = wsm + a.D * VQ_CD;              // [4][8]
   float* zes = part + 4 * VQ_CD;                // [8]
   float* bestv = zes + VQ_CD;                   // [256]
@@ -448,7 +448,7 @@ extern "C" int fac_vq_fwd(const fac_vq_desc* d, fac_stream_t stream) {
   FAC_REQUIRE(lds <= FAC_LDS_MAX, "vq_fwd: codebook of %d entries + %d in-proj rows do not fit LDS", d->Kc, d->D);
   allow_dynamic_lds<vq_fwd_kernel>();
   if (d->T <= 8 && !d->loss_part && d->D <= 4096) {   // streaming hops: one workgroup per (b, t)
-    const size_t lds_s = ((size_t)d->Kc * (VQ_CD + 1) + (size_t)d->D * (VQ_CD + 1) + 4 * VQ_CD + VQ_CD + 512) * 4;
+    const size_t lds_s = ((size_t)d->Kc * VQ_CD + ((d->Kc + 3) & ~3) + ((d->D + 3) & ~3) + (size_t)d->D * VQ_CD + 4 * VQ_CD + VQ_CD + 512) * 4;
     if (lds_s <= FAC_LDS_MAX) {
       allow_dynamic_lds<vq_fwd_small_t_kernel>();
       hipLaunchKernelGGL(vq_fwd_small_t_kernel, dim3(d->T, d->B), dim3(256), lds_s, (hipStream_t)stream, a);

@@ -569,6 +569,16 @@ int fac_bias_grad(const float* dy, float* db, float* scratch, int B, int C, int 
  *   z_st = z_e + (z_q - z_e);  out = W_out z_st + b_out;
  *   zq_acc += out * mask[b];  residual -= out;
  *   loss_part[b][tile] = sum_{d,t in tile} (z_e - z_q)^2   (commitment == codebook value).
+ * Aliasing: residual may be z_in itself (every RVQ stage after the first updates the residual in place), and nothing else
+ *   may overlap.  That is safe because a workgroup reads and writes only the frames it owns: frame (b, t) of z_in is read
+ *   for the in-projection and once more, by the thread that then writes residual[b][c][t], before that write; no workgroup
+ *   reads a frame another one writes.  zq_acc is read and written by the same thread in the same way.
+ * Routes: with T <= 8, loss_part == NULL, D <= 4096 and the LDS formula below satisfied, one workgroup per (b, t) frame
+ *   (streaming hops); otherwise one workgroup per (b, tile of 16 frames), on a grid padded to a multiple of 8.  Both
+ *   routes give the same bits in every output they share; only the tile route writes loss_part.
+ * Limits: B <= 65535; the codebook, its norms and the in-projection weights live in LDS (160 KiB), in floats
+ *   tile route   8 Kc + roundup4(Kc) + 1152 + 8 D               <= 40960   (Kc = 1024: D <= 3824; rejected beyond)
+ *   frame route  8 Kc + roundup4(Kc) + roundup4(D) + 8 D + 552  <= 40960   (Kc = 1024: D <= 3465; the tile route beyond)
  * ---------------------------------------------------------------------------------------- */
 typedef struct fac_vq_desc {
   float* residual;        /* (B, D, T) in/out: r <- r - out ; may be NULL to skip the update */
