@@ -366,6 +366,8 @@ def test_weight_norm_packing(O, ops, cuda):
     wp = ops.pack_conv_weight(v.to(cuda), gg.to(cuda))
     assert wp.shape == (48, 7, 96)                               # C_in 48 is already a multiple of 48
     assert rel(wp.permute(2, 0, 1), O.weight_norm_weight(v, gg)) < 1e-6
+    sc = ops.wn_scale(v.to(cuda), gg.to(cuda)).cpu()             # exact against fl32(v * scale): the pack is one fp32 multiply
+    assert torch.equal(wp.permute(2, 0, 1).cpu(), v * sc.view(-1, 1, 1))      # (every layout and edge: tests/test_weight_packs.py)
     v2 = torch.randn(40, 8, 1, generator=g)                      # C_out padded 40 -> 64, C_in 8 -> 48 with zeros
     wp2 = ops.pack_conv_weight(v2.to(cuda))
     assert wp2.shape == (48, 1, 64)
