@@ -37,6 +37,9 @@ __host__ __device__ constexpr int cin_pad_dev(int c) { return ((c + 47) / 48) * 
 // The rare paths are kept OUT of line on purpose: libm's sinf / tanhf / log1pf bodies are hundreds of
 // instructions each, and inlining them at every Snake site made the staging loop of the conv kernel
 // overflow the instruction cache (staging then ran at ~20k cycles per chunk -- profiles/ ablation).
+// sin_sq2 / snake_apply2 below are the same operations on two values at once (v_pk_fma/mul/add_f32, bit-equal per component): used by
+// the all-waves epilogue of conv1d_bsplit_kernel.h, where no MFMA runs on the CU; beside MFMAs packed f32 costs more than the scalar
+// pair it replaces, and the other Snake sites measured no gain or a loss with it, so they keep the scalar form.
 __device__ __attribute__((noinline)) float sin_sq_slow(float y) {
   const float s = sinf(y);
   return __fmul_rn(s, s);
@@ -66,6 +69,37 @@ __device__ __forceinline__ float snake_inv(float alpha) { return __fdiv_rn(1.0f,
 __device__ __forceinline__ float snake_apply(float x, float alpha, float inv) {
   return __fadd_rn(x, __fmul_rn(inv, sin_sq(__fmul_rn(alpha, x))));
 }
+
+// Two values per instruction: operation for operation the scalar functions above (fma -> llvm.fma.v2f32, * and + stay separate
+// roundings under -ffp-contract=off); rint, the |y| > 4096 test and the parity select work per component, and sin_sq_slow is called,
+// out of line, for exactly the components beyond 4096.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 sin_sq2(f32x2 y) {
+  const f32x2 k = __builtin_elementwise_rint(y * 0.63661977236758134308f);
+  f32x2 r = __builtin_elementwise_fma(k, (f32x2)(-1.5703125f), y);
+  r = __builtin_elementwise_fma(k, (f32x2)(-4.837512969970703125e-4f), r);
+  r = __builtin_elementwise_fma(k, (f32x2)(-7.54978995489188216e-8f), r);
+  const f32x2 z = r * r;
+  f32x2 ps = __builtin_elementwise_fma(z, (f32x2)(-1.9515295891e-4f), (f32x2)(8.3321608736e-3f));
+  ps = __builtin_elementwise_fma(ps, z, (f32x2)(-1.6666654611e-1f));
+  const f32x2 sn = __builtin_elementwise_fma(ps * z, r, r);
+  f32x2 pc = __builtin_elementwise_fma(z, (f32x2)(2.443315711809948e-5f), (f32x2)(-1.388731625493765e-3f));
+  pc = __builtin_elementwise_fma(pc, z, (f32x2)(4.166664568298827e-2f));
+  const f32x2 cs = __builtin_elementwise_fma(pc * z, z, __builtin_elementwise_fma(z, (f32x2)(-0.5f), (f32x2)(1.0f)));
+  const i32x2 ki = __builtin_convertvector(k, i32x2);
+  f32x2 v;
+  v.x = (ki.x & 1) ? cs.x : sn.x;
+  v.y = (ki.y & 1) ? cs.y : sn.y;
+  v = v * v;
+  const bool bx = fabsf(y.x) > 4096.0f, by = fabsf(y.y) > 4096.0f;
+  if (__builtin_expect(bx || by, 0)) {
+    if (bx) v.x = sin_sq_slow(y.x);
+    if (by) v.y = sin_sq_slow(y.y);
+  }
+  return v;
+}
+__device__ __forceinline__ f32x2 snake_apply2(f32x2 x, float alpha, float inv) { return x + inv * sin_sq2(alpha * x); }
 
 // Epilogue activations other than Snake (cold: once per output element of a few small layers).
 __device__ __attribute__((noinline)) float apply_act_slow(float v, int act) {
@@ -98,7 +132,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // x = h + m + l up to the rounding of the last residual: three round-to-nearest-even bf16 planes, each the bf16 of what the planes
@@ -110,6 +143,19 @@ __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l)
   const float r1 = x - (float)h;
   m = (__bf16)r1;
   l = (__bf16)(r1 - (float)m);
+}
+// split3 with both subtractions pinned to scalar v_sub_f32 (the same bits).  Unrolled over adjacent values, plain split3 is
+// SLP-packed into v_pk_add_f32, and packed f32 issued beside the partner wave's MFMAs costs more than the two scalar
+// instructions it replaces: the staging waves of conv1d_bsplit_kernel (one MFMA wave and one staging wave per SIMD) use this
+// form, -4 .. 6 % per k = 7 launch.  Not a general win: with three waves per SIMD (conv1d_pws_kernel) it measured
+// slower, and in conv1d_gemm_split_kernel no different.
+__device__ __forceinline__ void split3_scalar_sub(float x, __bf16& h, __bf16& m, __bf16& l) {
+  h = (__bf16)x;
+  float r1, r2;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r1) : "v"(x), "v"((float)h));
+  m = (__bf16)r1;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r2) : "v"(r1), "v"((float)m));
+  l = (__bf16)r2;
 }
 
 // Raw workgroup barrier between compiler fences: no s_waitcnt of its own (the caller has waited for exactly what it needs).

@@ -26,6 +26,27 @@ __host__ __device__ constexpr int bs_group(int C_in) { return C_in >= BS_WIDE_MI
 
 __host__ __device__ constexpr int bs_slots(int K, int G) { return (G * K + 1) & ~1; }
 
+// Per-channel constants of the all-waves epilogue (bias, alpha, 1 / (alpha + 1e-9) of the first and of the second output), loaded and
+// divided ONCE per tile row instead of once per quad: lane l of each aligned group of 16 lanes holds the row that group visits in
+// iteration l of the quad loop (the loop steps by a multiple of 16 quads over rows of a multiple of 16 quads, so the 16 lanes of a group
+// always share a row, and a tile takes at most 16 iterations); iteration j fetches lane j of the own group through the LDS crossbar
+// (ds_bpermute_b32: no memory, no barrier).  Every lane of the wave must be active at the fetch.
+struct EpiRow {
+  float bs, al, inv, a2, i2;
+};
+__device__ __forceinline__ EpiRow epi_row_load(bool valid, int co, const float* bias, const float* alpha, const float* alpha2) {
+  EpiRow r = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (valid) {
+    if (bias) r.bs = bias[co];
+    if (alpha) { r.al = alpha[co]; r.inv = snake_inv(r.al); }
+    if (alpha2) { r.a2 = alpha2[co]; r.i2 = snake_inv(r.a2); }
+  }
+  return r;
+}
+__device__ __forceinline__ float epi_row_get(float mine, int lane, int j) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & 48) + j) << 2, __float_as_int(mine)));
+}
+
 // MB: 32-row blocks of the tile (2: 64 output channels; 3: the 96-row form, whose weight stage only fits twice with G = 1).
 // WIDE (NMW == 4): one MFMA wave and one staging wave per SIMD -- the in-flight staging pipeline and the cross-barrier fragment pipeline.
 template <int KT, int G, int NMW, int NSW, int MB = 2>
@@ -143,7 +164,7 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           __bf16 p0, p1, p2;
-          split3(xr[j][i], p0, p1, p2);
+          split3_scalar_sub(xr[j][i], p0, p1, p2);
           h[i] = p0; m[i] = p1; l[i] = p2;
         }
         *reinterpret_cast<bf16x8*>(xd + ((0 * G + u_g[j]) * XW + u_c[j]) * 16) = h;
@@ -570,15 +591,20 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
     const bool vec_ok = (e->y_cs & 3) == 0 && (e->y_bs & 3) == 0 && (!yg || (reinterpret_cast<unsigned long long>(e->y) & 15) == 0) &&
                         (!y2g || (reinterpret_cast<unsigned long long>(e->y2) & 15) == 0) &&
                         (!rg || (reinterpret_cast<unsigned long long>(e->res) & 15) == 0);
-    for (int q = tid; q < CO * QPR; q += NTH) {
+    // bias / alpha / 1 / (alpha + 1e-9) of both outputs: once per row and tile (EpiRow), not once per quad
+    static_assert(QPR % 16 == 0 && NTH % 16 == 0 && (CO * QPR) % 64 == 0 && (CO * QPR + NTH - 1) / NTH <= 16, "EpiRow: 16 lanes share a row, <= 16 iterations");
+    const int row_l = (tid + NTH * (lane & 15)) / QPR;
+    const EpiRow mine = epi_row_load(row_l < CO && co0 + row_l < e->C_out, co0 + row_l, e->bias, e->alpha_out, y2g ? e->alpha2 : nullptr);
+    int j = 0;
+    for (int q = tid; q < CO * QPR; q += NTH, ++j) {
+      const float bs = epi_row_get(mine.bs, lane, j), al = epi_row_get(mine.al, lane, j), inv = epi_row_get(mine.inv, lane, j);
+      float a2 = 0.f, i2 = 0.f;
+      if (y2g) { a2 = epi_row_get(mine.a2, lane, j); i2 = epi_row_get(mine.i2, lane, j); }
       const int row = q / QPR, tq = q - row * QPR;
       const int co = co0 + row, t = t0 + 4 * tq;
       if (co >= e->C_out || t >= e->T_out) continue;
       const float4 av = *reinterpret_cast<const float4*>(tile + row * EP + 4 * tq);
-      float v[4] = {av.x, av.y, av.z, av.w};
-      const float bs = e->bias ? e->bias[co] : 0.f;
-      const float al = e->alpha_out ? e->alpha_out[co] : 0.f;
-      const float inv = e->alpha_out ? snake_inv(al) : 0.f;
+      f32x2 v[2] = {{av.x, av.y}, {av.z, av.w}};
       const long long o = (long long)co * e->y_cs + t;
       const bool full = vec_ok && t + 3 < e->T_out;
       float rv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -591,28 +617,28 @@ __global__ __launch_bounds__((NMW + NSW) * 64, (NMW + NSW) / 4) void conv1d_bspl
           for (int i = 0; i < 4; ++i) rv[i] = t + i < e->T_out ? rg[o + i] : 0.f;
         }
       }
+      // the quad as two pairs: packed f32 (no MFMA runs during the epilogue), the same operations per component as the scalar form
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float x = v[i] + bs;
-        if (e->alpha_out) x = snake_apply(x, al, inv);
-        if (e->act != FAC_ACT_NONE) x = apply_act_slow(x, e->act);
-        v[i] = x + rv[i];
+      for (int i = 0; i < 2; ++i) {
+        f32x2 x = v[i] + bs;
+        if (e->alpha_out) x = snake_apply2(x, al, inv);
+        if (e->act != FAC_ACT_NONE) { x.x = apply_act_slow(x.x, e->act); x.y = apply_act_slow(x.y, e->act); }
+        v[i] = x + (f32x2){rv[2 * i], rv[2 * i + 1]};
       }
-      float w[4];
+      f32x2 w[2] = {};
       if (y2g) {
-        const float a2 = e->alpha2[co], i2 = snake_inv(a2);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
+        for (int i = 0; i < 2; ++i) w[i] = snake_apply2(v[i], a2, i2);
       }
       if (full) {
-        if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w[0], w[1], w[2], w[3]);
+        if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+        if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w[0].x, w[0].y, w[1].x, w[1].y);
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (t + i >= e->T_out) continue;
-          if (yg) yg[o + i] = v[i];
-          if (y2g) y2g[o + i] = w[i];
+          if (yg) yg[o + i] = v[i >> 1][i & 1];
+          if (y2g) y2g[o + i] = w[i >> 1][i & 1];
         }
       }
     }
