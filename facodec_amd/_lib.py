@@ -202,6 +202,7 @@ SIGNATURES = {
     "fac_stft_frames_ragged": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fac_mask_tail": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_mask_tail_i64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "fac_edge_tail": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fac_frame_mask": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_resample": (_i, [C.POINTER(ResampleDesc), _p]),
     "fac_resample_form": (_i, [C.POINTER(ResampleDesc), _p]),

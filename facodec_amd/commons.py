@@ -302,6 +302,146 @@ def reconstruct_clips(model, waves, n_c=2, max_batch_samples=MAX_BATCH_SAMPLES, 
                         sample_rate=sample_rate, quality=quality)
 
 
+# ------------------------------------------------------------------------------------ voice conversion of clip lists
+def edge_plan(redecoder):
+    """-> [(name, columns per frame, n, pad mode)], in execution order: every conv of redecoder.encoder (the WaveNet) and
+    redecoder.decoder that looks to the right of its output column, with the n columns it reads behind a clip's end and what it
+    expects there (its own rule: SConv1d.edge_rule / SConvTranspose1d.edge_rule).  These are the ops.edge_tail_ launches of
+    Redecoder.forward_ragged and Decoder.forward_ragged, each on the conv's input.  Causal modules contribute nothing; a
+    non-causal strided SConv1d raises NotImplementedError naming it.  Host only: no launch."""
+    from .layers import SConv1d, SConvTranspose1d
+    plan = []
+    for key in ("encoder", "decoder"):
+        cols = 1
+        for name, m in redecoder[key].named_modules():
+            if not isinstance(m, (SConv1d, SConvTranspose1d)):
+                continue
+            try:
+                rule = m.edge_rule()
+            except NotImplementedError as e:
+                raise NotImplementedError(f"{key}.{name}: {e}") from None
+            if rule is not None:
+                plan.append((f"{key}.{name}", cols, rule[0], rule[1]))
+            if isinstance(m, SConvTranspose1d):
+                cols *= m.stride
+    return plan
+
+
+def ragged_slack_frames(redecoder):
+    """Frames a padded batch must hold behind its longest clip: every edge of edge_plan has to fit into the tensor, so that the
+    kernel's own padding at the end of the tensor only serves columns nobody keeps.  max ceil(n / columns per frame)."""
+    return max((-(-n // cols) for _, cols, n, _ in edge_plan(redecoder)), default=0)
+
+
+def min_redecode_frames(redecoder):
+    """Shortest clip whose every reflection stays inside the clip: max n // (columns per frame) + 1 over the reflect edges."""
+    from . import ops
+    return max((n // cols + 1 for _, cols, n, mode in edge_plan(redecoder) if mode == ops.PAD_REFLECT), default=0)
+
+
+def _redecoder_hop(redecoder):
+    from .layers import SConvTranspose1d
+    hop = 1
+    for m in redecoder.decoder.modules():
+        if isinstance(m, SConvTranspose1d):
+            hop *= m.stride
+    return hop
+
+
+def _check_redecode(redecoder, frames, n_c):
+    """The host-side checks redecode_clips and convert_clips share, before any launch."""
+    tables = redecoder.encoder.n_c_codebooks
+    if not 0 <= n_c <= tables:
+        raise ValueError(f"n_c = {n_c}: the redecoder has {tables} content tables")
+    need = max(min_redecode_frames(redecoder), 1)
+    for i, F in enumerate(frames):
+        if F < need:
+            raise ValueError(f"clip {i} has {F} frames; the shortest clip the redecoder takes has {need} frames "
+                             "(its longest reflect padding must stay inside the clip)")
+
+
+@torch.no_grad()
+def redecode_clips(redecoder, codes_list, timbres, use_p_code=False, n_c=1, max_batch_samples=MAX_BATCH_SAMPLES,
+                   sample_rate=MODEL_RATE, quality="best"):
+    """Codes of clips of different lengths + one timbre per clip -> list of waves (1, 300 F_i) through the voice-conversion
+    redecoder, in the caller's order: the counterpart of decode_clips for build_model(..., stage="redecoder"), causal,
+    non-causal (the shipped configuration) or mixed.  codes_list[i] = [p (n_p, F_i), c (>= n_c, F_i), ...] int64 as encode_clips
+    returns them; timbres[i] (1024,): the target speaker's.  use_p_code / n_c as in Redecoder.forward (the reference converts with
+    use_p_code=False, n_c=1).
+
+    Per group of plan_groups (on the lengths plus ragged_slack_frames) the codes are padded with code 0 to F' = longest clip +
+    slack frames and go through one Redecoder.forward_ragged and one Decoder.forward_ragged, which write every non-causal
+    conv's padding behind each clip's own end (edge_plan); every wave is cropped to its clip and equals the B = 1 calls
+    `redecoder.decoder(redecoder.encoder(p, c, timbre, ...))` on that clip alone within fp32 noise.  sample_rate: as decode_clips."""
+    from . import ops
+    ratio = None
+    if sample_rate != MODEL_RATE:
+        geo = ops.resample_table(MODEL_RATE, sample_rate, quality)
+        ratio = (geo["o"], geo["n"])
+    codes_list = [list(c) for c in codes_list]
+    if not codes_list:
+        return []
+    timbres = list(timbres)
+    if len(timbres) != len(codes_list):
+        raise ValueError(f"{len(codes_list)} clips but {len(timbres)} timbres")
+    for c in codes_list:
+        if len(c) < 2 or any(not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != c[0].shape[1] for x in c):
+            raise ValueError("every clip's codes must be [codes_p (n_p, F), codes_c (n_c, F), ...]")
+        if [x.shape[0] for x in c[:2]] != [x.shape[0] for x in codes_list[0][:2]]:
+            raise ValueError("the clips disagree on the quantizer counts (n_p, n_c)")
+    frames = [int(c[0].shape[1]) for c in codes_list]
+    _check_redecode(redecoder, frames, n_c)
+    if n_c > codes_list[0][1].shape[0]:
+        raise ValueError(f"n_c = {n_c} but the clips carry {codes_list[0][1].shape[0]} content code rows")
+    _need_gpu([x for c in codes_list for x in c[:2]], "codes")
+    _need_gpu(timbres, "timbres")
+    hop, slack = _redecoder_hop(redecoder), ragged_slack_frames(redecoder)
+    out = [None] * len(codes_list)
+    for group in plan_groups([hop * (F + slack) for F in frames], max_batch_samples):
+        Fp = max(frames[i] for i in group) + slack
+        codes = [torch.stack([torch.nn.functional.pad(codes_list[i][s], (0, Fp - frames[i])) for i in group]) for s in range(2)]
+        timbre = torch.stack([timbres[i].reshape(-1) for i in group])
+        lens = ops.h2d(torch.tensor([frames[i] for i in group], dtype=torch.int32), timbre.device)
+        z = redecoder.encoder.forward_ragged(codes[0], codes[1], timbre, lens, use_p_code=use_p_code, n_c=n_c)
+        wave = redecoder.decoder.forward_ragged(z, lens)
+        if ratio is not None:
+            lens_s = ops.h2d(torch.tensor([hop * frames[i] for i in group], dtype=torch.int32), wave.device)
+            wave = ops.resample(wave, MODEL_RATE, sample_rate, lens=lens_s, quality=quality)
+        for j, i in enumerate(group):
+            n = hop * frames[i]
+            out[i] = wave[j, :, :n if ratio is None else -(-n * ratio[1] // ratio[0])]
+    return out
+
+
+@torch.no_grad()
+def convert_clips(codec, redecoder, sources, targets, use_p_code=False, n_c=1, max_batch_samples=MAX_BATCH_SAMPLES,
+                  sample_rate=MODEL_RATE, quality="best"):
+    """Zero-shot voice conversion of a list of clips (reconstruct_redecoder.py:110-122 per clip): sources[i] (T_i,) or (1, T_i)
+    spoken with the voice of targets[i] -> list of waves (1, 300 (T_i // 300)) in the caller's order.  targets: one clip per
+    source, or a single clip (a tensor, or a list of one) for all of them.  Sources and targets go through
+    encode_clips(codec, ., n_c=2); clip i's codes are redecoded with target i's timbre by redecode_clips.  sample_rate is the
+    rate of the sources, the targets and the output."""
+    sources = list(sources)
+    targets = [targets] if isinstance(targets, torch.Tensor) else list(targets)
+    if len(targets) not in (1, len(sources)):
+        raise ValueError(f"{len(sources)} sources but {len(targets)} targets (one per source, or a single one for all)")
+    if not sources:
+        return []
+    from . import ops
+    ratio = None
+    if sample_rate != MODEL_RATE:
+        geo = ops.resample_table(sample_rate, MODEL_RATE, quality)
+        ratio = (geo["o"], geo["n"])
+    hop = codec.quantizer.hop_length
+    _check_redecode(redecoder, [n // hop for n in _clip_lengths(codec, sources, "sources", ratio=ratio)], n_c)
+    kw = dict(max_batch_samples=max_batch_samples, sample_rate=sample_rate, quality=quality)
+    src = encode_clips(codec, sources, n_c=2, **kw)
+    tgt = encode_clips(codec, targets, n_c=2, **kw)
+    if len(tgt) == 1:
+        tgt = tgt * len(src)
+    return redecode_clips(redecoder, [s["codes"] for s in src], [t["timbre"] for t in tgt], use_p_code=use_p_code, n_c=n_c, **kw)
+
+
 # ------------------------------------------------------------------------------------ recordings of any length
 LONG_CHUNK_SECONDS = 30      # default chunk of the *_long calls: the fastest of 2 / 10 / 30 s measured (DESIGN.md 19.5)
 

@@ -1,7 +1,8 @@
 // Batches of clips with different lengths: the per-row pieces of the offline path.  The clips of a batch are
 // right-padded with zeros to one length T; `lens` (B,) int32 holds every row's own length in SAMPLES and stays on the device --
 // no launch here needs a host copy of it.  A length is clamped to [0, T] before it is used as an index, so a wrong value can
-// zero the wrong columns but can never address memory outside its row.
+// zero the wrong columns but can never address memory outside its row.  (fac_edge_tail, DESIGN.md 23, counts in FRAMES times a
+// per-tensor multiplier instead; the same clamp.)
 #include "common.h"
 #include <limits.h>
 
@@ -77,6 +78,25 @@ __global__ __launch_bounds__(256) void frame_mask_kernel(const int* __restrict__
   if (n_valid && blockIdx.x == 0 && threadIdx.x == 0) n_valid[b] = nf;
 }
 
+// x (B, C, T): behind every clip's own end L_b = clamp(lens[b] * mul, 0, T) the next min(n, T - L_b) columns become what a
+// non-causal conv pads there when it sees the clip alone -- its reflection x[L_b - 2 - j] (0 where that lies in front of the
+// clip), or zeros.  One thread per (row, j): reads lie below L_b and writes at or above it, both inside the row, so the
+// in-place form has no hazard.  Store-only but for the reflected sources; nothing else is touched.
+__global__ __launch_bounds__(256) void edge_tail_kernel(float* __restrict__ x, const int* __restrict__ lens, int rows, int C,
+                                                        int T, int mul, int n, int reflect) {
+  const long long total = (long long)rows * n;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int row = (int)(i / n);
+    const int j = (int)(i - (long long)row * n);
+    const long long Lw = (long long)row_len(lens, row / C, INT_MAX) * mul;
+    const int L = Lw > T ? T : (int)Lw;
+    if (j >= T - L) continue;
+    float* r = x + (long long)row * T;
+    const int src = L - 2 - j;
+    r[L + j] = (reflect && src >= 0) ? r[src] : 0.f;
+  }
+}
+
 static int launch_mask_tail(void* x, const int* lens, int B, int C, int T, int wpe, int unit, fac_stream_t stream, const char* what) {
   FAC_REQUIRE(x && lens && B > 0 && C > 0 && T > 0 && unit > 0, "%s: bad arguments", what);
   FAC_REQUIRE((long long)B * C <= (1 << 30) && (long long)T * wpe <= INT_MAX, "%s: B*C = %lld rows of %lld words do not fit 32-bit indices",
@@ -120,6 +140,20 @@ extern "C" int fac_mask_tail(float* x, const int32_t* lens, int B, int C, int T,
 
 extern "C" int fac_mask_tail_i64(int64_t* x, const int32_t* lens, int B, int C, int T, int unit, fac_stream_t stream) {
   return launch_mask_tail(x, lens, B, C, T, 2, unit, stream, "mask_tail_i64");
+}
+
+extern "C" int fac_edge_tail(float* x, const int32_t* lens, int B, int C, int T, int mul, int n, int mode, fac_stream_t stream) {
+  FAC_REQUIRE(x && lens && B > 0 && C > 0 && T > 0 && mul > 0 && n > 0, "edge_tail: bad arguments");
+  FAC_REQUIRE(mode == FAC_PAD_ZERO || mode == FAC_PAD_REFLECT, "edge_tail: mode %d is neither FAC_PAD_ZERO nor FAC_PAD_REFLECT", mode);
+  FAC_REQUIRE((long long)B * C <= (1 << 30), "edge_tail: B*C = %lld rows do not fit 32-bit indices", (long long)B * C);
+  FAC_REQUIRE(((uintptr_t)x & 3) == 0, "edge_tail: x is not 4-byte aligned");
+  if (n > T) n = T;                                          // a row has no more than T columns behind any end
+  const long long total = (long long)B * C * n;
+  long long g = (total + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(edge_tail_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, lens, B * C, C, T, mul, n,
+                     mode == FAC_PAD_REFLECT ? 1 : 0);
+  return check_launch("edge_tail");
 }
 
 extern "C" int fac_frame_mask(const int32_t* lens, float* mask, int32_t* n_valid, int B, int F, int unit, fac_stream_t stream) {

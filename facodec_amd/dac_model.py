@@ -21,7 +21,7 @@ from torch import nn
 from . import autograd as A
 from . import ops
 from .wprep import cached_forward
-from .layers import SConv1d, SConvTranspose1d, SLSTM, Snake1d
+from .layers import SConv1d, SConvTranspose1d, SLSTM, Snake1d, write_edge
 
 # channel counts that take the single-launch fp32 ResidualUnit kernel
 FUSED_RU_CHANNELS = (64,)
@@ -44,9 +44,11 @@ class ResidualUnit(nn.Module):
     def alpha_in(self):
         return self.block[0].flat()
 
-    def run(self, x, x_act, alpha_next=None, want_raw=True):
+    def run(self, x, x_act, alpha_next=None, want_raw=True, edge=None):
         """x: raw input (skip path); x_act = snake(x, alpha_in) from the producer.
-        Returns (y, snake(y, alpha_next)); y is None when want_raw is False."""
+        Returns (y, snake(y, alpha_next)); y is None when want_raw is False.
+        edge = (lens, columns per frame): the k = 7 conv's padding is written behind every clip of x_act, in place (SConv1d.run;
+        Snake is element-wise and snake(0) = 0, so the reflection / zeros of x_act are those of the activated clip)."""
         b = self.block
         k7, k1 = b[1], b[3]
         # big batches take the split-bf16 k = 7 kernel + the streaming k = 1 kernel instead (same time for the k = 7 part,
@@ -54,11 +56,12 @@ class ResidualUnit(nn.Module):
         streaming = ops.BF16_SPLIT and x.shape[0] * ((x.shape[-1] + 31) // 32) >= 8192
         if k7.w.c_out in FUSED_RU_CHANNELS and x_act.shape[-1] == x.shape[-1] and not streaming:
             # whole unit in one launch: the 1x1 conv runs out of the k7 accumulators (conv1d_fused_ru.hip)
+            write_edge(k7, x_act, edge)
             return_pair = ops.conv1d(x_act, k7.w.packed(), k7.w.c_out, 7, bias=k7.w.bias, dilation=k7.dilation,
                                      alpha_out=b[2].flat(), res=x, w_k1=k1.w.packed(), bias_k1=k1.w.bias,
                                      alpha_y2=alpha_next, want_y=want_raw or alpha_next is None, causal=k7.causal)
             return return_pair if alpha_next is not None else (return_pair, None)
-        h = b[1].run(x_act, alpha_out=b[2].flat())
+        h = b[1].run(x_act, alpha_out=b[2].flat(), edge=edge)
         if h.shape[-1] != x.shape[-1]:  # non-causal trimming of :38-41 never triggers with SConv1d padding
             pad = (x.shape[-1] - h.shape[-1]) // 2
             x = x[..., pad:-pad].contiguous()
@@ -74,12 +77,12 @@ class ResidualUnit(nn.Module):
         return self.run(x, ops.snake(x, self.alpha_in))[0]
 
 
-def _run_units(units, x, x_act, alpha_after):
+def _run_units(units, x, x_act, alpha_after, edge=None):
     """Chains ResidualUnits; the last one only emits the copy pre-activated with `alpha_after`."""
     for j, ru in enumerate(units):
         last = j == len(units) - 1
         nxt = alpha_after if last else units[j + 1].alpha_in
-        x, x_act = ru.run(x, x_act, alpha_next=nxt, want_raw=not last)
+        x, x_act = ru.run(x, x_act, alpha_next=nxt, want_raw=not last, edge=edge)
     return x_act
 
 
@@ -183,11 +186,13 @@ class DecoderBlock(nn.Module):
     def alpha_in(self):
         return self.block[0].flat()
 
-    def run(self, x_act, alpha_after):
-        """x_act = snake(x, alpha_in); returns the block output pre-activated with `alpha_after`."""
+    def run(self, x_act, alpha_after, edge=None):
+        """x_act = snake(x, alpha_in); returns the block output pre-activated with `alpha_after`.
+        edge = (lens, columns per frame of x_act); the units behind the transposed conv run at `stride` times as many."""
         b = self.block
-        y, y_act = b[1].run(x_act, alpha_y2=b[2].alpha_in)
-        return _run_units([b[2], b[3], b[4]], y, y_act, alpha_after)
+        y, y_act = b[1].run(x_act, alpha_y2=b[2].alpha_in, edge=edge)
+        return _run_units([b[2], b[3], b[4]], y, y_act, alpha_after,
+                          edge=None if edge is None else (edge[0], edge[1] * b[1].stride))
 
     def forward(self, x):
         raise NotImplementedError("DecoderBlock is executed through Decoder.forward's fused plan")
@@ -236,19 +241,41 @@ class Decoder(nn.Module):
                 x = A.slstm(m, x)
         return A.conv(mods[-2], xa, act=ops.ACT_TANH)
 
+    def _run(self, x, lens=None):
+        """The fused eval plan; lens (B,) int32 frames on the device: a right-padded batch of clips (forward_ragged)."""
+        mods = list(self.model)
+        blocks = [m for m in mods if isinstance(m, DecoderBlock)]
+        final_alpha = mods[-3].flat()
+        cols = 1                                               # columns per frame of the tensor at hand
+
+        def edge():
+            return None if lens is None else (lens, cols)
+
+        if self.use_lstm:
+            x = mods[0].run(x, edge=edge())
+            x_act = mods[1](x, alpha_out=blocks[0].alpha_in)
+        else:
+            _, x_act = mods[0].run(x, alpha_y2=blocks[0].alpha_in, want_y=False, edge=edge())
+        for i, blk in enumerate(blocks):
+            nxt = blocks[i + 1].alpha_in if i + 1 < len(blocks) else final_alpha
+            x_act = blk.run(x_act, nxt, edge=edge())
+            cols *= blk.block[1].stride
+        return mods[-2].run(x_act, act=ops.ACT_TANH, edge=edge())
+
     @cached_forward
     def forward(self, x):
         if self.training:
             return self._forward_train(x)
-        mods = list(self.model)
-        blocks = [m for m in mods if isinstance(m, DecoderBlock)]
-        final_alpha = mods[-3].flat()
-        if self.use_lstm:
-            x = mods[0].run(x)
-            x_act = mods[1](x, alpha_out=blocks[0].alpha_in)
-        else:
-            _, x_act = mods[0].run(x, alpha_y2=blocks[0].alpha_in, want_y=False)
-        for i, blk in enumerate(blocks):
-            nxt = blocks[i + 1].alpha_in if i + 1 < len(blocks) else final_alpha
-            x_act = blk.run(x_act, nxt)
-        return mods[-2].run(x_act, act=ops.ACT_TANH)
+        return self._run(x)
+
+    @cached_forward
+    def forward_ragged(self, z, lens):
+        """forward on a right-padded batch of clips of different lengths: z (B, input_channel, F') fp32 contiguous,
+        lens (B,) int32 on the device, every clip's length in FRAMES -> (B, d_out, F' * prod(rates)), of which
+        [b, :, :lens[b] * prod(rates)] is what forward gives z[b:b+1, :, :lens[b]] alone.  F' must leave
+        commons.ragged_slack_frames columns behind the longest clip.  The same fused plan as forward; in front of every conv that
+        looks to the right, the conv's own padding is written behind each clip IN PLACE (ops.edge_tail_) -- into the tails of the
+        caller's z too -- and what the outputs hold behind a clip is meaningless.  A causal decoder makes no such launch.  Eval only."""
+        if self.training:
+            raise RuntimeError("Decoder.forward_ragged is an eval-mode forward (call .eval() first); training batches are equal-length crops")
+        return self._run(z, lens)

@@ -97,6 +97,14 @@ FLAT_SHORT_CLIPS = True
 FLAT_STRIDE1 = True      # wide stride-1 k = 7 convs on short clips too
 
 
+def write_edge(conv, x, edge):
+    """edge = (lens (B,) int32 frames on the device, columns per frame of x) or None: where `conv` looks to the right
+    (conv.edge_rule()), its padding is written behind every clip of x, in place (ops.edge_tail_)."""
+    rule = conv.edge_rule() if edge is not None else None
+    if rule is not None:
+        ops.edge_tail_(x, edge[0], edge[1], rule[0], rule[1])
+
+
 class SConv1d(nn.Module):
     """Causal / asymmetric-padded Conv1d (dac/model/encodec.py:192-228).  State-dict keys:
     conv.conv.{weight_g,weight_v,bias} (norm='weight_norm') or conv.conv.{weight,bias}."""
@@ -120,9 +128,25 @@ class SConv1d(nn.Module):
                              grad=torch.is_grad_enabled(), c_out_mult16=False, tail="always", flat_infer=FLAT_SHORT_CLIPS,
                              flat_stride1=FLAT_STRIDE1)
 
-    def run(self, x, alpha_in=None, alpha_out=None, res=None, act=ops.ACT_NONE, alpha_y2=None, want_y=True):
-        """alpha_y2: additionally emit snake(y, alpha_y2) for the next Snake->conv (returns (y, y2))."""
+    def edge_rule(self):
+        """What this conv reads behind the last column of a clip it sees alone: (columns, pad mode), or None when it does not look
+        to the right (causal, or a non-causal 1x1).  A non-causal strided conv has an extra right padding that depends on the
+        length (dac/model/encodec.py:71-78): no rule, NotImplementedError."""
+        if self.causal:
+            return None
+        if self.stride != 1:
+            raise NotImplementedError(f"a non-causal strided SConv1d (k = {self.kernel_size}, stride {self.stride}) pads its right "
+                                      "side by an amount that depends on the clip's length: no per-clip edge rule")
+        n = ((self.kernel_size - 1) * self.dilation) // 2
+        return (n, self.pad_mode) if n > 0 else None
+
+    def run(self, x, alpha_in=None, alpha_out=None, res=None, act=ops.ACT_NONE, alpha_y2=None, want_y=True, edge=None):
+        """alpha_y2: additionally emit snake(y, alpha_y2) for the next Snake->conv (returns (y, y2)).
+        edge = (lens (B,) int32 frames on the device, columns per frame): a right-padded batch of clips -- the
+        columns behind every clip's own end are first overwritten IN PLACE with this conv's padding (ops.edge_tail_), then the
+        unchanged launch follows."""
         w, k, s_ = self.w, self.kernel_size, self.stride
+        write_edge(self, x, edge)
         B, _, T = x.shape       # (x is an fp32 tensor: no caller hands a P8 to a module, so the old chains' isinstance guards are gone)
         plan = self.plan(B, T, alpha_in is not None, alpha_out is None and res is None and act == ops.ACT_NONE, res is not None)
         split = (w.packed_split_strided(s_) if plan.layout == ops.W_GEMM_STRIDED
@@ -164,8 +188,15 @@ class SConvTranspose1d(nn.Module):
         return ops.plan_convtr(self.w.c_in, self.w.c_out, self.stride, B, T, causal=self.causal, alpha_in=alpha_in,
                                grad=torch.is_grad_enabled(), flat_infer=FLAT_SHORT_CLIPS)
 
-    def run(self, x, alpha_in=None, alpha_y2=None):
+    def edge_rule(self):
+        """Non-causal (trimmed on both sides): the last ceil(stride / 2) outputs of a clip also take the column behind its end, which
+        is no signal -- (1, PAD_ZERO).  Causal: None."""
+        return None if self.causal else (1, ops.PAD_ZERO)
+
+    def run(self, x, alpha_in=None, alpha_y2=None, edge=None):
+        """edge = (lens, columns per frame of x): see SConv1d.run; the column behind every clip is zeroed in place first."""
         w = self.w
+        write_edge(self, x, edge)
         B, c_in, T = x.shape
         plan = self.plan(B, T, alpha_in is not None)
         if plan.layout == ops.TR_FLAT:

@@ -1276,6 +1276,19 @@ def mask_tail_(x, lens, unit):
     return x
 
 
+def edge_tail_(x, lens, mul, n, mode):
+    """x (B, C, T) fp32, contiguous, of `mul` columns per frame; lens (B,) int32 in FRAMES.  Behind every clip's own end
+    L_b = min(lens[b] * mul, T) the next min(n, T - L_b) columns become, in place, what a non-causal conv pads there when it
+    sees the clip alone: PAD_REFLECT x[b, :, L_b + j] = x[b, :, L_b - 2 - j] (0 in front of the clip), PAD_ZERO zeros."""
+    if not x.is_cuda:
+        raise _lib.FacodecHipError(f"tensor must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dim() != 3 or not x.is_contiguous() or x.dtype != torch.float32:
+        raise _lib.FacodecHipError(f"edge_tail_: a contiguous (B, C, T) float32 tensor, got {x.dtype} {tuple(x.shape)}")
+    B, c, T = x.shape
+    _lib.check(_lib.load().fac_edge_tail(_ptr(x), _ptr(_lens(lens, B)), B, c, T, mul, n, mode, _stream()), "fac_edge_tail")
+    return x
+
+
 def frame_mask(lens, n_frames, unit):
     """-> (mask (B, n_frames) float 0 / 1 with mask[b, f] = f < lens[b] // unit, frame_lens (B,) int32 = min(lens // unit, n_frames))."""
     B = lens.shape[0]

@@ -173,7 +173,9 @@ class WN(nn.Module):
             rs = 2 * hidden_channels if i < n_layers - 1 else hidden_channels
             self.res_skip_layers.append(SConv1d(hidden_channels, rs, 1, norm="weight_norm", causal=causal))
 
-    def forward(self, x, x_mask=None, g=None):
+    def forward(self, x, x_mask=None, g=None, edge=None):
+        """edge = (lens (B,) int32 frames on the device, 1): a right-padded batch of clips -- every in_layer's padding is written
+        behind each clip of the running x before that layer reads it (SConv1d.run; x is this call's own copy)."""
         x = x.clone()
         out = torch.zeros_like(x)
         cond = None
@@ -181,7 +183,7 @@ class WN(nn.Module):
             cond = self.cond_layer.run(g.reshape(g.shape[0], -1, 1)).reshape(g.shape[0], -1)   # (B, 2*H*L)
         H2 = 2 * self.hidden_channels
         for i in range(self.n_layers):
-            a = self.in_layers[i].run(x)
+            a = self.in_layers[i].run(x, edge=edge)
             acts = ops.gate_tanh_sigmoid(a, None if cond is None else cond[:, i * H2:(i + 1) * H2])
             rs = self.res_skip_layers[i].run(acts)
             ops.wn_res_skip_(rs, x, out, last=(i == self.n_layers - 1))

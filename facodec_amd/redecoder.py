@@ -37,6 +37,19 @@ class Redecoder(nn.Module):
         (golden tests)."""
         if self.training:
             return self._forward_train(p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, dropout)
+        return self._forward_eval(p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c)
+
+    def forward_ragged(self, p_code, c_code, timbre_vec, lens, use_p_code=True, use_c_code=True, n_c=2):
+        """forward on a right-padded batch of clips of different lengths: codes (B, n, F') padded with any valid
+        code, lens (B,) int32 on the device, every clip's length in frames -> (B, 1024, F'), of which [b, :, :lens[b]] is what
+        forward gives clip b alone; what sits behind a clip is meaningless.  F' must leave commons.ragged_slack_frames columns
+        behind the longest clip.  Every non-causal WaveNet layer is preceded by one ops.edge_tail_ launch that writes the
+        layer's reflection at each clip's own end; a causal WaveNet gets none.  Eval only."""
+        if self.training:
+            raise RuntimeError("Redecoder.forward_ragged is an eval-mode forward (call .eval() first); training batches are equal-length crops")
+        return self._forward_eval(p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, edge=(lens, 1))
+
+    def _forward_eval(self, p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, edge=None):
         B, _, T = p_code.shape
         x = torch.zeros(B, self.embed_dim, T, device=p_code.device, dtype=torch.float32)
         if use_p_code and self.n_p_codebooks:
@@ -45,7 +58,7 @@ class Redecoder(nn.Module):
         if use_c_code and n_c:
             tabs = torch.stack([e.weight.detach() for e in list(self.content_embed)[:n_c]])
             ops.embed_sum(c_code, tabs, 0, out=x)
-        x = self.encoder(x, None, g=timbre_vec)
+        x = self.encoder(x, None, g=timbre_vec, edge=edge)
         return self.conv_out.run(x)
 
     def _forward_train(self, p_code, c_code, timbre_vec, use_p_code, use_c_code, n_c, dropout):

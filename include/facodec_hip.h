@@ -710,6 +710,11 @@ int fac_stft_frames_ragged(const float* wave, const int32_t* lens, float* frames
  * int64 (code tensors) for the _i64 form.  Store-only: 16-byte stores over the tails, nothing else is touched. */
 int fac_mask_tail(float* x, const int32_t* lens, int B, int C, int T, int unit, fac_stream_t stream);
 int fac_mask_tail_i64(int64_t* x, const int32_t* lens, int B, int C, int T, int unit, fac_stream_t stream);
+/* What a non-causal conv pads behind a clip that it sees alone, written behind every clip of a right-padded batch, in place
+ * (DESIGN.md 23).  Here lens counts FRAMES and x (B, C, T) fp32 has `mul` columns per frame: L_b = clamp(lens[b] * mul, 0, T).
+ * For j in [0, min(n, T - L_b)) and every channel: mode FAC_PAD_REFLECT writes x[b, c, L_b + j] = x[b, c, L_b - 2 - j] (0 where
+ * that source index is negative), mode FAC_PAD_ZERO writes 0.  Reads lie below L_b, writes at or above it; nothing else is touched. */
+int fac_edge_tail(float* x, const int32_t* lens, int B, int C, int T, int mul, int n, int mode, fac_stream_t stream);
 /* mask[b, f] = f < lens[b] / unit ? 1 : 0  (B, F) fp32, the mask of fac_attention / fac_masked_mean;
  * n_valid (B,) int32 = min(lens[b] / unit, F), or NULL. */
 int fac_frame_mask(const int32_t* lens, float* mask, int32_t* n_valid, int B, int F, int unit, fac_stream_t stream);
