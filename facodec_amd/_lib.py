@@ -58,6 +58,22 @@ class VqDecodeDesc(C.Structure):
     ]
 
 
+class CodesPackDesc(C.Structure):
+    _fields_ = [
+        ("codes", _p * 3), ("codes_bs", _i64 * 3), ("codes_qs", _i64 * 3), ("n_q", C.c_int32 * 3),
+        ("lens", _p), ("out", _p), ("out_bs", _i64),
+        ("B", C.c_int32), ("T", C.c_int32), ("bits", C.c_int32),
+    ]
+
+
+class CodesUnpackDesc(C.Structure):
+    _fields_ = [
+        ("in_", _p), ("in_bs", _i64), ("codes", _p * 3), ("codes_bs", _i64 * 3), ("codes_qs", _i64 * 3), ("n_q", C.c_int32 * 3),
+        ("lens", _p),
+        ("B", C.c_int32), ("T", C.c_int32), ("bits", C.c_int32),
+    ]
+
+
 class ResampleDesc(C.Structure):
     _fields_ = [
         ("hist", _p), ("x", _p), ("lens", _p), ("y", _p), ("hist_out", _p), ("table", _p), ("offs", _p),
@@ -179,6 +195,9 @@ SIGNATURES = {
     "fac_vq_fwd": (_i, [C.POINTER(VqDesc), _p]),
     "fac_vq_loss_tiles": (_i, [_i]),
     "fac_vq_decode": (_i, [C.POINTER(VqDecodeDesc), _p]),
+    "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),
+    "fac_codes_unpack": (_i, [C.POINTER(CodesUnpackDesc), _p]),
+    "fac_codes_row_bytes": (_i64, [_i, _i, _i]),
     "fac_rccl_available": (_i, []),
     "fac_rccl_unique_id": (_i, [_p]),
     "fac_rccl_comm_init": (_i, [C.POINTER(_p), _p, _i, _i]),

@@ -551,6 +551,247 @@ def reconstruct_long(model, wave, n_c=2, chunk_seconds=LONG_CHUNK_SECONDS, timbr
     return decode_long(model, enc["codes"], enc["timbre"], chunk_seconds=chunk_seconds)
 
 
+# ------------------------------------------------------------------------------------ the bitstream
+def code_bits(model):
+    """Field width of the model's codes: ceil(log2(codebook_size)), 10 for the shipped 1024-entry codebooks."""
+    return max(1, (model.quantizer.prosody_quantizer.codebook_size - 1).bit_length())
+
+
+def _blobs_from_codes(model, codes, timbre, frames, sample_rate, n_samples, lens=None):
+    """codes [p, c, r] (B, n, T) int64 on the device (strided views welcome) -> B container blobs: one ops.pack_codes launch, one
+    device-to-host copy of the uint8 rows (and one of the timbres, when they are stored), then host slicing to every clip's own
+    payload_bytes.  frames[b] / n_samples[b]: clip b's frame count and original length; lens: the frame counts on the device
+    when they differ."""
+    from . import bitstream, ops
+    bits = code_bits(model)
+    n_q = tuple(int(c.shape[1]) for c in codes)
+    rows = ops.pack_codes(codes, bits=bits, lens=lens).cpu().numpy()
+    tim = timbre.detach().to(torch.float32).cpu().numpy() if timbre is not None else None
+    q = model.quantizer
+    out = []
+    for b, F in enumerate(frames):
+        head = dict(bits=bits, n_q=n_q, sample_rate=sample_rate, n_frames=F, n_samples=n_samples[b],
+                    codebook_size=q.prosody_quantizer.codebook_size, timbre_dim=q.in_dim)
+        out.append(bitstream.write(head, tim[b].tobytes() if tim is not None else None,
+                                   rows[b, :bitstream.payload_bytes(F, sum(n_q), bits)].tobytes()))
+    return out
+
+
+def _check_n_r(model, n_r):
+    top = model.quantizer.residual_quantizer.n_codebooks
+    if not 0 <= n_r <= top:
+        raise ValueError(f"n_r = {n_r}: the model has {top} residual quantizers")
+
+
+@torch.no_grad()
+def compress(model, wave, n_c=2, n_r=3, with_timbre=True, sample_rate=MODEL_RATE, quality="best"):
+    """Audio -> bytes.  wave (B, 1, T) float32 on the GPU -> list of B container blobs (bitstream.py); one clip (T,) or (1, T)
+    -> one blob.
+
+        blob = compress(model, wave)                         # 4.8 kbit/s of payload + the timbre (4 KiB) + 36 bytes
+        wave_hat = decompress(model, blob)                   # decode_codes(model, codes, timbre) of the same forward
+
+    The codes are those of `model.encoder` -> `model.quantizer(z, wave, n_c, return_codes=True)` on the batch; n_r < 3 stores
+    the first n_r residual rows only (the strided view codes_r[:, :n_r]: bitrate scalability, nothing is re-encoded).  One
+    ops.pack_codes launch and one device-to-host copy of the packed rows per call.  with_timbre=False leaves the timbre out
+    (decompress then needs timbre=).  sample_rate: the rate of `wave`; other than 24000 it is resampled first (ops.resample,
+    `quality`), and the header records the rate so that decompress returns audio at it."""
+    from . import ops
+    _need_gpu([wave], "wave")
+    _check_n_r(model, n_r)
+    single = wave.dim() <= 2
+    if single:
+        if not (wave.dim() == 1 or wave.shape[0] == 1):
+            raise ValueError(f"one clip must be (T,) or (1, T), a batch (B, 1, T); got {tuple(wave.shape)}")
+        wave = wave.reshape(1, 1, -1)
+    if wave.dim() != 3 or wave.shape[1] != 1 or wave.dtype != torch.float32:
+        raise ValueError(f"wave must be float32 (B, 1, T), got {wave.dtype} {tuple(wave.shape)}")
+    B, n_in = wave.shape[0], wave.shape[-1]
+    x = wave.contiguous()
+    if sample_rate != MODEL_RATE:
+        x = ops.resample(x, sample_rate, MODEL_RATE, quality=quality)
+    _clip_lengths(model, [x[0, 0]], "wave")
+    out = model.quantizer(model.encoder(x), x, n_c=n_c, return_codes=True)
+    timbre, codes = out[4], out[5]
+    codes = [codes[0], codes[1], codes[2][:, :n_r]]
+    F = codes[0].shape[-1]
+    blobs = _blobs_from_codes(model, codes, timbre if with_timbre else None, [F] * B, sample_rate, [n_in] * B)
+    return blobs[0] if single else blobs
+
+
+@torch.no_grad()
+def compress_clips(model, waves, n_c=2, n_r=3, with_timbre=True, max_batch_samples=MAX_BATCH_SAMPLES, sample_rate=MODEL_RATE,
+                   quality="best"):
+    """Clips of different lengths -> one container blob per clip, in the caller's order: encode_clips' groups and forward, then
+    per group one ops.pack_codes launch with the group's frame counts as `lens` and one device-to-host copy."""
+    from . import ops
+    _check_n_r(model, n_r)
+    ratio = None
+    if sample_rate != MODEL_RATE:
+        geo = ops.resample_table(sample_rate, MODEL_RATE, quality)
+        ratio = (geo["o"], geo["n"])
+    waves = list(waves)
+    if not waves:
+        return []
+    for w in waves:
+        if isinstance(w, torch.Tensor) and not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = _clip_lengths(model, waves, "clips", ratio=ratio)
+    dev, hop = waves[0].device, model.quantizer.hop_length
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True).unsqueeze(1)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), dev)
+        if ratio is not None:
+            lens_in = ops.h2d(torch.tensor([waves[i].shape[-1] for i in group], dtype=torch.int32), dev)
+            batch = ops.resample(batch, sample_rate, MODEL_RATE, lens=lens_in, quality=quality)
+        z = model.encoder(batch)
+        _, codes, timbre, frame_lens = model.quantizer.forward_ragged(z, batch, lens, n_c=n_c)
+        codes = [codes[0], codes[1], codes[2][:, :n_r]]
+        blobs = _blobs_from_codes(model, codes, timbre if with_timbre else None, [lengths[i] // hop for i in group], sample_rate,
+                                  [int(waves[i].shape[-1]) for i in group], lens=frame_lens)
+        for j, i in enumerate(group):
+            out[i] = blobs[j]
+    return out
+
+
+def _parse_blobs(model, blobs):
+    """bitstream.read of every blob + the checks against the model -> [(Header, timbre ndarray | None, payload)]."""
+    from . import bitstream
+    q = model.quantizer
+    parsed = []
+    for i, blob in enumerate(blobs):
+        hdr, tim, payload = bitstream.read(blob)
+        if hdr.is_stream_header:
+            raise ValueError(f"blob {i} is a stream header (streaming.CodeDepacketizer reads those), not a clip")
+        if hdr.codebook_size != q.prosody_quantizer.codebook_size:
+            raise ValueError(f"blob {i}: codebook_size {hdr.codebook_size}, the model has {q.prosody_quantizer.codebook_size}")
+        if hdr.timbre_dim != q.in_dim:
+            raise ValueError(f"blob {i}: timbre_dim {hdr.timbre_dim}, the model has {q.in_dim}")
+        for n, rvq, name in zip(hdr.n_q, (q.prosody_quantizer, q.content_quantizer, q.residual_quantizer), "pcr"):
+            if n > rvq.n_codebooks:
+                raise ValueError(f"blob {i}: n_{name} = {n}, the model has {rvq.n_codebooks} such quantizers")
+        if hdr.n_frames < 1:
+            raise ValueError(f"blob {i} has no frames")
+        parsed.append((hdr, tim, payload))
+    return parsed
+
+
+def _timbres_for(model, parsed, timbre, dev):
+    """(B, dim) float32 on the device: the override (one (dim,) / (1, dim) vector for all, or (B, dim), or a list), else the
+    stored timbres in one host-to-device copy."""
+    import numpy as np
+    from . import ops
+    B, dim = len(parsed), model.quantizer.in_dim
+    if timbre is not None:
+        if isinstance(timbre, (list, tuple)):
+            _need_gpu(timbre, "timbre")
+            timbre = torch.stack([t.reshape(-1) for t in timbre])
+        _need_gpu([timbre], "timbre")
+        timbre = timbre.reshape(-1, timbre.shape[-1]).to(torch.float32)
+        if timbre.shape[0] == 1 and B > 1:
+            timbre = timbre.expand(B, -1)
+        if tuple(timbre.shape) != (B, dim):
+            raise ValueError(f"timbre must be ({dim},) or ({B}, {dim}), got {tuple(timbre.shape)}")
+        return timbre.contiguous()
+    for i, (_, tim, _) in enumerate(parsed):
+        if tim is None:
+            raise ValueError(f"blob {i} carries no timbre (compressed with with_timbre=False): pass timbre=")
+    return ops.h2d(torch.from_numpy(np.stack([tim for _, tim, _ in parsed])), dev)
+
+
+def _codes_from_payloads(headers, payloads, dev, ragged):
+    """Payloads of clips that agree on (n_q, bits) -> [p, c, r] (B, n, T) int64 on the device, T the longest clip, code 0 behind
+    every clip's own frames: one host-to-device copy of the zero-padded rows and one ops.unpack_codes launch."""
+    import numpy as np
+    from . import ops
+    h0 = headers[0]
+    T = max(h.n_frames for h in headers)
+    rows = np.zeros((len(headers), ops.codes_row_bytes(T, h0.Q, h0.bits)), dtype=np.uint8)
+    for b, p in enumerate(payloads):
+        rows[b, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+    lens = ops.h2d(torch.tensor([h.n_frames for h in headers], dtype=torch.int32), dev) if ragged else None
+    return ops.unpack_codes(ops.h2d(torch.from_numpy(rows), dev), h0.n_q, T, bits=h0.bits, lens=lens)
+
+
+def _blob_device(model):
+    return next(model.decoder.parameters()).device
+
+
+@torch.no_grad()
+def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MAX_BATCH_SAMPLES, quality="best"):
+    """Bytes -> audio: a list of container blobs -> list of waves (1, N_i) in the caller's order; one blob -> one wave.
+
+    The headers are read on the host (bitstream.read: magic, version, length, CRC), the blobs grouped by their layout
+    (n_p, n_c, n_r, bits) and, within one layout, by plan_groups; per group one host-to-device copy of the payload rows, one
+    ops.unpack_codes launch with the clips' frame counts, then decode_clips' path (decode_codes on the padded batch, every wave
+    cropped to its clip).  timbre: overrides the stored timbres (timbre swap): one vector for all blobs or one per blob;
+    required for blobs written with with_timbre=False.  sample_rate: None gives every clip back at its header's rate; a value
+    resamples every clip to it.  A header whose codebook_size or timbre_dim is not the model's raises ValueError."""
+    from . import ops
+    single = isinstance(blobs, (bytes, bytearray, memoryview))
+    blobs = [blobs] if single else list(blobs)
+    if not blobs:
+        return []
+    parsed = _parse_blobs(model, blobs)
+    dev = timbre[0].device if isinstance(timbre, (list, tuple)) else timbre.device if timbre is not None else _blob_device(model)
+    timbres = _timbres_for(model, parsed, timbre, dev)
+    hop = model.quantizer.hop_length
+    need = min_clip_samples(model)
+    for i, (h, _, _) in enumerate(parsed):
+        if h.n_frames * hop < need:
+            raise ValueError(f"blob {i} has {h.n_frames} frames; the shortest clip this path takes has {-(-need // hop)} frames")
+    layouts = {}
+    for i, (h, _, _) in enumerate(parsed):
+        layouts.setdefault((h.n_q, h.bits, sample_rate if sample_rate is not None else h.sample_rate), []).append(i)
+    out = [None] * len(blobs)
+    for (_, _, rate), members in layouts.items():
+        ratio = None
+        if rate != MODEL_RATE:
+            geo = ops.resample_table(MODEL_RATE, rate, quality)
+            ratio = (geo["o"], geo["n"])
+        lengths = [parsed[i][0].n_frames * hop for i in members]
+        for g in plan_groups(lengths, max_batch_samples):
+            group = [members[j] for j in g]
+            headers = [parsed[i][0] for i in group]
+            codes = _codes_from_payloads(headers, [parsed[i][2] for i in group], dev, len({h.n_frames for h in headers}) > 1)
+            wave = decode_codes(model, codes, timbres if group == list(range(len(blobs))) else timbres[group])
+            if ratio is not None:
+                lens = ops.h2d(torch.tensor([h.n_frames * hop for h in headers], dtype=torch.int32), dev)
+                wave = ops.resample(wave, MODEL_RATE, rate, lens=lens, quality=quality)
+            for j, i in enumerate(group):
+                n = headers[j].n_frames * hop
+                out[i] = wave[j, :, :n if ratio is None else -(-n * ratio[1] // ratio[0])]
+    return out[0] if single else out
+
+
+@torch.no_grad()
+def compress_long(model, wave, n_c=2, n_r=3, with_timbre=True, chunk_seconds=LONG_CHUNK_SECONDS, timbre=None, timbre_seconds=None):
+    """encode_long into the container: wave (B, 1, T) float32 on the GPU at 24 kHz, any length -> list of B blobs.  The whole
+    code stream of the recording is packed by one ops.pack_codes launch (64-bit bit offsets) and copied to the host once."""
+    _check_n_r(model, n_r)
+    enc = encode_long(model, wave, n_c=n_c, chunk_seconds=chunk_seconds, timbre=timbre, timbre_seconds=timbre_seconds)
+    codes = [enc["codes"][0], enc["codes"][1], enc["codes"][2][:, :n_r]]
+    B, F = wave.shape[0], codes[0].shape[-1]
+    return _blobs_from_codes(model, codes, enc["timbre"] if with_timbre else None, [F] * B, MODEL_RATE, [int(wave.shape[-1])] * B)
+
+
+@torch.no_grad()
+def decompress_long(model, blobs, timbre=None, chunk_seconds=LONG_CHUNK_SECONDS):
+    """Blobs of compress_long (equal frame counts and one layout, as one recording batch has) -> (B, 1, 300 F) through decode_long:
+    one host-to-device copy and one ops.unpack_codes launch for the whole code stream, then the chunked decoder."""
+    blobs = [blobs] if isinstance(blobs, (bytes, bytearray, memoryview)) else list(blobs)
+    parsed = _parse_blobs(model, blobs)
+    headers = [h for h, _, _ in parsed]
+    if len({(h.n_q, h.bits, h.n_frames) for h in headers}) != 1:
+        raise ValueError("decompress_long takes the blobs of one recording batch: equal n_frames, quantizer counts and bits "
+                         f"(got {sorted({(h.n_q, h.bits, h.n_frames) for h in headers})}); decompress handles mixed lists")
+    dev = timbre.device if isinstance(timbre, torch.Tensor) else _blob_device(model)
+    timbres = _timbres_for(model, parsed, timbre, dev)
+    codes = _codes_from_payloads(headers, [p for _, _, p in parsed], dev, False)
+    return decode_long(model, codes, timbres, chunk_seconds=chunk_seconds)
+
+
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):
     """modules/commons.py:446-471: {'net': {key: state_dict}, ...}; strips DDP's 'module.' prefix."""
     state = torch.load(path, map_location="cpu")

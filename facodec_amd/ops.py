@@ -1082,6 +1082,109 @@ def vq_decode(codes, weights, style, Kc, out=None, z_out=(None, None, None)):
     return out
 
 
+def codes_row_bytes(T, Q, bits=10):
+    """Bytes of one row of pack_codes' buffer: 4 * ceil(ceil(T Q bits / 8) / 4) (fac_codes_row_bytes)."""
+    return int(_lib.load().fac_codes_row_bytes(int(T), int(Q), int(bits)))
+
+
+def _codes_desc(d, codes, what, B=None, T=None):
+    """Fills codes / codes_bs / codes_qs / n_q of a pack or unpack descriptor from three (B, n, T) int64 device tensors (any batch /
+    row stride, unit frame stride; None or n == 0 for an RVQ without quantizers) -> (B, T, Q)."""
+    if len(codes) != 3:
+        raise ValueError(f"{what}: codes is [prosody, content, residual], got {len(codes)} entries")
+    Q = 0
+    for r, c in enumerate(codes):
+        if c is None:
+            continue
+        if not isinstance(c, torch.Tensor) or not c.is_cuda:
+            raise _lib.FacodecHipError(f"{what}: codes must live on the GPU (got {getattr(c, 'device', type(c))}); there is no CPU path")
+        if c.dtype != torch.int64 or c.dim() != 3:
+            raise _lib.FacodecHipError(f"{what}: codes must be int64 (B, n, T), got {c.dtype} {tuple(c.shape)}")
+        if B is None:
+            B, T = c.shape[0], c.shape[2]
+        if c.shape[0] != B or c.shape[2] != T:
+            raise ValueError(f"{what}: RVQ {r} is {tuple(c.shape)} but the others have B = {B}, T = {T}")
+        n = c.shape[1]
+        if n == 0:
+            continue
+        if T > 1 and c.stride(2) != 1:
+            raise ValueError(f"{what}: codes need unit stride along time (RVQ {r} has {c.stride(2)})")
+        d.codes[r], d.codes_bs[r], d.codes_qs[r], d.n_q[r] = c.data_ptr(), c.stride(0), c.stride(1), n
+        Q += n
+    if B is None:
+        raise ValueError(f"{what}: no codes")
+    if not 1 <= Q <= _lib.VQ_DECODE_MAX_Q:
+        raise ValueError(f"{what}: {Q} quantizers in all (1..{_lib.VQ_DECODE_MAX_Q})")
+    return B, T, Q
+
+
+def _check_bits(bits, what):
+    if not isinstance(bits, int) or not 1 <= bits <= 16:
+        raise ValueError(f"{what}: bits = {bits!r} is outside 1..16")
+
+
+def pack_codes(codes, bits=10, lens=None, out=None):
+    """[codes_p, codes_c, codes_r] int64 (B, n, T) -> uint8 (B, row_bytes), the packed payload rows of DESIGN.md 24 (fac_codes_pack:
+    one store-only launch).  lens: (B,) int32 FRAMES on the device; row b then holds its min(lens[b], T) frames and zeros behind.
+    out: an optional uint8 (B, >= row_bytes) buffer with a row stride that is a multiple of 4; only [0, row_bytes) of each row is
+    written and the (B, row_bytes) view of it is returned."""
+    _check_bits(bits, "pack_codes")
+    d = _lib.CodesPackDesc()
+    B, T, Q = _codes_desc(d, codes, "pack_codes")
+    if B < 1 or T < 1:
+        raise ValueError(f"pack_codes: empty codes (B = {B}, T = {T})")
+    rb = codes_row_bytes(T, Q, bits)
+    dev = next(c for c in codes if c is not None).device
+    if out is None:
+        out = torch.empty(B, rb, device=dev, dtype=torch.uint8)
+    else:
+        if not out.is_cuda:
+            raise _lib.FacodecHipError(f"pack_codes: out must live on the GPU (got {out.device}); there is no CPU path")
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < rb or (B > 1 and out.stride(0) % 4) \
+                or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError(f"pack_codes: out must be uint8 ({B}, >= {rb}) with a row stride that is a multiple of 4, got {out.dtype} "
+                             f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.out, d.out_bs = out.data_ptr(), (out.stride(0) if B > 1 else rb)
+    d.B, d.T, d.bits = B, T, bits
+    _lib.check(_lib.load().fac_codes_pack(C.byref(d), _stream()), "fac_codes_pack")
+    return out[:, :rb]
+
+
+def unpack_codes(packed, n_q, T, bits=10, lens=None, out=None):
+    """uint8 (B, >= ceil(T Q bits / 8)) packed rows (any row stride and alignment) -> [codes_p, codes_c, codes_r] int64 (B, n_q[r], T)
+    (fac_codes_unpack: one launch); an RVQ with n_q[r] == 0 comes back as (B, 0, T).  lens: (B,) int32 frames on the device;
+    frames t >= lens[b] come back as code 0.  out: optional three int64 (B, n_q[r], T) tensors to write (strided views allowed)."""
+    _check_bits(bits, "unpack_codes")
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise _lib.FacodecHipError(f"unpack_codes: packed must live on the GPU (got {getattr(packed, 'device', type(packed))}); there is no CPU path")
+    if packed.dtype != torch.uint8 or packed.dim() != 2:
+        raise _lib.FacodecHipError(f"unpack_codes: packed must be uint8 (B, bytes), got {packed.dtype} {tuple(packed.shape)}")
+    n_q = tuple(int(n) for n in n_q)
+    T = int(T)
+    if len(n_q) != 3 or min(n_q) < 0 or not 1 <= sum(n_q) <= _lib.VQ_DECODE_MAX_Q:
+        raise ValueError(f"unpack_codes: n_q = {n_q} is not three counts with 1..{_lib.VQ_DECODE_MAX_Q} quantizers in all")
+    B, Q = packed.shape[0], sum(n_q)
+    if B < 1 or T < 1:
+        raise ValueError(f"unpack_codes: empty input (B = {B}, T = {T})")
+    need = (T * Q * bits + 7) // 8
+    if packed.shape[1] < need:
+        raise ValueError(f"unpack_codes: packed rows of {packed.shape[1]} bytes are too short for T = {T}, Q = {Q}, bits = {bits} ({need} bytes)")
+    if packed.shape[1] > 1 and packed.stride(1) != 1:
+        packed = packed.contiguous()
+    if out is None:
+        out = [torch.empty(B, n, T, device=packed.device, dtype=torch.int64) for n in n_q]
+    d = _lib.CodesUnpackDesc()
+    _codes_desc(d, out, "unpack_codes", B, T)
+    if tuple(d.n_q) != n_q:
+        raise ValueError(f"unpack_codes: out has {tuple(d.n_q)} rows, n_q = {n_q}")
+    d.in_, d.in_bs = packed.data_ptr(), (packed.stride(0) if B > 1 else packed.shape[1])
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.B, d.T, d.bits = B, T, bits
+    _lib.check(_lib.load().fac_codes_unpack(C.byref(d), _stream()), "fac_codes_unpack")
+    return list(out)
+
+
 def vq_loss_tiles(T):
     """Row length of `vq_step`'s loss_part buffer (one partial sum per time tile of the kernel)."""
     return int(_lib.load().fac_vq_loss_tiles(int(T)))

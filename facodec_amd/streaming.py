@@ -1037,3 +1037,87 @@ class ResampledSession:
 
     def set_target(self, timbre):
         return self.session.set_target(timbre)
+
+
+# ------------------------------------------------------------------------------------ what travels between the two halves
+class CodePacketizer:
+    """Sender side of the link between StreamingCodec / StreamingConverter and StreamingDecoder: every push's codes as bytes.
+
+        tx = CodePacketizer(n_q=(1, 2, 3))                   # quantizer counts of the codes that will be sent
+        headers = tx.header(timbre)                          # once: one stream-header blob per stream (timbre (B, 1024) or None)
+        packets = tx.packet(out["codes"])                    # every call that returned codes: one packet per stream
+
+    packet() is one ops.pack_codes launch on the current stream and one device-to-host copy of the packed rows ((B, 4 ceil(k Q
+    bits / 32)) bytes instead of three int64 tensors); the codes may be a session's static graph buffers, they are read before
+    packet() returns.  It sits outside the captured graphs.  A packet is b"FP", seq uint16 (wrapping, the same for all streams
+    of a push), n_frames uint16, ceil(k Q bits / 8) payload bytes, CRC-32 (bitstream.write_packet).  codes with fewer entries
+    than three (StreamingConverter emits [p, c]) stand for n_q with trailing zeros."""
+
+    def __init__(self, n_q, bits=10, codebook_size=1024):
+        from . import bitstream
+        self.n_q = tuple(int(n) for n in n_q) + (0,) * (3 - len(n_q))
+        bitstream._check_layout(bits, self.n_q, "CodePacketizer")
+        self.bits, self.codebook_size, self.seq = int(bits), int(codebook_size), 0
+
+    def header(self, timbre=None):
+        from . import bitstream
+        if not isinstance(timbre, torch.Tensor) or timbre.dim() != 2:
+            raise ValueError("header(timbre): the receiver takes its timbre from the stream header; pass the session's (B, dim) tensor")
+        _check_timbre(timbre, None, timbre.shape[1], "timbre")
+        tim = timbre.detach().cpu().numpy()
+        head = dict(bits=self.bits, n_q=self.n_q, sample_rate=MODEL_RATE, n_frames=0, n_samples=0,
+                    codebook_size=self.codebook_size, timbre_dim=tim.shape[1], stream=True)
+        return [bitstream.write(head, tim[b].tobytes(), b"") for b in range(tim.shape[0])]
+
+    def packet(self, codes):
+        from . import bitstream
+        codes = list(codes) + [None] * (3 - len(codes))
+        got = tuple(0 if c is None else int(c.shape[1]) for c in codes)
+        if got != self.n_q:
+            raise ValueError(f"codes with {got} rows, the packetizer was built for n_q = {self.n_q}")
+        k = next(c for c in codes if c is not None).shape[-1]
+        rows = ops.pack_codes(codes, bits=self.bits).cpu().numpy()
+        n = bitstream.payload_bytes(k, sum(self.n_q), self.bits)
+        seq, self.seq = self.seq, (self.seq + 1) & 0xFFFF
+        return [bitstream.write_packet(seq, k, rows[b, :n].tobytes()) for b in range(rows.shape[0])]
+
+
+class CodeDepacketizer:
+    """Receiver side: stream headers and packets in, code tensors for StreamingDecoder out.
+
+        rx_codes = CodeDepacketizer(headers)                 # .timbre (B, dim) on the device, .n_q, .bits, .codebook_size
+        rx = StreamingDecoder(model, rx_codes.timbre)
+        wave = rx.prime(rx_codes.feed(packets))              # then rx.push(rx_codes.feed(packets)) per push
+
+    feed() checks the packets on the host (bitstream.PacketReader: CRC, equal n_frames and seq across the streams, the
+    sequence), then makes one host-to-device copy of the payload rows and one ops.unpack_codes launch -> [p, c, r] (B, n, k)
+    int64.  ValueError for a corrupt packet or streams that disagree; bitstream.PacketLoss(missing=n) for a gap in the sequence,
+    after which the same packets are accepted when fed again.  Nothing is concealed: what to play for lost frames is the
+    caller's decision (StreamingDecoder has no notion of a missing push)."""
+
+    def __init__(self, header_blobs, device="cuda"):
+        import numpy as np
+        from . import bitstream
+        parsed = [bitstream.read(b) for b in header_blobs]
+        if not parsed:
+            raise ValueError("no stream headers")
+        for i, (h, tim, _) in enumerate(parsed):
+            if not h.is_stream_header:
+                raise ValueError(f"blob {i} is a clip, not a stream header (commons.decompress reads those)")
+            if tim is None:
+                raise ValueError(f"stream header {i} carries no timbre")
+        h0 = parsed[0][0]
+        if any((h.n_q, h.bits, h.codebook_size, h.timbre_dim) != (h0.n_q, h0.bits, h0.codebook_size, h0.timbre_dim) for h, _, _ in parsed):
+            raise ValueError("the stream headers disagree on (n_q, bits, codebook_size, timbre_dim)")
+        self.n_q, self.bits, self.codebook_size, self.B = h0.n_q, h0.bits, h0.codebook_size, len(parsed)
+        self.device = torch.device(device)
+        self.timbre = ops.h2d(torch.from_numpy(np.stack([tim for _, tim, _ in parsed])), self.device)
+        self.reader = bitstream.PacketReader(self.B, h0.Q, h0.bits)
+
+    def feed(self, packets):
+        import numpy as np
+        k, payloads = self.reader.feed(packets)
+        if k < 1:
+            raise ValueError("a packet without frames")
+        rows = np.stack([np.frombuffer(p, dtype=np.uint8) for p in payloads])
+        return ops.unpack_codes(ops.h2d(torch.from_numpy(rows), self.device), self.n_q, k, bits=self.bits)

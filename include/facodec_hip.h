@@ -629,6 +629,58 @@ typedef struct fac_vq_decode_desc {
 
 int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Packed codes: the payload of the bitstream (csrc/bitpack.hip).  This comment is the normative layout.
+ *
+ * One clip of F frames with quantizer counts (n_p, n_c, n_r), Q = n_p + n_c + n_r in 1..FAC_VQ_DECODE_MAX_Q, and a field
+ * width `bits` in 1..16 (default ceil(log2(codebook_size)), 10 for the shipped model) is the little-endian byte string of
+ *     N = sum over t < F, q < Q of  (code[q][t] & (2^bits - 1)) << (bits * (t * Q + q))
+ *     payload = N.to_bytes(ceil(F * Q * bits / 8), "little")
+ * Frame-major; within a frame the fields run in quantizer order (prosody rows, content rows, residual rows); fields are
+ * LSB-first with no padding between fields or frames; the unused high bits of the last byte are 0.  Any run of whole frames
+ * is therefore a self-contained bit range (k frames of the shipped model: ceil(60 k / 8) bytes).
+ *   bits = 10, p = [1], c = [2, 3], r = [4, 5, 1023], F = 1          ->  01 08 30 00 01 05 fc 0f
+ *   ... then a frame p = [512], c = [0, 1], r = [1000, 7, 341]       ->  01 08 30 00 01 05 fc 0f 20 00 01 a0 7f 40 55
+ *
+ * Device buffer: (B, row_bytes) uint8 with row_bytes = fac_codes_row_bytes(T, Q, bits) = 4 * ceil(ceil(T Q bits / 8) / 4),
+ * whole 32-bit words.  With lens ((B,) int32 FRAMES on the device, never read on the host, clamped to [0, T]) row b holds
+ * its clip's min(lens[b], T) frames and every bit behind them up to row_bytes is 0.
+ *
+ * fac_codes_pack is store-only: one thread per 32-bit output word gathers the fields that overlap it, each masked to `bits`
+ * (a code outside [0, 2^bits) cannot disturb its neighbours), and writes the word once -- no atomics, no read of `out`.
+ * Every word of [0, row_bytes) of every row is written; nothing outside, the gap up to out_bs included.
+ * fac_codes_unpack is the inverse: it reads `in` byte by byte (at most 3 per field; no alignment of `in` or in_bs assumed)
+ * and writes every code of the (B, n_q[r], T) tensors, code 0 for frames t >= lens[b].  Neither checks code VALUES (validate
+ * on the host, as everywhere else).  Both refuse, before any launch: bits outside 1..16, Q outside 1..16, a NULL code
+ * pointer with n_q > 0, a row stride that is too small (pack: or no multiple of 4), B or T < 1.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct fac_codes_pack_desc {
+  const int64_t* codes[3];  /* as in fac_vq_decode_desc: codes[r][b*codes_bs[r] + i*codes_qs[r] + t]; NULL when n_q[r] == 0 */
+  int64_t codes_bs[3];
+  int64_t codes_qs[3];
+  int32_t n_q[3];
+  const int32_t* lens;      /* (B,) frames, or NULL (every row has T frames) */
+  uint8_t* out;             /* (B, out_bs) bytes, 4-byte aligned */
+  int64_t out_bs;           /* row stride in bytes: a multiple of 4, >= fac_codes_row_bytes(T, Q, bits) */
+  int32_t B, T, bits;
+} fac_codes_pack_desc;
+
+typedef struct fac_codes_unpack_desc {
+  const uint8_t* in;        /* (B, in_bs) bytes */
+  int64_t in_bs;            /* row stride in bytes, any value >= ceil(T Q bits / 8) */
+  int64_t* codes[3];        /* written: codes[r][b*codes_bs[r] + i*codes_qs[r] + t]; NULL when n_q[r] == 0 */
+  int64_t codes_bs[3];
+  int64_t codes_qs[3];
+  int32_t n_q[3];
+  const int32_t* lens;      /* (B,) frames, or NULL */
+  int32_t B, T, bits;
+} fac_codes_unpack_desc;
+
+int fac_codes_pack(const fac_codes_pack_desc* d, fac_stream_t stream);
+int fac_codes_unpack(const fac_codes_unpack_desc* d, fac_stream_t stream);
+/* Bytes of one row of the device buffer (host helper); -1 for a non-positive argument. */
+int64_t fac_codes_row_bytes(int T, int Q, int bits);
+
 /* Nearest-code search only, on already-projected latents (N, 8) row-major -> idx (N) int64.
  * The isolated kernel of dac/nn/quantize.py:78-94 / quantize/fvq.py:101-116. */
 int fac_vq_search(const float* latents, const float* codebook, int64_t* idx, int64_t N, int Kc,
