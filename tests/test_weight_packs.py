@@ -30,7 +30,9 @@ own norm rounded to a power of two times a random factor in [0.5, 1.5), so scale
 Cases are the smallest at which each index path exists, not model shapes (tables below; every id names what it reaches).
 
 Left out, on purpose:
-  * the LSTM packs (fac_pack_lstm_whh*): no scale, no padding, and the fp64 LSTM tests fail on any misplacement;
+  * the LSTM packs: no scale, no padding.  fac_pack_lstm_whh, _whh16 and _whh_t feed the fp64 LSTM table of
+    tests/test_train_kernels_gen.py, which fails on any misplacement; fac_pack_lstm_whh_split, which that table does not run, is
+    pinned bit for bit to its documented layout in tests/test_lstm_split.py (with `_split3` and the 0xFF buffer of this file);
   * the grid-stride path past 65 535 workgroups of the one-thread-per-slot packers: it needs an 800 MB pack and no model shape
     reaches it."""
 import ctypes as C
