@@ -83,6 +83,16 @@ class ResampleDesc(C.Structure):
     ]
 
 
+class KweightDesc(C.Structure):
+    _fields_ = [
+        ("x", _p), ("lens", _p), ("e", _p), ("state_in", _p), ("state_out", _p), ("peak", _p), ("ws", _p),
+        ("x_bs", _i64), ("e_bs", _i64),
+        ("B", C.c_int32), ("T", C.c_int32), ("S", C.c_int32), ("offset", C.c_int32), ("peak_accumulate", C.c_int32),
+        ("reserved", C.c_int32),
+        ("coef", C.c_double * 10), ("pw", C.c_double * 16 * 7),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/facodec_hip.h declares
 SIGNATURES = {
     "fac_version": (_i, []),
@@ -225,6 +235,11 @@ SIGNATURES = {
     "fac_frame_mask": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_resample": (_i, [C.POINTER(ResampleDesc), _p]),
     "fac_resample_form": (_i, [C.POINTER(ResampleDesc), _p]),
+    "fac_kweight_ws_bytes": (_i64, [_i, _i]),
+    "fac_kweight_energy": (_i, [C.POINTER(KweightDesc), _p]),
+    "fac_loudness_chunk": (_i, [_i]),
+    "fac_loudness_gate": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _i, _p, _p, _i, _p]),
+    "fac_loudness_gain": (_i, [_p, _i64, _p, _p, _p, _p, C.c_double, _i, _p, _i64, _p, _i, _i, _p]),
     "fac_spec_power": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_reduce_pair": (_i, [_p, _p, _p, _p, _i64, _i, _f, _f, _i, _p]),
     "fac_aa_snakebeta_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

@@ -8,9 +8,10 @@ Container, everything little-endian:
      4  B   version = 1      16  I  n_frames F
      5  B   bits             20  I  n_samples (original length at sample_rate; informational)
      6  3B  n_p, n_c, n_r    24  I  codebook_size
-     9  B   flags (bit0: timbre present, bit1: stream header)
+     9  B   flags (bit0: timbre present, bit1: stream header, bit2: input loudness present)
     10  H   timbre_dim       28  I  reserved = 0
     32      timbre, fp32 x timbre_dim (absent when bit0 = 0)
+    ..  f   input_db, fp32: the integrated loudness (LUFS) the audio had before compress levelled it (absent when bit2 = 0)
     ..      payload, ceil(F Q bits / 8) bytes
     ..  I   CRC-32 of every preceding byte
 
@@ -26,7 +27,7 @@ import numpy as np
 
 MAGIC = b"FACB"
 VERSION = 1
-FLAG_TIMBRE, FLAG_STREAM = 1, 2
+FLAG_TIMBRE, FLAG_STREAM, FLAG_LOUDNESS = 1, 2, 4
 MAX_Q = 16                                   # FAC_VQ_DECODE_MAX_Q
 _HEAD = struct.Struct("<4sBB3BBHIIIII")
 HEADER_BYTES = _HEAD.size                    # 32
@@ -37,7 +38,9 @@ _PHEAD = struct.Struct("<2sHH")
 PACKET_OVERHEAD = _PHEAD.size + 4            # 10 bytes around the payload
 
 
-class Header(namedtuple("Header", "version bits n_p n_c n_r flags timbre_dim sample_rate n_frames n_samples codebook_size")):
+class Header(namedtuple("Header", "version bits n_p n_c n_r flags timbre_dim sample_rate n_frames n_samples codebook_size input_db",
+                        defaults=(None,))):
+    """input_db: the float32 behind the timbre when flag bit2 is set, else None."""
     __slots__ = ()
 
     @property
@@ -55,6 +58,10 @@ class Header(namedtuple("Header", "version bits n_p n_c n_r flags timbre_dim sam
     @property
     def is_stream_header(self):
         return bool(self.flags & FLAG_STREAM)
+
+    @property
+    def has_loudness(self):
+        return bool(self.flags & FLAG_LOUDNESS)
 
 
 class PacketLoss(Exception):
@@ -85,8 +92,9 @@ def _check_layout(bits, n_q, what):
 
 def write(header_fields, timbre_bytes, payload):
     """One container blob.  header_fields: a mapping (or Header) with bits, n_p, n_c, n_r (or n_q = the three), sample_rate,
-    n_frames, n_samples, codebook_size, optionally timbre_dim (else the timbre's length) and stream (flag bit1); version, flags
-    and the reserved word are written here.  timbre_bytes: timbre_dim float32 values as bytes (or a float32 array), or None.
+    n_frames, n_samples, codebook_size, optionally timbre_dim (else the timbre's length), stream (flag bit1) and input_db (a
+    number: flag bit2 and one float32 behind the timbre; None or absent: neither, the blob of before); version, flags and the
+    reserved word are written here.  timbre_bytes: timbre_dim float32 values as bytes (or a float32 array), or None.
     payload: exactly payload_bytes(n_frames, Q, bits) bytes."""
     h = header_fields._asdict() if isinstance(header_fields, Header) else dict(header_fields)
     n_q = tuple(h["n_q"]) if "n_q" in h else (h["n_p"], h["n_c"], h["n_r"])
@@ -98,6 +106,10 @@ def write(header_fields, timbre_bytes, payload):
     if len(timbre_bytes) % 4:
         raise ValueError(f"bitstream.write: a timbre of {len(timbre_bytes)} bytes is no whole number of float32 values")
     flags = (FLAG_TIMBRE if timbre_bytes else 0) | (FLAG_STREAM if h.get("stream") or h.get("flags", 0) & FLAG_STREAM else 0)
+    loud = b""
+    if h.get("input_db") is not None:
+        flags |= FLAG_LOUDNESS
+        loud = struct.pack("<f", float(h["input_db"]))
     dim = int(h.get("timbre_dim") or len(timbre_bytes) // 4)
     if timbre_bytes and len(timbre_bytes) != 4 * dim:
         raise ValueError(f"bitstream.write: timbre of {len(timbre_bytes) // 4} values, timbre_dim = {dim}")
@@ -107,7 +119,7 @@ def write(header_fields, timbre_bytes, payload):
         raise ValueError(f"bitstream.write: payload of {len(payload)} bytes, {F} frames x {sum(n_q)} x {bits} bits need "
                          f"{payload_bytes(F, sum(n_q), bits)}")
     body = _HEAD.pack(MAGIC, VERSION, bits, *n_q, flags, dim, int(h["sample_rate"]), F, int(h["n_samples"]),
-                      int(h["codebook_size"]), 0) + timbre_bytes + payload
+                      int(h["codebook_size"]), 0) + timbre_bytes + loud + payload
     return body + struct.pack("<I", zlib.crc32(body))
 
 
@@ -127,10 +139,10 @@ def read(blob):
     hdr = Header(version, bits, n_p, n_c, n_r, flags, dim, rate, F, n_samples, cb)
     if reserved != 0:
         raise ValueError(f"bitstream: reserved word is {reserved:#x}, not 0")
-    if flags & ~(FLAG_TIMBRE | FLAG_STREAM):
+    if flags & ~(FLAG_TIMBRE | FLAG_STREAM | FLAG_LOUDNESS):
         raise ValueError(f"bitstream: unknown flags {flags:#x}")
     _check_layout(bits, hdr.n_q, "bitstream")
-    n_t = 4 * dim if hdr.has_timbre else 0
+    n_t = (4 * dim if hdr.has_timbre else 0) + (4 if hdr.has_loudness else 0)
     n_p_bytes = payload_bytes(F, hdr.Q, bits)
     want = HEADER_BYTES + n_t + n_p_bytes + 4
     if len(blob) < want:
@@ -141,6 +153,8 @@ def read(blob):
     if zlib.crc32(blob[:want - 4]) != crc:
         raise ValueError("bitstream: CRC mismatch (corrupt blob)")
     timbre = np.frombuffer(blob, dtype="<f4", count=dim, offset=HEADER_BYTES).copy() if hdr.has_timbre else None
+    if hdr.has_loudness:
+        hdr = hdr._replace(input_db=struct.unpack_from("<f", blob, HEADER_BYTES + n_t - 4)[0])
     return hdr, timbre, blob[HEADER_BYTES + n_t:want - 4]
 
 

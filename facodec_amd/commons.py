@@ -557,21 +557,34 @@ def code_bits(model):
     return max(1, (model.quantizer.prosody_quantizer.codebook_size - 1).bit_length())
 
 
-def _blobs_from_codes(model, codes, timbre, frames, sample_rate, n_samples, lens=None):
+def _blobs_from_codes(model, codes, timbre, frames, sample_rate, n_samples, lens=None, input_db=None):
     """codes [p, c, r] (B, n, T) int64 on the device (strided views welcome) -> B container blobs: one ops.pack_codes launch, one
     device-to-host copy of the uint8 rows (and one of the timbres, when they are stored), then host slicing to every clip's own
     payload_bytes.  frames[b] / n_samples[b]: clip b's frame count and original length; lens: the frame counts on the device
-    when they differ."""
+    when they differ.  input_db (B,) float64 on the device, or None: the loudness the clips had before they were levelled; it
+    rides as one float32 behind every packed row, in the same copy, and goes into the blob (flag bit2)."""
+    import numpy as np
     from . import bitstream, ops
     bits = code_bits(model)
     n_q = tuple(int(c.shape[1]) for c in codes)
-    rows = ops.pack_codes(codes, bits=bits, lens=lens).cpu().numpy()
+    loud = None
+    if input_db is None:
+        rows = ops.pack_codes(codes, bits=bits, lens=lens).cpu().numpy()
+    else:
+        B, T = codes[0].shape[0], codes[0].shape[-1]
+        rb = ops.codes_row_bytes(T, sum(n_q), bits)
+        buf = torch.empty(B, rb + 4, device=input_db.device, dtype=torch.uint8)
+        ops.pack_codes(codes, bits=bits, lens=lens, out=buf)
+        buf[:, rb:].view(torch.float32).copy_(input_db.reshape(B, 1))
+        rows = buf.cpu().numpy()
+        loud = np.ascontiguousarray(rows[:, rb:]).view("<f4").reshape(B)
     tim = timbre.detach().to(torch.float32).cpu().numpy() if timbre is not None else None
     q = model.quantizer
     out = []
     for b, F in enumerate(frames):
         head = dict(bits=bits, n_q=n_q, sample_rate=sample_rate, n_frames=F, n_samples=n_samples[b],
-                    codebook_size=q.prosody_quantizer.codebook_size, timbre_dim=q.in_dim)
+                    codebook_size=q.prosody_quantizer.codebook_size, timbre_dim=q.in_dim,
+                    input_db=float(loud[b]) if loud is not None else None)
         out.append(bitstream.write(head, tim[b].tobytes() if tim is not None else None,
                                    rows[b, :bitstream.payload_bytes(F, sum(n_q), bits)].tobytes()))
     return out
@@ -584,7 +597,7 @@ def _check_n_r(model, n_r):
 
 
 @torch.no_grad()
-def compress(model, wave, n_c=2, n_r=3, with_timbre=True, sample_rate=MODEL_RATE, quality="best"):
+def compress(model, wave, n_c=2, n_r=3, with_timbre=True, sample_rate=MODEL_RATE, quality="best", normalize_db=None):
     """Audio -> bytes.  wave (B, 1, T) float32 on the GPU -> list of B container blobs (bitstream.py); one clip (T,) or (1, T)
     -> one blob.
 
@@ -595,7 +608,12 @@ def compress(model, wave, n_c=2, n_r=3, with_timbre=True, sample_rate=MODEL_RATE
     the first n_r residual rows only (the strided view codes_r[:, :n_r]: bitrate scalability, nothing is re-encoded).  One
     ops.pack_codes launch and one device-to-host copy of the packed rows per call.  with_timbre=False leaves the timbre out
     (decompress then needs timbre=).  sample_rate: the rate of `wave`; other than 24000 it is resampled first (ops.resample,
-    `quality`), and the header records the rate so that decompress returns audio at it."""
+    `quality`), and the header records the rate so that decompress returns audio at it.
+
+    normalize_db: None encodes the audio at the level it has.  A number levels it first, in the reference's order (dac/model/
+    base.py:166-180): resample to 24 kHz, measure the integrated loudness (ops.loudness), bring it to normalize_db LUFS, guard
+    the peak (ops.normalize_loudness), then encoder and quantizer -- the timbre is that of the levelled audio.  The measured
+    loudness travels to the host with the packed rows and is stored in the blob (Header.input_db); decompress restores it."""
     from . import ops
     _need_gpu([wave], "wave")
     _check_n_r(model, n_r)
@@ -611,19 +629,23 @@ def compress(model, wave, n_c=2, n_r=3, with_timbre=True, sample_rate=MODEL_RATE
     if sample_rate != MODEL_RATE:
         x = ops.resample(x, sample_rate, MODEL_RATE, quality=quality)
     _clip_lengths(model, [x[0, 0]], "wave")
+    input_db = None
+    if normalize_db is not None:
+        x, input_db, _ = ops.normalize_loudness(x, float(normalize_db), MODEL_RATE)
     out = model.quantizer(model.encoder(x), x, n_c=n_c, return_codes=True)
     timbre, codes = out[4], out[5]
     codes = [codes[0], codes[1], codes[2][:, :n_r]]
     F = codes[0].shape[-1]
-    blobs = _blobs_from_codes(model, codes, timbre if with_timbre else None, [F] * B, sample_rate, [n_in] * B)
+    blobs = _blobs_from_codes(model, codes, timbre if with_timbre else None, [F] * B, sample_rate, [n_in] * B, input_db=input_db)
     return blobs[0] if single else blobs
 
 
 @torch.no_grad()
 def compress_clips(model, waves, n_c=2, n_r=3, with_timbre=True, max_batch_samples=MAX_BATCH_SAMPLES, sample_rate=MODEL_RATE,
-                   quality="best"):
+                   quality="best", normalize_db=None):
     """Clips of different lengths -> one container blob per clip, in the caller's order: encode_clips' groups and forward, then
-    per group one ops.pack_codes launch with the group's frame counts as `lens` and one device-to-host copy."""
+    per group one ops.pack_codes launch with the group's frame counts as `lens` and one device-to-host copy.  normalize_db: as
+    in compress, every clip measured and levelled on its own samples (ops.normalize_loudness with the group's lengths)."""
     from . import ops
     _check_n_r(model, n_r)
     ratio = None
@@ -645,11 +667,14 @@ def compress_clips(model, waves, n_c=2, n_r=3, with_timbre=True, max_batch_sampl
         if ratio is not None:
             lens_in = ops.h2d(torch.tensor([waves[i].shape[-1] for i in group], dtype=torch.int32), dev)
             batch = ops.resample(batch, sample_rate, MODEL_RATE, lens=lens_in, quality=quality)
+        input_db = None
+        if normalize_db is not None:
+            batch, input_db, _ = ops.normalize_loudness(batch, float(normalize_db), MODEL_RATE, lens=lens)
         z = model.encoder(batch)
         _, codes, timbre, frame_lens = model.quantizer.forward_ragged(z, batch, lens, n_c=n_c)
         codes = [codes[0], codes[1], codes[2][:, :n_r]]
         blobs = _blobs_from_codes(model, codes, timbre if with_timbre else None, [lengths[i] // hop for i in group], sample_rate,
-                                  [int(waves[i].shape[-1]) for i in group], lens=frame_lens)
+                                  [int(waves[i].shape[-1]) for i in group], lens=frame_lens, input_db=input_db)
         for j, i in enumerate(group):
             out[i] = blobs[j]
     return out
@@ -719,7 +744,50 @@ def _blob_device(model):
 
 
 @torch.no_grad()
-def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MAX_BATCH_SAMPLES, quality="best"):
+def _restore_loudness(wave, headers, lens=None):
+    """The decoder's side of compress(normalize_db=): wave (B, 1, T) at 24 kHz, decoded from blobs with `headers`.  Rows whose
+    blob carries input_db are measured (ops.loudness, on their own lens[b] samples) and scaled by 10^((input_db - L_out) / 20), in
+    place and without a peak guard (dac/model/base.py:285); a row that measures -70 is left as it is, and so is a row without
+    the field.  One host-to-device copy of the targets, no host read."""
+    from . import ops
+    if not any(h.input_db is not None for h in headers):
+        return wave
+    target = ops.h2d(torch.tensor([h.input_db if h.input_db is not None else float("nan") for h in headers], dtype=torch.float64),
+                     wave.device)
+    L = ops.loudness(wave, MODEL_RATE, lens=lens)
+    ops.loudness_gain(wave, L, target_rows=target, lens=lens, guard=False, out=wave)
+    return wave
+
+
+@torch.no_grad()
+def loudness_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SAMPLES):
+    """Integrated loudness (ITU-R BS.1770-4, LUFS) of clips of different lengths -> list of floats in the caller's order.  The
+    clips (T_i,) or (1, T_i), float32 on the GPU at sample_rate (a multiple of 10), go through plan_groups' zero-padded groups
+    with their lengths: one ops.loudness call and one device-to-host copy per group; a clip measures what it measures alone,
+    whatever it is grouped with."""
+    from . import ops
+    ops._kweight_tables(sample_rate)                                # ValueError: the rate
+    waves = list(waves)
+    if not waves:
+        return []
+    _need_gpu(waves, "clips")
+    for w in waves:
+        if not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = [int(w.shape[-1]) for w in waves]
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), batch.device)
+        L = ops.loudness(batch, sample_rate, lens=lens).cpu().tolist()
+        for j, i in enumerate(group):
+            out[i] = L[j]
+    return out
+
+
+@torch.no_grad()
+def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MAX_BATCH_SAMPLES, quality="best",
+               restore_loudness=True):
     """Bytes -> audio: a list of container blobs -> list of waves (1, N_i) in the caller's order; one blob -> one wave.
 
     The headers are read on the host (bitstream.read: magic, version, length, CRC), the blobs grouped by their layout
@@ -727,7 +795,10 @@ def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MA
     ops.unpack_codes launch with the clips' frame counts, then decode_clips' path (decode_codes on the padded batch, every wave
     cropped to its clip).  timbre: overrides the stored timbres (timbre swap): one vector for all blobs or one per blob;
     required for blobs written with with_timbre=False.  sample_rate: None gives every clip back at its header's rate; a value
-    resamples every clip to it.  A header whose codebook_size or timbre_dim is not the model's raises ValueError."""
+    resamples every clip to it.  A header whose codebook_size or timbre_dim is not the model's raises ValueError.
+    restore_loudness: a blob written with compress(normalize_db=) carries the loudness its audio had; the decoded 24 kHz audio
+    is measured and brought back to it before resampling and cropping (_restore_loudness; blobs with and without the field may
+    be mixed, the gain is per row).  False returns the audio at the level it was encoded at."""
     from . import ops
     single = isinstance(blobs, (bytes, bytearray, memoryview))
     blobs = [blobs] if single else list(blobs)
@@ -756,8 +827,12 @@ def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MA
             headers = [parsed[i][0] for i in group]
             codes = _codes_from_payloads(headers, [parsed[i][2] for i in group], dev, len({h.n_frames for h in headers}) > 1)
             wave = decode_codes(model, codes, timbres if group == list(range(len(blobs))) else timbres[group])
-            if ratio is not None:
+            lens = None
+            if ratio is not None or (restore_loudness and any(h.input_db is not None for h in headers)):
                 lens = ops.h2d(torch.tensor([h.n_frames * hop for h in headers], dtype=torch.int32), dev)
+            if restore_loudness:
+                wave = _restore_loudness(wave, headers, lens)
+            if ratio is not None:
                 wave = ops.resample(wave, MODEL_RATE, rate, lens=lens, quality=quality)
             for j, i in enumerate(group):
                 n = headers[j].n_frames * hop
@@ -766,20 +841,30 @@ def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MA
 
 
 @torch.no_grad()
-def compress_long(model, wave, n_c=2, n_r=3, with_timbre=True, chunk_seconds=LONG_CHUNK_SECONDS, timbre=None, timbre_seconds=None):
+def compress_long(model, wave, n_c=2, n_r=3, with_timbre=True, chunk_seconds=LONG_CHUNK_SECONDS, timbre=None, timbre_seconds=None,
+                  normalize_db=None):
     """encode_long into the container: wave (B, 1, T) float32 on the GPU at 24 kHz, any length -> list of B blobs.  The whole
-    code stream of the recording is packed by one ops.pack_codes launch (64-bit bit offsets) and copied to the host once."""
+    code stream of the recording is packed by one ops.pack_codes launch (64-bit bit offsets) and copied to the host once.
+    normalize_db: as in compress; the loudness is that of the whole recording, and the levelled recording is ONE extra copy of
+    it (one float per sample) that lives until the codes are packed -- the chunks are cut from it."""
+    from . import ops
     _check_n_r(model, n_r)
+    input_db = None
+    if normalize_db is not None:
+        _long_wave(model, wave, "wave")
+        wave, input_db, _ = ops.normalize_loudness(wave, float(normalize_db), MODEL_RATE)
     enc = encode_long(model, wave, n_c=n_c, chunk_seconds=chunk_seconds, timbre=timbre, timbre_seconds=timbre_seconds)
     codes = [enc["codes"][0], enc["codes"][1], enc["codes"][2][:, :n_r]]
     B, F = wave.shape[0], codes[0].shape[-1]
-    return _blobs_from_codes(model, codes, enc["timbre"] if with_timbre else None, [F] * B, MODEL_RATE, [int(wave.shape[-1])] * B)
+    return _blobs_from_codes(model, codes, enc["timbre"] if with_timbre else None, [F] * B, MODEL_RATE, [int(wave.shape[-1])] * B,
+                             input_db=input_db)
 
 
 @torch.no_grad()
-def decompress_long(model, blobs, timbre=None, chunk_seconds=LONG_CHUNK_SECONDS):
+def decompress_long(model, blobs, timbre=None, chunk_seconds=LONG_CHUNK_SECONDS, restore_loudness=True):
     """Blobs of compress_long (equal frame counts and one layout, as one recording batch has) -> (B, 1, 300 F) through decode_long:
-    one host-to-device copy and one ops.unpack_codes launch for the whole code stream, then the chunked decoder."""
+    one host-to-device copy and one ops.unpack_codes launch for the whole code stream, then the chunked decoder.
+    restore_loudness: as in decompress, on the whole decoded recording, in place."""
     blobs = [blobs] if isinstance(blobs, (bytes, bytearray, memoryview)) else list(blobs)
     parsed = _parse_blobs(model, blobs)
     headers = [h for h, _, _ in parsed]
@@ -789,7 +874,8 @@ def decompress_long(model, blobs, timbre=None, chunk_seconds=LONG_CHUNK_SECONDS)
     dev = timbre.device if isinstance(timbre, torch.Tensor) else _blob_device(model)
     timbres = _timbres_for(model, parsed, timbre, dev)
     codes = _codes_from_payloads(headers, [p for _, _, p in parsed], dev, False)
-    return decode_long(model, codes, timbres, chunk_seconds=chunk_seconds)
+    wave = decode_long(model, codes, timbres, chunk_seconds=chunk_seconds)
+    return _restore_loudness(wave, headers) if restore_loudness else wave
 
 
 def load_checkpoint(model, optimizer, path, load_only_params=True, ignore_modules=(), is_distributed=False):

@@ -179,3 +179,52 @@ def resample_table(rate_in, rate_out, quality="best"):
     _RESAMPLE_TABLES[key] = out
     return out
 
+
+
+# ------------------------------------------------------------------------------------ loudness
+def k_weighting(rate):
+    """The two K-weighting sections of ITU-R BS.1770-4 designed for `rate` in float64: -> ((b, a) shelf, (b, a) high-pass), each a
+    pair of (3,) float64 arrays with a[0] = 1 (the high-pass numerator is [1, -2, 1], not normalised, as in the standard).  At
+    48000 this is the standard's coefficient table.  ValueError when the rate is no whole number of 100 ms sub-blocks."""
+    if isinstance(rate, bool) or int(rate) != rate or rate <= 0:
+        raise ValueError(f"k_weighting: rate = {rate!r} is no positive integer")
+    rate = int(rate)
+    if rate % 10:
+        raise ValueError(f"k_weighting: {rate} Hz is no whole number of samples per 100 ms sub-block; resample first "
+                         "(ops.resample) to a rate that is a multiple of 10")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / rate)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    d = 1.0 + K / Q + K * K
+    shelf = (np.array([(Vh + Vb * K / Q + K * K) / d, 2.0 * (K * K - Vh) / d, (Vh - Vb * K / Q + K * K) / d]),
+             np.array([1.0, 2.0 * (K * K - 1.0) / d, (1.0 - K / Q + K * K) / d]))
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / rate)
+    d = 1.0 + K / Q + K * K
+    high = (np.array([1.0, -2.0, 1.0]), np.array([1.0, 2.0 * (K * K - 1.0) / d, (1.0 - K / Q + K * K) / d]))
+    return shelf, high
+
+
+def k_weighting_transitions(rate, chunk, n=7):
+    """What fac_kweight_energy takes beside the signal: coef (10,) = [b0 b1 b2 a1 a2 | c0 c1 c2 d1 d2] and pw (n, 16), pw[k] the
+    row-major 4 x 4 matrix M^(chunk 2^k), M the zero-input step of both sections in transposed direct form II on the state
+    (s1, s2, t1, t2) (include/facodec_hip.h).  float64, by repeated squaring."""
+    (b, a), (c, d) = k_weighting(rate)
+    coef = np.concatenate([b, a[1:], c, d[1:]])
+    M = np.array([[-a[1], 1.0, 0.0, 0.0],
+                  [-a[2], 0.0, 0.0, 0.0],
+                  [c[1] - d[1] * c[0], 0.0, -d[1], 1.0],
+                  [c[2] - d[2] * c[0], 0.0, -d[2], 0.0]])
+    if chunk < 1 or chunk & (chunk - 1):
+        raise ValueError(f"k_weighting_transitions: chunk = {chunk} is no power of two")
+    # the high-pass has a double pole near z = 1 (radius 0.990 at 24 kHz), which amplifies rounding by ~1 / (1 - r)^2: square in
+    # extended precision where the platform has it and round once
+    P = M.astype(np.longdouble)
+    for _ in range(chunk.bit_length() - 1):
+        P = P @ P
+    pw = []
+    for _ in range(n):
+        pw.append(P.astype(np.float64).reshape(16))
+        P = P @ P
+    return coef, np.stack(pw)

@@ -1471,6 +1471,170 @@ def resample(x, rate_in, rate_out, lens=None, quality="best"):
     return y
 
 
+# --------------------------------------------------------------------------------- loudness
+_KWEIGHT = {}
+LoudnessEnergies = namedtuple("LoudnessEnergies", "e peak state")
+
+
+def loudness_chunk():
+    """Samples per chunk of fac_kweight_energy: a row is filtered in chunks of this length, whose states are handed across by a
+    scan inside groups of loudness_chunk_group() chunks and a serial scan across those groups."""
+    return _lib.load().fac_loudness_chunk(0)
+
+
+def loudness_chunk_group():
+    """Chunks per workgroup of fac_kweight_energy (the unit of its serial scan)."""
+    return _lib.load().fac_loudness_chunk(1)
+
+
+def _kweight_tables(rate):
+    """-> (S, coef (10,), pw (7, 16)) float64 on the host, once per rate (dsp.k_weighting_transitions).  ValueError: the rate."""
+    hit = _KWEIGHT.get(rate)
+    if hit is None:
+        from . import dsp
+        coef, pw = dsp.k_weighting_transitions(rate, loudness_chunk())
+        hit = _KWEIGHT[rate] = (int(rate) // 10, coef, pw)
+    return hit
+
+
+def _rows(x, what):
+    """(B, T) or (B, 1, T) float32 on the device -> the (B, T) view with dense samples."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+        raise ValueError(f"{what} takes (B, T) or (B, 1, T), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    if not x.is_cuda:
+        raise _lib.FacodecHipError(f"{what}: x must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dtype != torch.float32:
+        raise _lib.FacodecHipError(f"{what}: x must be float32 (got {x.dtype})")
+    x2 = x.reshape(x.shape[0], x.shape[-1]) if x.dim() == 3 else x
+    return x2 if x2.shape[-1] <= 1 or x2.stride(-1) == 1 else x2.contiguous()
+
+
+def loudness_energies(x, rate=24000, lens=None, state=None, offset=0, out=None, peak=None, state_out=None, ws=None):
+    """K-weighted energies per 100 ms sub-block (fac_kweight_energy): x (B, T) or (B, 1, T) float32 -> LoudnessEnergies(e (B, n_sub)
+    float64, peak (B,) float32 = max |x|, state (B, 4) float64 or None), n_sub = ceil((offset + T) / S), S = rate / 10.  lens (B,)
+    int32 on the device: row b is its first lens[b] samples, the energies behind are zeros.
+
+    A stream continues with state= (B, 4) float64, the filter state the previous call returned (then `state` of the result is
+    the state after this call; not with lens), and offset = samples so far modulo S; with offset > 0 the first sub-block is
+    ADDED to out[:, 0].  out / peak / state_out / ws: preallocated buffers (out (B, >= n_sub) float64 with dense rows; peak
+    accumulates by maximum when given; state_out may be `state`; ws uint8 of fac_kweight_ws_bytes) -- the call then allocates
+    nothing."""
+    S, coef, pw = _kweight_tables(rate)                             # ValueError: fs % 10
+    x = _rows(x, "loudness_energies")
+    B, T = x.shape
+    if not 0 <= offset < S:
+        raise ValueError(f"loudness_energies: offset = {offset} outside 0 .. {S - 1}")
+    if lens is not None and (state is not None or state_out is not None or offset):
+        raise ValueError("loudness_energies: a carried state or an offset (a stream) does not go with lens")
+    n_sub = -(-(offset + T) // S)
+    dev = x.device
+    if out is None:
+        if offset:
+            raise ValueError("loudness_energies: offset > 0 adds to out[:, 0]; pass out=")
+        out = torch.empty(B, n_sub, device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_sub or (out.shape[1] > 1 and out.stride(1) != 1) \
+            or not out.is_cuda:
+        raise ValueError(f"loudness_energies: out must be float64 ({B}, >= {n_sub}) on the GPU with dense rows, got {out.dtype} {tuple(out.shape)}")
+    acc = peak is not None
+    if peak is None:
+        peak = torch.empty(B, device=dev, dtype=torch.float32)
+    if state is not None and state_out is None:
+        state_out = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    for t, name in ((state, "state"), (state_out, "state_out")):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (B, 4) or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"loudness_energies: {name} must be contiguous float64 ({B}, 4) on the GPU")
+    if B == 0:
+        return LoudnessEnergies(out[:, :n_sub], peak, state_out)
+    lib = _lib.load()
+    if T == 0:
+        if not acc:
+            peak.zero_()
+        if state is not None and state_out is not state:
+            state_out.copy_(state)
+        return LoudnessEnergies(out[:, :n_sub], peak, state_out)
+    need = lib.fac_kweight_ws_bytes(B, T)
+    if need < 0:
+        raise ValueError(f"loudness_energies: B = {B}, T = {T} (T up to 2^30 samples per call)")
+    if ws is None:
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    elif ws.numel() < need or ws.dtype != torch.uint8 or ws.data_ptr() % 8:
+        raise ValueError(f"loudness_energies: ws must be uint8, 8-byte aligned, of at least {need} bytes")
+    d = _lib.KweightDesc()
+    d.x, d.lens, d.e = x.data_ptr(), (_lens(lens, B).data_ptr() if lens is not None else None), out.data_ptr()
+    d.state_in = state.data_ptr() if state is not None else None
+    d.state_out = state_out.data_ptr() if state_out is not None else None
+    d.peak, d.ws = peak.data_ptr(), ws.data_ptr()
+    d.x_bs, d.e_bs = (x.stride(0) if B > 1 else T), (out.stride(0) if B > 1 else out.shape[1])
+    d.B, d.T, d.S, d.offset, d.peak_accumulate = B, T, S, offset, 1 if acc else 0
+    d.coef[:] = coef.tolist()
+    for k in range(7):
+        d.pw[k][:] = pw[k].tolist()
+    _lib.check(lib.fac_kweight_energy(C.byref(d), _stream()), "fac_kweight_energy")
+    return LoudnessEnergies(out[:, :n_sub], peak, state_out)
+
+
+def loudness_gate(e, n_samples, rate=24000, lens=None, last_n=0, peaks=None):
+    """fac_loudness_gate over energies e (B, >= ceil(n_samples / S)) float64: -> L (B,) float64, or (L, peak (B,) float32) with
+    peaks (B, n) float32.  last_n = 0: the two-gate integrated loudness of BS.1770-4; last_n > 0: the last last_n sub-blocks,
+    ungated (4: momentary, 30: short-term).  Never below -70."""
+    S = _kweight_tables(rate)[0]
+    B = e.shape[0]
+    if not e.is_cuda:
+        raise _lib.FacodecHipError(f"loudness_gate: e must live on the GPU (got {e.device}); there is no CPU path")
+    if e.dtype != torch.float64 or e.dim() != 2 or (e.shape[1] > 1 and e.stride(1) != 1) or e.shape[1] < -(-int(n_samples) // S):
+        raise ValueError(f"loudness_gate: e must be float64 (B, >= {-(-int(n_samples) // S)}) with dense rows, got {e.dtype} {tuple(e.shape)}")
+    L = torch.empty(B, device=e.device, dtype=torch.float64)
+    pk = None
+    if peaks is not None:
+        peaks = _dev(peaks.reshape(B, -1), "peaks")
+        pk = torch.empty(B, device=e.device, dtype=torch.float32)
+    if B == 0:
+        return L if peaks is None else (L, pk)
+    # a row without sub-blocks is never read; keep the pointer valid all the same
+    e_ptr = e if e.numel() else torch.zeros(1, device=e.device, dtype=torch.float64)
+    _lib.check(_lib.load().fac_loudness_gate(_ptr(e_ptr), e.stride(0) if B > 1 else e.shape[1], _ptr(_lens(lens, B) if lens is not None else None),
+                                             int(n_samples), S, int(last_n), _ptr(peaks), peaks.shape[1] if peaks is not None else 0,
+                                             _ptr(L), _ptr(pk), B, _stream()), "fac_loudness_gate")
+    return L if peaks is None else (L, pk)
+
+
+def loudness(x, rate=24000, lens=None):
+    """Integrated loudness of ITU-R BS.1770-4 for mono signals: x (B, T) or (B, 1, T) float32 -> (B,) float64 on the device, in
+    LUFS, -70.0 for silence, an empty clip or a clip no block of which passes the gates.  lens (B,) int32 on the device: row b is
+    x[b, :lens[b]] and measures what that slice measures alone.  Two C calls (fac_kweight_energy, fac_loudness_gate), no host
+    read.  ValueError for a rate that is no multiple of 10 (resample first)."""
+    en = loudness_energies(x, rate, lens=lens)
+    return loudness_gate(en.e, x.shape[-1], rate, lens=lens)
+
+
+def loudness_gain(x, L, peak=None, target_db=-16.0, target_rows=None, lens=None, guard=True, out=None):
+    """fac_loudness_gain: g from (L, target, peak) on the device, y = x * g on every row's samples and 0 behind lens -> (y, g (B,)
+    float32).  target_rows (B,) float64 replaces target_db per row (NaN: leave the row alone); guard=False skips the peak
+    guard; out may be x."""
+    x2 = _rows(x, "loudness_gain")
+    B, T = x2.shape
+    y = torch.empty_like(x2) if out is None else _rows(out, "loudness_gain")
+    g = torch.empty(B, device=x2.device, dtype=torch.float32)
+    if B and T:
+        _lib.check(_lib.load().fac_loudness_gain(_ptr(x2), x2.stride(0) if B > 1 else T, _ptr(_lens(lens, B) if lens is not None else None),
+                                                 _ptr(L), _ptr(peak), _ptr(target_rows), float(target_db), 1 if guard else 0,
+                                                 _ptr(y), y.stride(0) if B > 1 else T, _ptr(g), B, T, _stream()), "fac_loudness_gain")
+    elif B:
+        g.fill_(1.0)
+    return y.view(x.shape) if out is None else out, g
+
+
+def normalize_loudness(x, target_db=-16.0, rate=24000, lens=None):
+    """Level x to target_db LUFS as the reference's compress does (normalize, then ensure_max_of_audio): -> (y, input_db (B,)
+    float64, gain (B,) float32), all on the device and without a host read in between.  gain = 10^((target_db - input_db) / 20),
+    1 for a silent row (input_db = -70), 1 / max|x| where the levelled row would exceed full scale; y = x * gain in fp32 on every
+    row's own samples, zeros behind lens."""
+    en = loudness_energies(x, rate, lens=lens)
+    L = loudness_gate(en.e, x.shape[-1], rate, lens=lens)
+    y, g = loudness_gain(x, L, en.peak, target_db=target_db, lens=lens)
+    return y, L, g
+
+
 def spec_power(spec, power):
     B, f2, nf = spec.shape
     out = torch.empty(B, f2 // 2, nf, device=spec.device, dtype=torch.float32)

@@ -969,6 +969,68 @@ class StreamingResampler:
         return self._launch(self._hist[self._cur], self.delay, carry=False, T=0)
 
 
+class LoudnessMeter:
+    """The BS.1770-4 meter over B parallel streams, one block at a time:
+
+        meter = LoudnessMeter(B)                             # rate 24000
+        meter.push(block)                                    # (B, 1, k) or (B, k) float32 on the GPU, any k >= 1
+        meter.momentary(), meter.short_term(), meter.integrated()      # (B,) float64 on the device, LUFS
+
+    push is one fac_kweight_energy call that carries the filter state (fp64, updated in place) and the position inside the
+    current 100 ms sub-block, so the sub-block grid and the energies are those of the offline call on the whole signal (up to
+    fp64 rounding: chunk boundaries move with the blocks).  It reads nothing back to the host and, in the steady state,
+    allocates nothing: the energy history is a preallocated device buffer (8 bytes per stream and 100 ms) that doubles when it
+    is full, the scratch grows only with the largest block seen.  momentary() is the last 400 ms, short_term() the last 3 s,
+    both ungated and counting what lies before the stream's start as silence; integrated() is the two-gate loudness of
+    everything pushed so far.  `peak` holds max |x| so far.  A session's caller can level its input with it or watch its output;
+    the sessions themselves do not use it."""
+
+    def __init__(self, B, rate=MODEL_RATE, device="cuda", seconds=60):
+        self.S = ops._kweight_tables(rate)[0]                 # ValueError: the rate
+        self.B, self.rate, self.device = int(B), int(rate), torch.device(device)
+        self.samples = 0
+        self._e = torch.zeros(self.B, max(8, int(seconds) * 10), device=self.device, dtype=torch.float64)
+        self._state = torch.zeros(self.B, 4, device=self.device, dtype=torch.float64)
+        self.peak = torch.zeros(self.B, device=self.device, dtype=torch.float32)
+        self._ws = None
+
+    def push(self, block):
+        if not isinstance(block, torch.Tensor) or block.dim() not in (2, 3) or block.shape[0] != self.B or (block.dim() == 3 and block.shape[1] != 1):
+            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k), got {tuple(block.shape) if isinstance(block, torch.Tensor) else type(block)}")
+        k = block.shape[-1]
+        if k < 1:
+            raise ValueError("push() takes at least one sample")
+        j0, offset = divmod(self.samples, self.S)
+        n_sub = -(-(offset + k) // self.S)
+        if j0 + n_sub > self._e.shape[1]:
+            grown = torch.zeros(self.B, max(2 * self._e.shape[1], j0 + n_sub), device=self.device, dtype=torch.float64)
+            grown[:, :self._e.shape[1]] = self._e
+            self._e = grown
+        need = ops._lib.load().fac_kweight_ws_bytes(self.B, k)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 0), device=self.device, dtype=torch.uint8)
+        ops.loudness_energies(block, self.rate, state=self._state, offset=offset, out=self._e[:, j0:], peak=self.peak,
+                              state_out=self._state, ws=self._ws)
+        self.samples += k
+
+    @property
+    def energies(self):
+        """(B, ceil(samples / S)) float64: the sub-block energies so far (a view of the history buffer)."""
+        return self._e[:, :-(-self.samples // self.S)]
+
+    def _gate(self, last_n):
+        return ops.loudness_gate(self._e, self.samples, self.rate, last_n=last_n)
+
+    def momentary(self):
+        return self._gate(4)
+
+    def short_term(self):
+        return self._gate(30)
+
+    def integrated(self):
+        return self._gate(0)
+
+
 class ResampledSession:
     """A StreamingCodec / StreamingConverter / StreamingDecoder that takes its audio at `in_rate` and gives it at `out_rate`:
 

@@ -866,6 +866,77 @@ int fac_jdc_head(const float* h_fwd, const float* h_bwd, const float* w, const f
 int fac_f0_normalize(const float* f0, float* out, float* mean_out, int B, int T, fac_stream_t stream);
 int fac_mel_log_norm(const float* mel, float* out, int B, int n_mels, int T, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Loudness: the ITU-R BS.1770-4 meter for mono signals and the level normalisation built on it.
+ *
+ * Rate fs, S = fs / 10 samples per 100 ms sub-block (fs % 10 == 0).  K-weighting is two biquads designed on the host in fp64
+ * (facodec_amd/dsp.py k_weighting), a0 = 1:
+ *   stage 1, shelf:      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                        K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, d = 1 + K/Q + K^2,
+ *                        b = [(Vh + Vb K/Q + K^2)/d, 2 (K^2 - Vh)/d, (Vh - Vb K/Q + K^2)/d], a = [1, 2 (K^2 - 1)/d, (1 - K/Q + K^2)/d]
+ *   stage 2, high-pass:  f0 = 38.13547087602444, Q = 0.5003270373238773, same K, d;  b = [1, -2, 1] (not normalised, as in the
+ *                        standard), a = [1, 2 (K^2 - 1)/d, (1 - K/Q + K^2)/d]
+ * Energies: y = the clip's own len_b samples through both biquads from zero state (or from the carried state); nothing behind
+ * the clip's end is filtered.  e[b, j] = sum of y^2 over sub-block j, j < ceil(len_b / S), the last one possibly partial; fp64.
+ * Gating: block j = sub-blocks j .. j + 3, whole blocks only: n_blocks = (len_b - 4 S) / S + 1; a clip with 0 < len_b < 4 S counts
+ * as zero-padded to one block.  z_j = (e_j + .. + e_{j+3}) / (4 S), l_j = -0.691 + 10 log10 z_j.  Absolute gate l_j > -70;
+ * Gr = -0.691 + 10 log10(mean of z over the absolute-gated blocks) - 10; L = -0.691 + 10 log10(mean of z over the blocks with
+ * l_j > -70 and l_j > Gr).  No block passes, or len_b = 0: L = -70.  L is never below -70.
+ * Normalising to `target`: g = 10^((target - L) / 20); L <= -70 (silence): g = 1; peak guard: g * max|x| > 1 -> g = 1 / max|x|;
+ * y = x * g in fp32 with g rounded once to fp32.
+ *
+ * fac_kweight_energy.  The two biquads in transposed direct form II are one linear system on the state (s1, s2, t1, t2):
+ *     y1 = b0 x + s1;  s1' = (b1 x + s2) - a1 y1;  s2' = b2 x - a2 y1;     (stage 1: b = coef[0..2], a1, a2 = coef[3..4])
+ *     y  = c0 y1 + t1; t1' = (c1 y1 + t2) - d1 y;  t2' = c2 y1 - d2 y      (stage 2: c = coef[5..7], d1, d2 = coef[8..9])
+ * (every product-and-add one fma)
+ * so the time axis is cut into chunks of FAC_LOUDNESS_CHUNK samples, 64 chunks to a workgroup: (1) every chunk runs from zero
+ * state and the 64 end states of a workgroup are combined by a fixed 6-step scan with M^(chunk 2^k), k = 0 .. 5; (2) a short
+ * serial scan hands states across workgroups with M^(64 chunk); (3) every chunk re-runs from its true state and sums squares.
+ * pw[k] = M^(chunk 2^k), k = 0 .. 6, row-major 4 x 4 on (s1, s2, t1, t2), fp64, from the host.  Everything is fp64 and in a
+ * fixed order: results are bit-identical run to run.  The filtered signal is never written to memory.
+ *   x (B rows of T fp32 samples, row pitch x_bs), lens (B) int32 or NULL (clamped to [0, T]);
+ *   offset: the position of the call's first sample within its sub-block, 0 <= offset < S; the call covers the
+ *           n_sub = ceil((offset + T) / S) sub-blocks e[b * e_bs + j], j < n_sub, all of which are written (0 behind len_b);
+ *           with offset > 0, e[b, 0] is read and the call's share is added to it (a stream's sub-block grid continues);
+ *   state_in / state_out (B, 4) fp64 or NULL: the state before the first and after the last of the T samples (they may be the
+ *           same buffer; state_out needs lens == NULL);
+ *   peak (B) fp32 or NULL: max |x| over the row's samples; with peak_accumulate != 0 the maximum of that and what it held;
+ *   ws: fac_kweight_ws_bytes(B, T) bytes of device scratch, 8-byte aligned.
+ * S >= FAC_LOUDNESS_CHUNK (fs >= 2560), T <= 2^30, B <= 65535.  T == 0 launches nothing.
+ *
+ * fac_loudness_gate: one workgroup per row, fixed order.  e (B rows of pitch e_bs), n_samples = the samples every row holds
+ * (int64: a stream), lens (B) int32 or NULL (clamped to [0, n_samples]).  last_n == 0: the two-gate integrated loudness above;
+ * last_n > 0: -0.691 + 10 log10(sum of the row's last last_n sub-blocks / (last_n S)), ungated and not below -70 (momentary:
+ * 4, short-term: 30; sub-blocks before the signal's start count as zero).  peaks (B, n_peaks) fp32 of pitch n_peaks or NULL:
+ * peak_out[b] = their maximum.  L_out (B) fp64.
+ *
+ * fac_loudness_gain: g[b] from (L[b], target, peak[b]) by the rule above, on the device, then y[b, t] = x[b, t] * g[b] for
+ * t < len_b and 0 behind, t < T; g_out (B) fp32 or NULL.  target_rows (B) fp64 or NULL replaces `target` per row, and a NaN
+ * there means g = 1 (a row to leave alone).  guard == 0 skips the peak guard (peak may then be NULL).  y may be x.
+ * ---------------------------------------------------------------------------------------- */
+#define FAC_LOUDNESS_CHUNK 256
+typedef struct fac_kweight_desc {
+  const float* x;
+  const int32_t* lens;
+  double* e;
+  const double* state_in;
+  double* state_out;
+  float* peak;
+  void* ws;
+  int64_t x_bs, e_bs;
+  int32_t B, T, S, offset, peak_accumulate, reserved;
+  double coef[10];
+  double pw[7][16];
+} fac_kweight_desc;
+int64_t fac_kweight_ws_bytes(int B, int T);
+int fac_kweight_energy(const fac_kweight_desc* d, fac_stream_t stream);
+/* which = 0: samples per chunk (FAC_LOUDNESS_CHUNK), 1: chunks per workgroup. */
+int fac_loudness_chunk(int which);
+int fac_loudness_gate(const double* e, int64_t e_bs, const int32_t* lens, int64_t n_samples, int S, int last_n, const float* peaks,
+                      int n_peaks, double* L_out, float* peak_out, int B, fac_stream_t stream);
+int fac_loudness_gain(const float* x, int64_t x_bs, const int32_t* lens, const double* L, const float* peak, const double* target_rows,
+                      double target, int guard, float* y, int64_t y_bs, float* g_out, int B, int T, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
