@@ -93,6 +93,17 @@ class KweightDesc(C.Structure):
     ]
 
 
+SLOT_MAX_DST, SLOT_TILE = 8, 4096        # FAC_SLOT_MAX_DST, FAC_SLOT_TILE
+
+
+class SlotSeg(C.Structure):
+    _fields_ = [
+        ("base", _p), ("slot_hi", _i64),
+        ("rows", C.c_int32), ("row_stride", C.c_int32), ("row_len", C.c_int32), ("slot_lo", C.c_int32),
+        ("elems", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/facodec_hip.h declares
 SIGNATURES = {
     "fac_version": (_i, []),
@@ -240,6 +251,8 @@ SIGNATURES = {
     "fac_loudness_chunk": (_i, [_i]),
     "fac_loudness_gate": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _i, _p, _p, _i, _p]),
     "fac_loudness_gain": (_i, [_p, _i64, _p, _p, _p, _p, C.c_double, _i, _p, _i64, _p, _i, _i, _p]),
+    "fac_slot_copy": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(C.c_int32), _i, _p]),
+    "fac_rows_pick": (_i, [_p, _i64, _p, _p, _i, _i, _i, _p]),
     "fac_spec_power": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fac_reduce_pair": (_i, [_p, _p, _p, _p, _i64, _i, _f, _f, _i, _p]),
     "fac_aa_snakebeta_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

@@ -2179,3 +2179,141 @@ def mel_log_norm(mel):
     out = torch.empty(B, T, device=mel.device, dtype=torch.float32)
     _lib.check(_lib.load().fac_mel_log_norm(_ptr(mel), _ptr(out), B, M, T, _stream()), "fac_mel_log_norm")
     return out
+
+
+# --------------------------------------------------------------------------------- slots of a running streaming session
+def edge_segments(C, W):
+    """Where a contiguous left-context buffer (B, C, W) keeps slot b (the segment form of include/facodec_hip.h):
+    [(offset, rows, row_stride, row_len, slot_lo, slot_hi)], elements relative to the tensor's first."""
+    return [(0, 1, 0, C * W, C * W, 32 * C * W)]
+
+
+def lstm_state_segments(H, BP):
+    """The same for a carried LSTM state (3, H, BP) = [c | h ping | h pong] (fac_lstm_layer_fwd): the cell plane is row-major
+    (H, BP), the two hidden planes are in MFMA-B fragment order [BP/32][H/8][2][32 batch][4]."""
+    if H % 8 or BP % 32:
+        raise ValueError(f"LSTM state with H = {H}, BP = {BP}: H must be a multiple of 8, BP of 32")
+    plane = H * BP
+    return [(0, H, BP, 1, 1, 32), (plane, H // 4, 128, 4, 4, 32 * H), (2 * plane, H // 4, 128, 4, 4, 32 * H)]
+
+
+def _segment_extent(seg, b):
+    off, rows, row_stride, row_len, slot_lo, slot_hi = seg
+    first = off + (b >> 5) * slot_hi + (b & 31) * slot_lo
+    return first, first + (rows - 1) * row_stride + row_len
+
+
+class SlotTable:
+    """The device-resident segment table and tile list of fac_slot_copy over B slots, built once:
+
+        table = SlotTable(B); table.add_edge(buf) ...; table.add_lstm_state(state) ...; table.freeze()
+        table.copy(src, [dst, ...])               # any number of destinations, FAC_SLOT_MAX_DST per launch
+
+    Every run of every slot is checked against its tensor's extent here, on the host: the entry trusts the table."""
+
+    def __init__(self, B):
+        self.B = int(B)
+        self._tensors, self._segs = [], []
+        self._dev = None
+        self.elems = 0                                # floats one slot holds
+
+    def _add(self, t, segs, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.FacodecHipError(f"{what} must live on the GPU (got {getattr(t, 'device', type(t).__name__)}); there is no CPU path")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.FacodecHipError(f"{what} must be contiguous float32 (got {t.dtype})")
+        if self._dev is not None:
+            raise RuntimeError("the table is frozen")
+        for seg in segs:
+            for b in range(self.B):
+                lo, hi = _segment_extent(seg, b)
+                if lo < 0 or hi > t.numel():
+                    raise ValueError(f"{what} {tuple(t.shape)}: slot {b} reaches element {hi} of {t.numel()}")
+            if seg[1] * seg[3] >= 1 << 31:
+                raise ValueError(f"{what} {tuple(t.shape)}: a slot of 2^31 elements or more")
+            self._segs.append((t.data_ptr() + 4 * seg[0],) + tuple(seg[1:]))
+        self._tensors.append(t)                       # the table holds raw pointers: keep their owners alive
+
+    def add_edge(self, buf):
+        if buf.dim() != 3 or buf.shape[0] != self.B:
+            raise ValueError(f"a left-context buffer is (B = {self.B}, C, W), got {tuple(buf.shape)}")
+        self._add(buf, edge_segments(buf.shape[1], buf.shape[2]), "left-context buffer")
+
+    def add_lstm_state(self, state):
+        if state.dim() != 3 or state.shape[0] != 3 or state.shape[2] < self.B:
+            raise ValueError(f"an LSTM state is (3, H, BP >= B = {self.B}), got {tuple(state.shape)}")
+        self._add(state, lstm_state_segments(state.shape[1], state.shape[2]), "LSTM state")
+
+    def freeze(self):
+        if not self._segs:
+            raise ValueError("an empty slot table")
+        arr = (_lib.SlotSeg * len(self._segs))()
+        tiles = []
+        for i, (ptr, rows, row_stride, row_len, slot_lo, slot_hi) in enumerate(self._segs):
+            s = arr[i]
+            s.base, s.slot_hi, s.rows, s.row_stride, s.row_len, s.slot_lo, s.elems = ptr, slot_hi, rows, row_stride, row_len, slot_lo, rows * row_len
+            tiles += [(i, e) for e in range(0, rows * row_len, _lib.SLOT_TILE)]
+            self.elems += rows * row_len
+        device = self._tensors[0].device
+        self._segs_dev = h2d(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8), device)
+        self._tiles_dev = h2d(torch.tensor(tiles, dtype=torch.int32), device)
+        self.n_seg, self.n_tiles = len(self._segs), len(tiles)
+        self._dev = device
+        return self
+
+    def copy(self, src, dsts):
+        """Slot `src` -> every slot of `dsts` on the current stream; refusals are fac_slot_copy's."""
+        if self._dev is None:
+            raise RuntimeError("freeze() the table first")
+        dsts = [int(d) for d in dsts]
+        if len(set(dsts)) != len(dsts):
+            raise _lib.FacodecHipError(f"fac_slot_copy: duplicate destination slot in {dsts}")
+        lib = _lib.load()
+        for i in range(0, max(len(dsts), 1), _lib.SLOT_MAX_DST):
+            part = dsts[i:i + _lib.SLOT_MAX_DST]
+            _lib.check(lib.fac_slot_copy(_ptr(self._segs_dev), self.n_seg, _ptr(self._tiles_dev), self.n_tiles, self.B, int(src),
+                                         (C.c_int32 * max(len(part), 1))(*part), len(part), _stream()), "fac_slot_copy")
+
+
+def slot_copy_raw(table, src, dsts):
+    """fac_slot_copy exactly as given (one launch, no splitting): what the refusal tests call."""
+    dsts = [int(d) for d in dsts]
+    _lib.check(_lib.load().fac_slot_copy(_ptr(table._segs_dev), table.n_seg, _ptr(table._tiles_dev), table.n_tiles, table.B, int(src),
+                                         (C.c_int32 * max(len(dsts), 1))(*dsts), len(dsts), _stream()), "fac_slot_copy")
+
+
+def rows_pick_map(rows, inner, device):
+    """Host list of source rows (-1: none) -> the device int32 map of rows_pick for a source with `inner` sub-rows per row
+    ((B, n_q, k) codes: inner = n_q), through h2d (no host stall)."""
+    flat = [(-1 if r < 0 else r * inner + q) for r in rows for q in range(inner)]
+    return h2d(torch.tensor(flat, dtype=torch.int32), device)
+
+
+def rows_pick(src, row_map, out=None):
+    """out[r] = src[row_map[r]] where row_map[r] names a row of src, zeros elsewhere (fac_rows_pick).  src (n_src, L) or
+    (n, q, L) taken as n q rows, float32 / int32 / int64, last dimension dense, rows of one pitch (a [:, :, :k] slice of a wider
+    static buffer is read in place); row_map: int32 on the device, one entry per output row; out: dense, row_map.numel() rows."""
+    if not src.is_cuda or not row_map.is_cuda:
+        raise _lib.FacodecHipError(f"rows_pick: src and row_map must live on the GPU (got {src.device}, {row_map.device}); there is no CPU path")
+    if src.dtype not in (torch.float32, torch.int32, torch.int64) or row_map.dtype != torch.int32 or not row_map.is_contiguous():
+        raise _lib.FacodecHipError(f"rows_pick: src float32 / int32 / int64 and a dense int32 row_map (got {src.dtype}, {row_map.dtype})")
+    if src.dim() not in (2, 3) or (src.shape[-1] > 1 and src.stride(-1) != 1):
+        raise ValueError(f"rows_pick: src must be (n, L) or (n, q, L) with a dense last dimension, got {tuple(src.shape)}")
+    L = src.shape[-1]
+    n_src = src.numel() // L
+    pitch = src.stride(-2)
+    if src.dim() == 3 and src.shape[0] > 1 and src.shape[1] > 1 and src.stride(0) != src.shape[1] * pitch:
+        raise ValueError("rows_pick: the rows of src do not have one pitch")
+    if src.dim() == 3 and src.shape[1] == 1:
+        pitch = src.stride(0)
+    if n_src == 1:
+        pitch = L
+    words = src.element_size() // 4
+    n_dst = row_map.numel()
+    if out is None:
+        out = torch.empty((n_dst, L) if src.dim() == 2 else (n_dst // src.shape[1], src.shape[1], L), device=src.device, dtype=src.dtype)
+    elif out.dtype != src.dtype or not out.is_contiguous() or out.numel() != n_dst * L or not out.is_cuda:
+        raise ValueError(f"rows_pick: out must be dense {src.dtype} with {n_dst} rows of {L}, got {tuple(out.shape)} {out.dtype}")
+    _lib.check(_lib.load().fac_rows_pick(_ptr(src), pitch * words, _ptr(out), _ptr(row_map), n_dst, n_src, L * words, _stream()),
+               "fac_rows_pick")
+    return out

@@ -450,6 +450,16 @@ class _HopSession:
     def _state(self):
         return [list(o.c) for o in self._counters]
 
+    def _slot_state(self):
+        """Every tensor that carries per-stream state from one hop to the next, as ("edge", (B, C, W)) / ("lstm", (3, H, BP)):
+        the buffers the captured graphs read in place (StreamPool re-initialises a slot by overwriting its rows of them)."""
+        for o in self._counters:
+            if isinstance(o, _Edge):
+                yield "edge", o.buf
+            elif isinstance(o, _LSTMState):
+                for s in o.state:
+                    yield "lstm", s
+
     def _set_state(self, base, delta, k):
         for o, b, d in zip(self._counters, base, delta):
             o.c[:] = [bi + k * di for bi, di in zip(b, d)]
@@ -1183,3 +1193,260 @@ class CodeDepacketizer:
             raise ValueError("a packet without frames")
         rows = np.stack([np.frombuffer(p, dtype=np.uint8) for p in payloads])
         return ops.unpack_codes(ops.h2d(torch.from_numpy(rows), self.device), self.n_q, k, bits=self.bits)
+
+
+# ------------------------------------------------------------------------------------ streams that join and leave
+DRAIN_HOPS = 3       # ticks of silence a leaving stream is still run for: the 1 024 samples of look-ahead, in whole hops
+
+
+class PoolFull(RuntimeError):
+    """StreamPool.join(): every slot is taken by a live or a draining stream."""
+
+
+def pool_preroll(n_consumed):
+    """Output samples a stream joining after `n_consumed` session samples receives that lie before its own first input sample:
+    the session has emitted (n - 1024) // 300 + 1 frames of its n samples, the next frame it emits starts there."""
+    return n_consumed - FRAME * ((n_consumed - LOOKAHEAD) // FRAME + 1)
+
+
+class SlotBook:
+    """The host-side book-keeping of a StreamPool, no device in sight: which stream holds which slot, who is draining, who
+    missed a tick.  Slot 0 is the donor and is never handed out; ids count up from 0 and are never reused."""
+
+    def __init__(self, slots):
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError(f"slots = {slots}: a pool has at least one slot")
+        self.slots = slots
+        self.free = list(range(1, slots + 1))
+        self.slot = {}           # id -> slot, live and draining streams
+        self.live = []           # ids in join order
+        self.draining = {}       # id -> ticks left, in leave order
+        self.underruns = {}      # id -> ticks a live stream was not fed
+        self._next = 0
+
+    def join(self):
+        if not self.free:
+            raise PoolFull(f"all {self.slots} slots are taken ({len(self.live)} live, {len(self.draining)} draining)")
+        b = min(self.free)
+        self.free.remove(b)
+        sid, self._next = self._next, self._next + 1
+        self.slot[sid] = b
+        self.live.append(sid)
+        self.underruns[sid] = 0
+        return sid, b
+
+    def leave(self, sid):
+        if sid not in self.live:
+            raise ValueError(f"stream {sid!r} is {'already leaving' if sid in self.draining else 'unknown'}")
+        self.live.remove(sid)
+        self.draining[sid] = DRAIN_HOPS
+
+    def check(self, sids):
+        seen = set()
+        for s in sids:
+            if s in self.draining:
+                raise ValueError(f"stream {s!r} has left and is draining: it takes no more audio")
+            if s not in self.slot:
+                raise ValueError(f"unknown stream {s!r}")
+            if s in seen:
+                raise ValueError(f"stream {s!r} named twice")
+            seen.add(s)
+
+    def tick(self, sids):
+        """One tick fed the streams `sids` (in that order) -> (out, scatter, last): the ids whose outputs the tick returns -- the
+        fed streams, the live ones that were not fed, the draining ones --, for every slot 0 .. slots the index into `sids` of
+        the stream to feed it or -1 (silence), and {id: True on a draining stream's last tick}.  Slots of streams that drained
+        out are free on return; their ids stay valid in `out` for this tick only (`slot_of` = their slots)."""
+        sids = list(sids)
+        self.check(sids)
+        fed = set(sids)
+        missed = [s for s in self.live if s not in fed]
+        for s in missed:
+            self.underruns[s] += 1
+        out = sids + missed + list(self.draining)
+        scatter = [-1] * (self.slots + 1)
+        for i, s in enumerate(sids):
+            scatter[self.slot[s]] = i
+        self.slot_of = [self.slot[s] for s in out]
+        last = {s: False for s in out}
+        for s in list(self.draining):
+            self.draining[s] -= 1
+            if self.draining[s] == 0:
+                last[s] = True
+                del self.draining[s]
+                self.free.append(self.slot.pop(s))
+        return out, scatter, last
+
+
+class StreamPool:
+    """A running streaming session whose streams join and leave one by one:
+
+        pool = StreamPool(model, slots=16, n_c=2)                                    # codec pool
+        pool = StreamPool(codec, slots=16, redecoder=red, use_p_code=False, n_c=1)   # conversion pool
+        sid = pool.join(timbre)                  # (1024,) fp32 on the device: source timbre (codec) / target voice (converter)
+        out = pool.tick(sids, hops)              # sids: ids in any order; hops (len(sids), 480) fp32 on the device
+        pool.set_timbre(sid, timbre)
+        pool.leave(sid)
+
+    One StreamingCodec / StreamingConverter over B = slots + 1 streams runs every tick, whoever is there: the hop is launch
+    bound, so a tick costs what a lockstep hop of B streams costs plus three small launches.  Slot 0 is the donor: it hears
+    silence under the all-zero timbre for ever, so its rows of the session's state tensors (left-context buffers, LSTM states;
+    _HopSession._slot_state) are at every tick those of a stream that has been silent since the session began.  join() copies
+    them into the lowest free slot (fac_slot_copy on the current stream, before the next tick; joins before one tick share a
+    launch) and writes the slot's style row (converter: cond row).  From that tick on the stream is, bit for bit, its row of a
+    lockstep session of the same B that heard silence and then the stream.
+
+    tick() scatters the hops into the session's input (fac_rows_pick; donor, idle, draining and unfed slots get zeros), pushes,
+    and gathers the rows of the live and draining streams into pool-owned buffers, valid until the next tick ->
+        dict(sids=[fed streams in the order given, live streams that were not fed, draining streams],
+             codes=[p, c, r] ((n, n_q, k) int64; a converter pool: [p, c]), wave=(n, 1, 300 k), rows in the order of sids,
+             frame0={sid: frames the stream had received before this tick}, preroll={sid: ...}, last={sid: bool})
+    A live stream missing from `sids` hears silence for that tick and pool.underruns[sid] counts it.  A stream's first
+    preroll(sid) output samples lie before its own first input sample (900 / 780 / 960 / 840 / 1020 by the phase of the join
+    in the session's 5-hop period): the codec's look-ahead plus the offset of the stream's start on the POOL's 300-sample
+    frame grid.  leave() feeds the stream DRAIN_HOPS more ticks of silence, which emits the frame that holds its last sample
+    for every alignment; its outputs keep coming, the last with last[sid] = True, then the slot is free.  No finish() and no
+    reflect padding of a stream's end.
+
+    Limits: until its join a stream's left context is silence under the null timbre; the frame grid is the pool's; kernel routes
+    depend on B as everywhere, so outputs equal a B-row lockstep session bit for bit and a one-stream session up to near ties.
+    Everything runs on the stream that is current at the call; the device maps are uploaded again (ops.h2d) only when the
+    membership or the order of `sids` changes."""
+
+    def __init__(self, model, slots=16, n_c=None, use_graphs=True, redecoder=None, use_p_code=False, device="cuda"):
+        self.book = SlotBook(slots)
+        self.slots, self.B = self.book.slots, self.book.slots + 1
+        self.device = torch.device(device)
+        q = model.quantizer
+        self._dim = q.in_dim
+        zero = torch.zeros(self.B, q.in_dim, device=self.device)
+        if redecoder is None:
+            self.session = StreamingCodec(model, zero, n_c=2 if n_c is None else n_c, use_graphs=use_graphs)
+        else:
+            self.session = StreamingConverter(model, redecoder, zero, use_p_code=use_p_code, n_c=1 if n_c is None else n_c,
+                                              use_graphs=use_graphs)
+        self.converter = redecoder is not None
+        self._q = q
+        sess = self.session
+        self._in = sess._hop_in                                   # the session's own static input: push() then copies nothing
+        with torch.no_grad():
+            sess.prime(torch.zeros(self.B, 1, sess.prime_samples, device=self.device))
+            for _ in range(10):                                   # both periods: every phase's graph captured, every edge in
+                self._in.zero_()                                  # its steady-state layout
+                o = sess.push(self._in)
+        self._n_q = [c.shape[1] for c in o["codes"]]              # quantizers per code tensor: [1, n_c, 3] / [1, n_c]
+        self.table = ops.SlotTable(self.B)
+        for kind, t in sess._slot_state():
+            (self.table.add_edge if kind == "edge" else self.table.add_lstm_state)(t)
+        self.table.freeze()
+        self._pending = []                                        # slots joined since the last tick
+        self._preroll, self._frames = {}, {}
+        self._key, self._maps = None, None
+        self._wave, self._codes = {}, {}
+        self.ticks = 0
+
+    # ------------------------------------------------------------------------------------------ membership
+    @property
+    def underruns(self):
+        return self.book.underruns
+
+    @property
+    def live(self):
+        return list(self.book.live)
+
+    def preroll(self, sid):
+        return self._preroll[sid]
+
+    def _row(self, timbre):
+        if not isinstance(timbre, torch.Tensor) or timbre.numel() != self._dim or timbre.dim() > 2:
+            got = tuple(timbre.shape) if isinstance(timbre, torch.Tensor) else type(timbre).__name__
+            raise ValueError(f"timbre must be a float32 GPU tensor ({self._dim},), got {got}")
+        timbre = timbre.reshape(1, self._dim)
+        _check_timbre(timbre, 1, self._dim, "timbre")
+        with torch.no_grad():
+            if self.converter:
+                return self.session.red.r.encoder.cond_layer.run(timbre.contiguous().reshape(1, -1, 1)).reshape(-1)
+            return self._q.timbre_linear(timbre.contiguous()).reshape(-1)
+
+    def _write_row(self, slot, row):
+        (self.session.red.cond if self.converter else self.session.qs.style)[slot].copy_(row)
+
+    def join(self, timbre):
+        row = self._row(timbre)                                   # refuses before a slot is taken
+        sid, slot = self.book.join()
+        self._pending.append(slot)
+        self._write_row(slot, row)
+        self._preroll[sid] = pool_preroll(self.session.n_samples)
+        self._frames[sid] = 0
+        return sid
+
+    def set_timbre(self, sid, timbre):
+        """Codec pool: the stream's style row; conversion pool: its cond row (StreamingConverter.set_target for one row).  Between
+        ticks; the next tick already uses it.  Left contexts are not reset."""
+        if sid not in self.book.live:
+            raise ValueError(f"stream {sid!r} is not live")
+        self._write_row(self.book.slot[sid], self._row(timbre))
+
+    def leave(self, sid):
+        self.book.leave(sid)
+
+    # ------------------------------------------------------------------------------------------ the tick
+    def _out_buffers(self, codes, k):
+        if k not in self._wave:
+            self._wave[k] = torch.zeros(self.slots, 1, FRAME * k, device=self.device)
+            self._codes[k] = [torch.zeros(self.slots, c.shape[1], k, device=self.device, dtype=torch.int64) for c in codes]
+        return self._wave[k], self._codes[k]
+
+    def tick(self, sids, hops=None):
+        sids = list(sids)
+        self.book.check(sids)
+        n_in = len(sids)
+        if n_in or hops is not None:
+            if not isinstance(hops, torch.Tensor) or tuple(hops.shape) != (n_in, HOP):
+                got = tuple(hops.shape) if isinstance(hops, torch.Tensor) else type(hops).__name__
+                raise ValueError(f"hops must be ({n_in}, {HOP}) float32 on {self.device}, got {got}")
+            if hops.dtype != torch.float32 or hops.device.type != self.device.type or not hops.is_cuda:
+                raise ValueError(f"hops must be float32 on {self.device}, got {hops.dtype} on {hops.device}")
+            if hops.stride(-1) != 1:
+                hops = hops.contiguous()
+        out_sids, scatter, last = self.book.tick(sids)
+        slot_of = self.book.slot_of
+        n_out = len(out_sids)
+        if self._pending:
+            self.table.copy(0, self._pending)
+            self._pending = []
+        key = (tuple(scatter), tuple(slot_of))
+        if key != self._key:
+            inners = sorted({1} | set(self._n_q))
+            flat, spans = list(scatter), {}
+            for q in inners:
+                spans[q] = (len(flat), len(flat) + n_out * q)
+                flat += [b * q + i for b in slot_of for i in range(q)]
+            dev = ops.h2d(torch.tensor(flat, dtype=torch.int32), self.device)
+            self._key, self._maps = key, (dev, spans)
+        dev, spans = self._maps
+        if n_in:
+            ops.rows_pick(hops, dev[:self.B], out=self._in)
+        else:
+            self._in.zero_()
+        with torch.no_grad():
+            o = self.session.push(self._in)
+        codes_s, wave_s = o["codes"], o["wave"]
+        k = codes_s[0].shape[-1]
+        wave, codes = self._out_buffers(codes_s, k)
+        if n_out:
+            ops.rows_pick(wave_s, dev[spans[1][0]:spans[1][1]], out=wave[:n_out])
+            for c_s, c in zip(codes_s, codes):
+                a, b = spans[c_s.shape[1]]
+                ops.rows_pick(c_s, dev[a:b], out=c[:n_out])
+        frame0 = {s: self._frames[s] for s in out_sids}
+        for s in out_sids:
+            self._frames[s] += k
+        res = dict(sids=out_sids, codes=[c[:n_out] for c in codes], wave=wave[:n_out], frame0=frame0,
+                   preroll={s: self._preroll[s] for s in out_sids}, last=last)
+        for s, done in last.items():
+            if done:
+                del self._frames[s], self._preroll[s]
+        self.ticks += 1
+        return res

@@ -937,6 +937,50 @@ int fac_loudness_gate(const double* e, int64_t e_bs, const int32_t* lens, int64_
 int fac_loudness_gain(const float* x, int64_t x_bs, const int32_t* lens, const double* L, const float* peak, const double* target_rows,
                       double target, int guard, float* y, int64_t y_bs, float* g_out, int B, int T, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Slots of a running streaming session (csrc/stream_pool.hip).  This comment is the normative layout.
+ *
+ * A session over B streams keeps every per-stream piece of state in static, batch-indexed fp32 buffers.  A SEGMENT describes
+ * where one such buffer keeps the state of slot b: `rows` runs of `row_len` contiguous floats, `row_stride` elements apart,
+ * the first at
+ *     base + (b >> 5) * slot_hi + (b & 31) * slot_lo                                     (all strides in elements)
+ *   left-context buffer (B, C, W), contiguous       rows 1,   row_len C W, row_stride 0,   slot_lo C W, slot_hi 32 C W
+ *   LSTM state (3, H, BP) = [c | h ping | h pong] (fac_lstm_layer_fwd):
+ *     c plane (H, BP)                               rows H,   row_len 1,   row_stride BP,  slot_lo 1,   slot_hi 32
+ *     each h plane, MFMA-B fragment order
+ *       [BP/32][H/8][2][32 batch][4]                rows H/4, row_len 4,   row_stride 128, slot_lo 4,   slot_hi 32 H
+ *   (both h planes are copied: which one is live depends on the parity of the steps taken).
+ * `elems` = rows * row_len.  The work of one copy is cut into TILES of up to FAC_SLOT_TILE elements of one segment's per-slot
+ * element range: tile = {segment index, first element}, first element a multiple of FAC_SLOT_TILE.  Segment table and tile list
+ * live on the device and are built once per pool (ops.SlotTable checks every run against its tensor's extent); the entry
+ * trusts them.
+ *
+ * fac_slot_copy: for every destination d of dst[0 .. n_dst) (HOST array) and every segment, slot d's runs = slot src's runs,
+ * in one launch of n_tiles x n_dst workgroups.  A run is moved with 16-byte loads and stores when row_len and (for rows > 1)
+ * row_stride are multiples of 4 and both slots' first addresses are 16-byte aligned, with 4-byte accesses otherwise (decided
+ * per segment and destination, uniform over the workgroup).  Plain vector stores, no atomics; nothing outside the destination
+ * slots' runs is written.  Refused before any launch: a NULL table or tile list, n_seg or n_tiles < 1, B < 1, n_dst outside
+ * 1 .. FAC_SLOT_MAX_DST, a slot outside [0, B), src among the destinations, a destination named twice.
+ *
+ * fac_rows_pick: dst[r, 0 .. row_words) = map[r] in [0, n_src) ? src[map[r] * src_stride + 0 .. row_words) : 0 for r < n_dst,
+ * over 32-bit words (an int64 row of k values is 2 k words).  dst is dense (n_dst, row_words); map: n_dst int32 on the device.
+ * Destination driven: every word of dst is written exactly once, the rows without a source by stores alone; src is only read.
+ * 16-byte accesses when row_words and src_stride are multiples of 4 and both pointers are 16-byte aligned.  Refused: NULL
+ * pointers, n_dst, n_src or row_words < 1, src_stride < row_words.
+ * ---------------------------------------------------------------------------------------- */
+#define FAC_SLOT_MAX_DST 8
+#define FAC_SLOT_TILE 4096
+typedef struct fac_slot_seg {
+  float* base;
+  int64_t slot_hi;
+  int32_t rows, row_stride, row_len, slot_lo;
+  int32_t elems, reserved;
+} fac_slot_seg;
+int fac_slot_copy(const fac_slot_seg* segs, int n_seg, const int32_t* tiles, int n_tiles, int B, int src, const int32_t* dst,
+                  int n_dst, fac_stream_t stream);
+int fac_rows_pick(const void* src, int64_t src_stride, void* dst, const int32_t* map, int n_dst, int n_src, int row_words,
+                  fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
