@@ -93,6 +93,18 @@ class KweightDesc(C.Structure):
     ]
 
 
+SI_SDR_CHUNK = 4096                      # FAC_SI_SDR_CHUNK
+
+
+class StoiDesc(C.Structure):
+    _fields_ = [
+        ("x", _p), ("y", _p), ("lens", _p), ("kept_idx", _p), ("n_frames", _p), ("n_kept", _p), ("n_segments", _p),
+        ("stoi", _p), ("estoi", _p), ("ws", _p),
+        ("x_bs", _i64), ("y_bs", _i64), ("ws_bytes", _i64),
+        ("B", C.c_int32), ("T", C.c_int32),
+    ]
+
+
 SLOT_MAX_DST, SLOT_TILE = 8, 4096        # FAC_SLOT_MAX_DST, FAC_SLOT_TILE
 
 
@@ -251,6 +263,12 @@ SIGNATURES = {
     "fac_loudness_chunk": (_i, [_i]),
     "fac_loudness_gate": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _i, _p, _p, _i, _p]),
     "fac_loudness_gain": (_i, [_p, _i64, _p, _p, _p, _p, C.c_double, _i, _p, _i64, _p, _i, _i, _p]),
+    "fac_si_sdr_ws_bytes": (_i64, [_i, _i]),
+    "fac_si_sdr": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _p]),
+    "fac_stoi_geometry": (_i, [_i, C.POINTER(_i64)]),
+    "fac_stoi_select": (_i, [C.POINTER(StoiDesc), _p]),
+    "fac_stoi_bands": (_i, [C.POINTER(StoiDesc), _p]),
+    "fac_stoi_score": (_i, [C.POINTER(StoiDesc), _p]),
     "fac_slot_copy": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(C.c_int32), _i, _p]),
     "fac_rows_pick": (_i, [_p, _i64, _p, _p, _i, _i, _i, _p]),
     "fac_spec_power": (_i, [_p, _p, _i, _i, _i, _i, _p]),

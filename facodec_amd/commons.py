@@ -785,6 +785,59 @@ def loudness_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SA
     return out
 
 
+SCORE_METRICS = ("si_sdr", "stoi", "estoi")
+
+
+@torch.no_grad()
+def score_clips(refs, ests, sample_rate=MODEL_RATE, metrics=SCORE_METRICS, max_batch_samples=MAX_BATCH_SAMPLES):
+    """Objective scores of estimates against references, clip by clip -> list of dicts {metric: float} in the
+    caller's order.  refs[i], ests[i]: (T,) or (1, T) float32 on the GPU at sample_rate; every pair is cropped to the shorter of
+    the two (the codec gives back 300 (T // 300) samples).  metrics: any of "si_sdr" (dB, ops.si_sdr), "stoi", "estoi"
+    (ops.stoi_scores; NaN for a clip under 30 kept frames of 12.8 ms).  The pairs go through plan_groups' zero-padded groups with
+    their lengths: per group one ops call per metric family and one device-to-host copy; a pair scores what it scores alone."""
+    from . import ops
+    metrics = tuple(metrics)
+    for m in metrics:
+        if m not in SCORE_METRICS:
+            raise ValueError(f"unknown metric {m!r}; this build scores {SCORE_METRICS}")
+    refs, ests = list(refs), list(ests)
+    if len(refs) != len(ests):
+        raise ValueError(f"{len(refs)} references but {len(ests)} estimates")
+    if not refs:
+        return []
+    _need_gpu(refs + ests, "clips")
+    for w in refs + ests:
+        if not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = [min(int(r.shape[-1]), int(e.shape[-1])) for r, e in zip(refs, ests)]
+    out = [None] * len(refs)
+    for group in plan_groups(lengths, max_batch_samples):
+        x, y = (torch.nn.utils.rnn.pad_sequence([ws[i].reshape(-1)[:lengths[i]].to(torch.float32) for i in group], batch_first=True)
+                for ws in (refs, ests))
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), x.device)
+        rows = {}
+        if "si_sdr" in metrics:
+            rows["si_sdr"] = ops.si_sdr(x, y, lens=lens)
+        if "stoi" in metrics or "estoi" in metrics:
+            s = ops.stoi_scores(x, y, sample_rate, lens)
+            rows["stoi"], rows["estoi"] = s.stoi, s.estoi
+        table = torch.stack([rows[m] for m in metrics]).cpu().tolist() if metrics else []
+        for j, i in enumerate(group):
+            out[i] = {m: table[k][j] for k, m in enumerate(metrics)}
+    return out
+
+
+@torch.no_grad()
+def evaluate_clips(model, waves, n_c=2, sample_rate=MODEL_RATE, metrics=SCORE_METRICS, max_batch_samples=MAX_BATCH_SAMPLES,
+                   quality="best"):
+    """What the codec does to clips, in numbers: reconstruct_clips (encode, quantize with n_c content codebooks, decode with every
+    clip's own timbre) then score_clips of the results against the inputs -> (scores, waves_out): a list of dicts as score_clips
+    returns them and the reconstructed waves (1, 300 (T_i // 300)), both in the caller's order and at sample_rate."""
+    waves = list(waves)
+    waves_out = reconstruct_clips(model, waves, n_c=n_c, max_batch_samples=max_batch_samples, sample_rate=sample_rate, quality=quality)
+    return score_clips(waves, waves_out, sample_rate=sample_rate, metrics=metrics, max_batch_samples=max_batch_samples), waves_out
+
+
 @torch.no_grad()
 def decompress(model, blobs, timbre=None, sample_rate=None, max_batch_samples=MAX_BATCH_SAMPLES, quality="best",
                restore_loudness=True):

@@ -1635,6 +1635,106 @@ def normalize_loudness(x, target_db=-16.0, rate=24000, lens=None):
     return y, L, g
 
 
+# --------------------------------------------------------------------------------- objective scores
+STOI_RATE = 10000
+StoiGeometry = namedtuple("StoiGeometry", "n_frames ws_bytes_per_row energy_frames scan_block band_frames score_segments")
+StoiScores = namedtuple("StoiScores", "stoi estoi n_frames n_kept n_segments kept_idx")
+
+
+def si_sdr_chunk():
+    """Samples per chunk (one workgroup's partial sums) of fac_si_sdr."""
+    return _lib.SI_SDR_CHUNK
+
+
+def stoi_geometry(T):
+    """fac_stoi_geometry for rows of T samples at 10 kHz (host only): frames per row, workspace bytes per row, and the tile
+    constants of the launches -- frames per workgroup of the energy pass, frames per block of the keep scan, frames per
+    workgroup of fac_stoi_bands, segments per workgroup of fac_stoi_score."""
+    out = (C.c_int64 * 6)()
+    _lib.check(_lib.load().fac_stoi_geometry(int(T), out), "fac_stoi_geometry")
+    return StoiGeometry(*(int(v) for v in out))
+
+
+def _score_pair(ref, est, lens, what):
+    """-> the (B, T) views of ref and est with dense samples and lens checked (or None)."""
+    if isinstance(ref, torch.Tensor) and isinstance(est, torch.Tensor) and ref.shape != est.shape:
+        raise ValueError(f"{what}: reference and estimate must have the same shape, got {tuple(ref.shape)} and {tuple(est.shape)}")
+    x, y = _rows(ref, what), _rows(est, what)
+    return x, y, (_lens(lens, x.shape[0]) if lens is not None else None)
+
+
+def si_sdr(ref, est, lens=None):
+    """Scale-invariant signal-to-distortion ratio in dB, higher is better (dac/nn/loss.py:91-130 with scaling and zero_mean, sign
+    flipped): ref, est (B, T) or (B, 1, T) float32 -> (B,) float64 on the device, evaluated in fp64 in three passes
+    (fac_si_sdr; include/facodec_hip.h states the formula).  lens (B,) int32 on the device: row b is its first lens[b] samples.
+    Identical rows give +inf, an empty or all-zero pair NaN, a zero reference with a non-zero estimate -80."""
+    x, y, lens = _score_pair(ref, est, lens, "si_sdr")
+    B, T = x.shape
+    out = torch.full((B,), float("nan"), device=x.device, dtype=torch.float64)
+    if B == 0 or T == 0:
+        return out
+    lib = _lib.load()
+    need = lib.fac_si_sdr_ws_bytes(B, T)
+    if need < 0:
+        raise ValueError(f"si_sdr: B = {B}, T = {T} (T up to 2^30 samples per call)")
+    ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+    _lib.check(lib.fac_si_sdr(_ptr(x), x.stride(0) if B > 1 else T, _ptr(y), y.stride(0) if B > 1 else T, _ptr(lens), _ptr(out), _ptr(ws),
+                              need, B, T, _stream()), "fac_si_sdr")
+    return out
+
+
+def _stoi_setup(x, y, lens):
+    """Results, descriptor and workspace of the three STOI launches for dense rows x, y (B, T) at 10 kHz -> (StoiScores,
+    fac_stoi_desc or None when there is nothing to launch, ws).  The results hold NaN / 0 until the launches have run."""
+    B, T = x.shape
+    dev = x.device
+    geo = stoi_geometry(T)
+    stoi, estoi = (torch.full((B,), float("nan"), device=dev, dtype=torch.float64) for _ in range(2))
+    n_frames, n_kept, n_seg = (torch.zeros(B, device=dev, dtype=torch.int32) for _ in range(3))
+    kept = torch.empty(B, geo.n_frames, device=dev, dtype=torch.int32)
+    res = StoiScores(stoi, estoi, n_frames, n_kept, n_seg, kept)
+    if B == 0 or T == 0:
+        return res, None, None
+    ws = torch.empty(max(8, B * geo.ws_bytes_per_row), device=dev, dtype=torch.uint8)
+    d = _lib.StoiDesc()
+    d.x, d.y, d.lens = x.data_ptr(), y.data_ptr(), (lens.data_ptr() if lens is not None else None)
+    d.kept_idx = kept.data_ptr() if kept.numel() else ws.data_ptr()          # M_max = 0: nothing is written there
+    d.n_frames, d.n_kept, d.n_segments = n_frames.data_ptr(), n_kept.data_ptr(), n_seg.data_ptr()
+    d.stoi, d.estoi, d.ws = stoi.data_ptr(), estoi.data_ptr(), ws.data_ptr()
+    d.x_bs, d.y_bs, d.ws_bytes = (x.stride(0) if B > 1 else T), (y.stride(0) if B > 1 else T), ws.numel()
+    d.B, d.T = B, T
+    return res, d, ws
+
+
+def stoi_scores(ref, est, rate=24000, lens=None):
+    """STOI and ESTOI of est against ref, both from one pass: ref, est (B, T) or (B, 1, T) float32 at `rate` -> StoiScores(stoi,
+    estoi (B,) float64; n_frames, n_kept, n_segments (B,) int32; kept_idx (B, M_max) int32, the first n_kept[b] entries of row b
+    the kept frames in order and -1 behind them), all on the device.  lens (B,) int32 on the device: row b is its first lens[b] samples.  A rate
+    other than 10000 goes through ops.resample(., rate, 10000, lens=lens, quality="best") first, with lengths ceil(lens n / o).
+    Rows with fewer than 30 kept frames (under 0.4 s) have no segment: NaN and n_segments = 0.  Three C calls
+    (fac_stoi_select, fac_stoi_bands, fac_stoi_score) on one descriptor, no host read in between."""
+    x, y, lens = _score_pair(ref, est, lens, "stoi_scores")
+    if int(rate) != STOI_RATE:
+        geo = resample_table(rate, STOI_RATE, "best")
+        x, y = resample(x, rate, STOI_RATE, lens=lens), resample(y, rate, STOI_RATE, lens=lens)
+        if lens is not None:
+            lens = ((lens.to(torch.int64) * geo["n"] + (geo["o"] - 1)) // geo["o"]).to(torch.int32)
+    res, d, _ = _stoi_setup(x, y, lens)
+    if d is not None:
+        lib = _lib.load()
+        _lib.check(lib.fac_stoi_select(C.byref(d), _stream()), "fac_stoi_select")
+        _lib.check(lib.fac_stoi_bands(C.byref(d), _stream()), "fac_stoi_bands")
+        _lib.check(lib.fac_stoi_score(C.byref(d), _stream()), "fac_stoi_score")
+    return res
+
+
+def stoi(ref, est, rate=24000, lens=None, extended=False):
+    """Short-time objective intelligibility (Taal et al. 2011), or with extended=True ESTOI (Jensen & Taal 2016): -> (B,) float64
+    on the device; see stoi_scores, which gives both from the same pass."""
+    s = stoi_scores(ref, est, rate, lens)
+    return s.estoi if extended else s.stoi
+
+
 def spec_power(spec, power):
     B, f2, nf = spec.shape
     out = torch.empty(B, f2 // 2, nf, device=spec.device, dtype=torch.float32)

@@ -981,6 +981,81 @@ int fac_slot_copy(const fac_slot_seg* segs, int n_seg, const int32_t* tiles, int
 int fac_rows_pick(const void* src, int64_t src_stride, void* dst, const int32_t* map, int n_dst, int n_src, int row_words,
                   fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Objective scores of a reconstruction (csrc/metrics.hip): SI-SDR, STOI (Taal et al. 2011) and ESTOI (Jensen &
+ * Taal 2016).  This comment is the normative definition.
+ *
+ * Inputs: a reference x and an estimate y, B rows of T fp32 samples (row pitches x_bs, y_bs), lens (B) int32 on the device or
+ * NULL (clamped to [0, T]): row b is its first len_b samples and nothing behind them is read as signal.  All results are fp64.
+ *
+ * SI-SDR (dac/nn/loss.py:91-130 with scaling = True, zero_mean = True, sign flipped: higher is better), eps = 1e-8:
+ *     r = x - mean(x);  e = y - mean(y);  a = (sum e r + eps) / (sum r r + eps);  s = a r;  n = e - s;
+ *     SI-SDR = 10 log10(sum s^2 / sum n^2 + eps) dB.
+ * Three passes over the row (the means; sum e r and sum r r on the centred samples; sum s^2 and sum n^2 with n formed sample by
+ * sample -- never expanded from sums, which cancels when y ~ x).  Whatever the formula gives in IEEE fp64 is the answer:
+ * identical rows +inf, an empty or all-zero pair NaN, a zero reference with a non-zero estimate -80.  Every pass sums chunks of
+ * FAC_SI_SDR_CHUNK samples (chunk c = samples [c chunk, (c + 1) chunk) of the row, whatever T is) in a fixed order and the
+ * chunks of a row in a fixed order: a row scores the same bits alone as in any batch.
+ *   fac_si_sdr: out (B) fp64; ws = fac_si_sdr_ws_bytes(B, T) bytes of device scratch, 8-byte aligned.  T <= 2^30, B <= 65535.
+ *
+ * STOI / ESTOI, at FS = 10000 Hz (the caller resamples): frame length 256, hop 128, NFFT 512, 15 third-octave bands from 150 Hz,
+ * N = 30 frames per segment, BETA = -15 dB, dynamic range 40 dB, EPS = 2.220446049250313e-16, window
+ * w[n] = 0.5 - 0.5 cos(2 pi (n + 1) / 257), n = 0 .. 255.
+ *  1. Windowed frames f_m = w . x[128 m : 128 m + 256], m = 0 .. M - 1, M = (len - 256) / 128 + 1 (0 for len < 256).
+ *  2. E_m = 20 log10(||f_m||_2 + EPS) from the REFERENCE only; frame m is kept iff max_m E - 40 - E_m < 0 (an all-silent
+ *     reference keeps every frame).  Kept frames k_0 < .. < k_{K-1}.  The compacted signals are the overlap-add at hop 128 of
+ *     the kept windowed frames of x and of y, 128 (K - 1) + 256 samples.
+ *  3. The compacted signals are framed again (same window, length, hop: exactly K frames), zero-padded to 512; |X[k]|^2 of the
+ *     one-sided DFT.  Frame j of a compacted signal is never stored: its first half is f_{k_j}[n] + f_{k_{j-1}}[n + 128], its
+ *     second half f_{k_j}[n] + f_{k_{j+1}}[n - 128], the neighbour absent at the ends.
+ *  4. Bands j = 0 .. 14: Tb[j, m] = sqrt(sum_{k = lo_j}^{hi_j - 1} |X[k, m]|^2), (lo, hi) = (7,9) (9,11) (11,14) (14,17) (17,22)
+ *     (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219): the bins nearest
+ *     150 2^(j/3) 2^(-+1/6) Hz on the grid k 10000 / 512.
+ *  5. Segments s = 0 .. K - 30: X_s = Tx[:, s : s + 30], Y_s = Ty[:, s : s + 30] (15 x 30).  K < 30: no segment, both scores NaN.
+ *  6. STOI, per band row of a segment: alpha = ||x|| / (||y|| + EPS); y' = min(alpha y, x (1 + 10^(15/20))); both vectors minus
+ *     their mean, over (their norm + EPS); c = sum x^ y'^.  STOI = the mean of c over all bands and segments.
+ *  7. ESTOI, per segment: rows of X_s and Y_s minus their mean over time, over (norm + EPS); then columns minus their mean over
+ *     bands, over (norm + EPS); d_s = (1 / 30) sum_{j, m} X^ Y^.  ESTOI = the mean of d_s over the segments.
+ * Everything is fp64 (the 512-point transform included), every reduction in a fixed order without atomics; a row scores the
+ * same bits alone as in any batch.
+ *
+ * The three launches share one descriptor and run in this order on one stream; nothing is read back between them.
+ *   fac_stoi_select  E_m per frame, then per row the maximum, the keep flags and an exclusive scan in blocks of out[3] frames
+ *                    with a carried offset: kept_idx (B, M_max) int32 of pitch M_max (the first n_kept[b] entries of a row are
+ *                    the kept frames, the others -1), n_frames, n_kept (B) int32.
+ *   fac_stoi_bands   Tb (B, 2, 15, M_max) fp64 in ws for x and y from one launch; frames j >= n_kept[b] are not computed.
+ *   fac_stoi_score   per (row, segment) sum_j c and d_s, then per row the fixed-order means: stoi, estoi (B) fp64, n_segments (B)
+ *                    int32 (max(n_kept - 29, 0)).
+ *   fac_stoi_geometry(T, out6), host only: out6 = {M_max, ws bytes per row, frames per workgroup of the energy launch, frames
+ *                    per block of the scan, frames per workgroup of fac_stoi_bands, segments per workgroup of fac_stoi_score};
+ *                    ws holds, in this order, E (B, M_max), Tb (B, 2, 15, M_max) and the segment sums (B, 2, max(M_max - 29, 0)),
+ *                    all fp64: out6[1] * B bytes, 8-byte aligned.  -1 for T < 0 or T > 2^28.
+ * Refused before any launch: a NULL descriptor or pointer, B outside 1 .. 65535, T outside 0 .. 2^28, ws_bytes below
+ * out6[1] * B, ws not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define FAC_SI_SDR_CHUNK 4096
+int64_t fac_si_sdr_ws_bytes(int B, int T);
+int fac_si_sdr(const float* x, int64_t x_bs, const float* y, int64_t y_bs, const int32_t* lens, double* out, void* ws, int64_t ws_bytes,
+               int B, int T, fac_stream_t stream);
+typedef struct fac_stoi_desc {
+  const float* x;
+  const float* y;
+  const int32_t* lens;
+  int32_t* kept_idx;
+  int32_t* n_frames;
+  int32_t* n_kept;
+  int32_t* n_segments;
+  double* stoi;
+  double* estoi;
+  void* ws;
+  int64_t x_bs, y_bs, ws_bytes;
+  int32_t B, T;
+} fac_stoi_desc;
+int fac_stoi_geometry(int T, int64_t* out6);
+int fac_stoi_select(const fac_stoi_desc* d, fac_stream_t stream);
+int fac_stoi_bands(const fac_stoi_desc* d, fac_stream_t stream);
+int fac_stoi_score(const fac_stoi_desc* d, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
