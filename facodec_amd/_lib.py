@@ -33,6 +33,7 @@ class ConvDesc(C.Structure):
         ("x_p8", _p), ("x_p8_plane_bytes", _i64), ("y2_p8", _p), ("y2_p8_plane_bytes", _i64),
         ("pw_split", C.c_int32), ("split_rows", C.c_int32),
         ("gate_cond", _p), ("gate_cond_bs", _i64),
+        ("keep_tile160", C.c_int32),
     ]
 
 
@@ -247,6 +248,10 @@ SIGNATURES = {
     "fac_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_attention_stream": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_attention_route": (_i, [_i, _i]),
+    "fac_attention_form": (_i, [_i, _i]),
+    "fac_attention_tiled_fits": (_i, [_i, _i]),
+    "fac_attention_tiled": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fac_attention_serial": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_attention_stream_tile": (_i, [_i]),
     "fac_masked_mean": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_layernorm_c_affine": (_i, [_p, _p, _p, _i, _i, _i, _p]),

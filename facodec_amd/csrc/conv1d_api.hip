@@ -40,7 +40,15 @@ static ConvKernel select_variant(const fac_conv_desc* d) {
   // (measured +15..30 % on the k = 1 layers, neutral on k = 7).
   const bool wide = d->K == 1 && d->n_phase == 1 && d->T_out >= 512;   // (wide tiles measured slower for K = 2)
   // 2 s clips are 160 latent frames: a 160-wide tile wastes nothing where 128 + 32 would waste 37 %
-  if (d->T_out > 128 && d->T_out <= 160 && co > 64) return CK_128x160;
+  if (d->T_out > 128 && d->T_out <= 160 && co > 64) {
+    // ... but it is one workgroup per (clip, 128 rows), and a k = 1 conv has nothing else to spread: the style path's 1025 -> 80,
+    // 80 -> 512 (+ Mish) and 20 -> 256 at 32 clips are 32 / 128 / 64 workgroups on 256 CUs, each walking all 160 columns of every
+    // stage and of the epilogue alone.  Five 32-column tiles per clip instead, while the wide tiles would leave CUs empty; a
+    // k = 1 tile has no halo, so nothing is staged twice but the weights.  keep_tile160 holds the wide tile (A/B, tests).
+    const long long wide_tiles = (long long)d->B * ((co + 127) / 128);
+    if (d->K == 1 && d->stride == 1 && d->n_phase == 1 && !d->keep_tile160 && wide_tiles < 256) return CK_128x32;
+    return CK_128x160;
+  }
   if (co % 128 != 0 && co % 96 == 0) return wide ? CK_96x256 : CK_96x128;
   return wide ? CK_128x256 : CK_128x128;
 }

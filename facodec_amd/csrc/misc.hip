@@ -646,7 +646,7 @@ __global__ __launch_bounds__(256) void logdiff_rms_bwd_kernel(const float* __res
 
 using namespace fac;
 
-extern "C" int fac_version(void) { return 4; }   // 3: fac_conv_desc.row_phases, fac_adamw_step_masked, fac_pack_convtr_w_rows; 4: fac_conv_desc.gate_cond
+extern "C" int fac_version(void) { return 5; }   // 3: fac_conv_desc.row_phases, fac_adamw_step_masked, fac_pack_convtr_w_rows; 4: fac_conv_desc.gate_cond; 5: .keep_tile160
 extern "C" const char* fac_last_error(void) { return fac::g_err; }
 
 #define EW_LAUNCH(kern, n, ...)                                                         \
@@ -736,10 +736,25 @@ extern "C" int fac_attention_route(int dk, int T) {
   return ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float) <= FAC_LDS_MAX ? FAC_ATTN_LDS : FAC_ATTN_STREAM;
 }
 
+// The form of that launch: on the LDS route the register-tiled kernel (attention_tiled.hip) wherever its layout takes the shape,
+// attention_kernel for the rest (dk above 256, or T past 992).  Both return the same bits.
+extern "C" int fac_attention_form(int dk, int T) {
+  if (fac_attention_route(dk, T) == FAC_ATTN_STREAM) return FAC_ATTN_FORM_STREAM;
+  return fac_attention_tiled_fits(dk, T) ? FAC_ATTN_FORM_TILED : FAC_ATTN_FORM_SERIAL;
+}
+
 extern "C" int fac_attention(const float* q, const float* k, const float* v, const float* mask,
                              float* out, int B, int n_heads, int dk, int T, fac_stream_t stream) {
   FAC_REQUIRE(q && k && v && out && B > 0 && n_heads > 0 && dk > 0 && T > 0, "attention: bad arguments");
   if (fac_attention_route(dk, T) == FAC_ATTN_STREAM) return fac_attention_stream(q, k, v, mask, out, B, n_heads, dk, T, stream);
+  if (fac_attention_form(dk, T) == FAC_ATTN_FORM_TILED) return fac_attention_tiled(q, k, v, mask, out, B, n_heads, dk, T, stream);
+  return fac_attention_serial(q, k, v, mask, out, B, n_heads, dk, T, stream);
+}
+
+extern "C" int fac_attention_serial(const float* q, const float* k, const float* v, const float* mask,
+                                    float* out, int B, int n_heads, int dk, int T, fac_stream_t stream) {
+  FAC_REQUIRE(q && k && v && out && B > 0 && n_heads > 0 && dk > 0 && T > 0, "attention_serial: bad arguments");
+  FAC_REQUIRE(fac_attention_route(dk, T) == FAC_ATTN_LDS, "attention_serial: T=%d too long for the LDS score tile at dk=%d", T, dk);
   size_t lds = ((size_t)dk * 16 + (size_t)16 * T) * sizeof(float);
   const size_t lds_v = lds + (size_t)16 * (T + 1) * sizeof(float);       // + 16 rows of V per pass
   const int stage_v = lds_v <= FAC_LDS_MAX ? 1 : 0;

@@ -576,6 +576,7 @@ def conv_desc(B, c_in, t_in, c_out, k, stride=1, dilation=1, pad_left=None, pad_
     d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = 1, 1, act, 0, 0
     d.K1, d.dilation2, d.split_rows = k1, dilation2, split_rows
     d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and (k == 1 or (PW_TAPS and k == 4 and stride == 2))) else 0
+    d.keep_tile160 = 0 if K1_COLUMN_TILES else 1
     return d
 
 
@@ -719,6 +720,9 @@ FLAT_TRAIN = True
 PW_SPLIT = os.environ.get("FAC_PW_SPLIT", "1") != "0"
 # stride-2 layers with few channels on the streaming kernel with taps (conv1d_pw_split.hip, conv1d_pwt_kernel); follows PW_SPLIT
 PW_TAPS = True
+# k = 1 fp32 launches of 129 .. 160 columns per clip whose 128 x 160 tiles would be fewer than 256 workgroups (the style path's
+# 1025 -> 80, 80 -> 512, 20 -> 256 at 32 clips) on five 128 x 32 tiles per clip (conv1d_api.hip: select_variant); False: the wide tile
+K1_COLUMN_TILES = True
 
 
 def pack_conv_for(layout, v, g, stride=1, k1=0, scale=None):
@@ -1302,18 +1306,24 @@ def attention_stream_tiles():
     return lib.fac_attention_stream_tile(0), lib.fac_attention_stream_tile(1)
 
 
+def attention_form(dk, T):
+    """The form of fac_attention's launch for (dk, T): on the "lds" route "tiled" (csrc/attention_tiled.hip: dk <= 256 and
+    T <= 992) or "serial" (attention_kernel of csrc/misc.hip, the same bits); "stream" on the other route."""
+    return ("tiled", "serial", "stream")[_lib.load().fac_attention_form(int(dk), int(T))]
+
+
 def attention(q, k, v, mask, n_heads, kernel=None):
     """kernel: None (attention_route decides), or "lds" / "stream" to force a route (tests, A/B runs; "lds" past its LDS limit is
-    an error)."""
-    if kernel not in (None, "lds", "stream"):
-        raise ValueError(f"attention: kernel={kernel!r} (None, 'lds' or 'stream')")
+    an error), or "serial" to force the LDS route's one-thread-per-output kernel where attention_form would say "tiled"."""
+    if kernel not in (None, "lds", "stream", "serial"):
+        raise ValueError(f"attention: kernel={kernel!r} (None, 'lds', 'stream' or 'serial')")
     q, k, v = _dev(q), _dev(k), _dev(v)
     B, c, T = q.shape
     dk = c // n_heads
     out = torch.empty_like(q)
-    if kernel == "lds" and attention_route(dk, T) != "lds":
+    if kernel in ("lds", "serial") and attention_route(dk, T) != "lds":
         raise _lib.FacodecHipError(f"attention: T={T} too long for the LDS score tile at dk={dk}")
-    name = "fac_attention_stream" if kernel == "stream" else "fac_attention"
+    name = {"stream": "fac_attention_stream", "serial": "fac_attention_serial"}.get(kernel, "fac_attention")
     _lib.check(getattr(_lib.load(), name)(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(out), B, n_heads, dk, T, _stream()), name)
     return out
 

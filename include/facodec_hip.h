@@ -193,6 +193,10 @@ typedef struct fac_conv_desc {
    * followed by fac_gate_tanh_sigmoid with g (WN with gin_channels, modules/wavenet.py:146-155).  NULL: no conditioning. */
   const float* gate_cond;
   int64_t gate_cond_bs;
+  /* Optional (0 = off): keep the 128 x 160 fp32 tile for a k = 1 launch of 129 .. 160 columns per clip that would otherwise run on
+   * five 128 x 32 tiles per clip because B * ceil(C_out / 128) wide tiles are fewer than 256 workgroups.  For A/B runs and for the
+   * test that holds the two forms against each other; ignored by every other launch. */
+  int32_t keep_tile160;
 } fac_conv_desc;
 
 int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream);
@@ -726,6 +730,21 @@ int fac_attention_stream(const float* q, const float* k, const float* v, const f
 #define FAC_ATTN_LDS 0
 #define FAC_ATTN_STREAM 1
 int fac_attention_route(int dk, int T);
+/* The form of fac_attention's launch for (dk, T), from the shapes alone.  On the FAC_ATTN_LDS route: FAC_ATTN_FORM_TILED, the
+ * register-tiled kernel (csrc/attention_tiled.hip), while fac_attention_tiled_fits -- dk <= 256 and one pass of V (256 x 36
+ * floats) plus 32 score rows of T rounded up to 32 keys fit the 160 KiB of LDS, i.e. T <= 992 -- and FAC_ATTN_FORM_SERIAL, the
+ * kernel of csrc/misc.hip with one thread per output, past that.  The two return the same bits for the same inputs.
+ * fac_attention_tiled / fac_attention_serial launch one form whatever fac_attention would choose (arguments as fac_attention;
+ * a shape the form does not take is FAC_ERR_ARG). */
+#define FAC_ATTN_FORM_TILED 0
+#define FAC_ATTN_FORM_SERIAL 1
+#define FAC_ATTN_FORM_STREAM 2
+int fac_attention_form(int dk, int T);
+int fac_attention_tiled_fits(int dk, int T);
+int fac_attention_tiled(const float* q, const float* k, const float* v, const float* mask, float* out,
+                        int B, int n_heads, int dk, int T, fac_stream_t stream);
+int fac_attention_serial(const float* q, const float* k, const float* v, const float* mask, float* out,
+                         int B, int n_heads, int dk, int T, fac_stream_t stream);
 /* Tile sizes of fac_attention_stream: which = 0 queries per workgroup, 1 keys per LDS tile. */
 int fac_attention_stream_tile(int which);
 /* masked temporal average pool (modules/style_encoder.py:83-91): out[b,c] = sum_t x / sum_t mask */
