@@ -59,6 +59,27 @@ class VqDecodeDesc(C.Structure):
     ]
 
 
+class VqDecodeMaskedDesc(C.Structure):
+    _fields_ = [("base", VqDecodeDesc), ("n_use", _p), ("n_use_bs", _i64), ("n_use_ts", _i64)]
+
+
+PLC_MAX_FRAMES = 16                      # FAC_PLC_MAX_FRAMES
+PLC_PRIMARY, PLC_REDUNDANT, PLC_LOST = 0, 1, 2
+
+
+class PlcSelectDesc(C.Structure):
+    _fields_ = [
+        ("prim", _p * 3), ("prim_bs", _i64 * 3), ("prim_qs", _i64 * 3),
+        ("red", _p * 3), ("red_bs", _i64 * 3), ("red_qs", _i64 * 3),
+        ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3),
+        ("n_q", C.c_int32 * 3), ("n_red", C.c_int32 * 3),
+        ("status", _p), ("last_codes", _p), ("last_n", _p), ("g", _p), ("run", _p),
+        ("n_use", _p), ("n_use_bs", _i64), ("n_use_ts", _i64), ("ramp", _p),
+        ("B", C.c_int32), ("k", C.c_int32), ("hold", C.c_int32), ("fade", C.c_int32), ("recover", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class CodesPackDesc(C.Structure):
     _fields_ = [
         ("codes", _p * 3), ("codes_bs", _i64 * 3), ("codes_qs", _i64 * 3), ("n_q", C.c_int32 * 3),
@@ -229,6 +250,9 @@ SIGNATURES = {
     "fac_vq_fwd": (_i, [C.POINTER(VqDesc), _p]),
     "fac_vq_loss_tiles": (_i, [_i]),
     "fac_vq_decode": (_i, [C.POINTER(VqDecodeDesc), _p]),
+    "fac_vq_decode_masked": (_i, [C.POINTER(VqDecodeMaskedDesc), _p]),
+    "fac_plc_select": (_i, [C.POINTER(PlcSelectDesc), _p]),
+    "fac_plc_gain": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),
     "fac_codes_unpack": (_i, [C.POINTER(CodesUnpackDesc), _p]),
     "fac_codes_row_bytes": (_i64, [_i, _i, _i]),

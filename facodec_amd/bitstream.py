@@ -18,6 +18,17 @@ Container, everything little-endian:
 Packet of one streaming push, per stream:  b"FP", seq uint16 (wrapping), n_frames uint16, payload ceil(n_frames Q bits / 8)
 bytes, CRC-32 of every preceding byte.  What Q and bits are is the stream header's business (a container with flag bit1 and
 F = 0, sent once per stream).  A lost packet is reported (PacketLoss), not concealed.
+
+Packet with in-band redundancy, per stream:
+
+     0  2s  b"FQ"             6  H   n_red_frames (0: no redundant payload, the first push)
+     2  H   seq (wrapping)    8  3B  n_red = (rp, rc, rr), each <= the stream's n_q
+     4  H   n_frames         11      primary payload, ceil(n_frames Q bits / 8) bytes
+    ..      redundant payload, ceil(n_red_frames (rp + rc + rr) bits / 8) bytes: the PREVIOUS push's leading rp / rc / rr
+            quantizers of the three RVQs, in the same normative layout (frame-major, quantizer order, LSB-first)
+    ..  I   CRC-32 of every preceding byte
+
+LossyPacketReader reads both kinds per stream and never raises for a loss; what is played for one is StreamingReceiver's business.
 """
 import struct
 import zlib
@@ -77,9 +88,12 @@ def payload_bytes(F, Q, bits):
     return (int(F) * int(Q) * int(bits) + 7) // 8
 
 
-def bitrate(n_q, bits, frame_rate=80):
-    """Payload bits per second for quantizer counts n_q = (n_p, n_c, n_r) (or their sum): Q * bits * frame_rate."""
+def bitrate(n_q, bits, frame_rate=80, redundancy=None):
+    """Payload bits per second for quantizer counts n_q = (n_p, n_c, n_r) (or their sum): Q * bits * frame_rate.  redundancy =
+    (rp, rc, rr) (or their sum) adds the share of the in-band redundant copy: (Q + R) * bits * frame_rate."""
     Q = sum(n_q) if isinstance(n_q, (tuple, list)) else int(n_q)
+    if redundancy is not None:
+        Q += sum(redundancy) if isinstance(redundancy, (tuple, list)) else int(redundancy)
     return Q * bits * frame_rate
 
 
@@ -215,3 +229,104 @@ class PacketReader:
             raise PacketLoss(missing)
         self.expected = (seq + 1) & 0xFFFF
         return n_frames, [p[2] for p in parsed]
+
+
+# ------------------------------------------------------------------------------------ packets that survive a loss
+FEC_MAGIC = b"FQ"
+_QHEAD = struct.Struct("<2sHHH3B")
+FEC_OVERHEAD = _QHEAD.size + 4               # 15 bytes around the two payloads
+assert _QHEAD.size == 11
+
+Packet = namedtuple("Packet", "seq n_frames payload n_red_frames n_red red_payload")
+Packet.__doc__ = """A parsed packet of either kind; an b"FP" packet has n_red_frames = 0, n_red = (0, 0, 0), red_payload = b""."""
+
+
+def _check_red(n_red, n_q, what):
+    n_red = tuple(int(n) for n in n_red)
+    if len(n_red) != 3 or any(not 0 <= r <= n for r, n in zip(n_red, n_q)):
+        raise ValueError(f"{what}: redundant quantizer counts {n_red} are not three counts within n_q = {tuple(n_q)}")
+    return n_red
+
+
+def write_packet_fec(seq, n_frames, payload, n_red_frames=0, n_red=(0, 0, 0), red_payload=b""):
+    """One push of one stream with the previous push's redundant layer: b"FQ", seq (modulo 65536), n_frames, n_red_frames, n_red,
+    primary payload, redundant payload, CRC-32.  The payload lengths are the caller's (read_packet_fec checks them against the
+    layout it is handed)."""
+    if not 0 <= n_frames <= 0xFFFF or not 0 <= n_red_frames <= 0xFFFF:
+        raise ValueError(f"packet: n_frames = {n_frames} / n_red_frames = {n_red_frames} do not fit 16 bits")
+    n_red = tuple(int(n) for n in n_red)
+    if len(n_red) != 3 or any(not 0 <= n <= MAX_Q for n in n_red):
+        raise ValueError(f"packet: redundant quantizer counts {n_red} (three counts, 0..{MAX_Q})")
+    body = _QHEAD.pack(FEC_MAGIC, seq & 0xFFFF, n_frames, n_red_frames, *n_red) + bytes(payload) + bytes(red_payload)
+    return body + struct.pack("<I", zlib.crc32(body))
+
+
+def read_packet_fec(blob, n_q, bits):
+    """-> Packet(seq, n_frames, payload, n_red_frames, n_red, red_payload) for the stream layout n_q = (n_p, n_c, n_r), bits.
+    ValueError for a short packet, a wrong magic, a CRC failure, n_red beyond n_q, redundant frames without redundant
+    quantizers, or a length that is not 15 + payload_bytes(n_frames, Q, bits) + payload_bytes(n_red_frames, R, bits)."""
+    blob = bytes(blob)
+    if len(blob) < FEC_OVERHEAD:
+        raise ValueError(f"packet: truncated ({len(blob)} bytes)")
+    magic, seq, n_frames, n_red_frames, rp, rc, rr = _QHEAD.unpack_from(blob)
+    if magic != FEC_MAGIC:
+        raise ValueError(f"packet: wrong magic {magic!r} (expected {FEC_MAGIC!r})")
+    crc, = struct.unpack_from("<I", blob, len(blob) - 4)
+    if zlib.crc32(blob[:-4]) != crc:
+        raise ValueError("packet: CRC mismatch (corrupt packet)")
+    n_red = _check_red((rp, rc, rr), n_q, "packet")
+    if n_red_frames and not sum(n_red):
+        raise ValueError(f"packet: {n_red_frames} redundant frames of no quantizers")
+    n1, n2 = payload_bytes(n_frames, sum(n_q), bits), payload_bytes(n_red_frames, sum(n_red), bits)
+    if len(blob) - FEC_OVERHEAD != n1 + n2:
+        raise ValueError(f"packet: {len(blob) - FEC_OVERHEAD} payload bytes, {n_frames} frames x {sum(n_q)} x {bits} bits and "
+                         f"{n_red_frames} redundant frames x {sum(n_red)} x {bits} bits need {n1} + {n2}")
+    return Packet(seq, n_frames, blob[_QHEAD.size:_QHEAD.size + n1], n_red_frames, n_red, blob[_QHEAD.size + n1:-4])
+
+
+class LossyPacketReader:
+    """Byte-level half of a receiver that survives loss: per push one entry per stream in -- a packet (b"FP" or b"FQ") or None --
+    and per stream the parsed Packet or None out.  Every stream is judged on its own:
+
+        rd = LossyPacketReader(n_streams, n_q, bits)
+        parsed = rd.feed(packets)                  # parsed[b] is a Packet, or None: missing, corrupt or of the wrong seq
+
+    Every feed() is one push: the expected seq advances by one (modulo 65536) whatever arrived.  A packet that does not parse
+    (truncation, magic, CRC, a length that disagrees with the layout) counts in corrupt[b], one with another seq than the expected
+    in misordered[b], a good one in received[b]; the first two are treated as missing.  feed() never raises for a loss (only for
+    a list that has not one entry per stream)."""
+
+    def __init__(self, n_streams, n_q, bits, first_seq=0):
+        self.n_streams, self.n_q, self.bits = int(n_streams), tuple(int(n) for n in n_q), int(bits)
+        _check_layout(self.bits, self.n_q, "LossyPacketReader")
+        self.expected = first_seq & 0xFFFF
+        self.received, self.corrupt, self.misordered = ([0] * self.n_streams for _ in range(3))
+
+    def parse(self, blob):
+        """One packet of either kind -> Packet; ValueError as read_packet / read_packet_fec."""
+        blob = bytes(blob)
+        if blob[:2] == FEC_MAGIC:
+            return read_packet_fec(blob, self.n_q, self.bits)
+        seq, n_frames, payload = read_packet(blob, sum(self.n_q), self.bits)
+        return Packet(seq, n_frames, payload, 0, (0, 0, 0), b"")
+
+    def feed(self, packets):
+        packets = list(packets)
+        if len(packets) != self.n_streams:
+            raise ValueError(f"{len(packets)} entries for {self.n_streams} streams")
+        out = []
+        for b, blob in enumerate(packets):
+            pkt = None
+            if blob is not None:
+                try:
+                    pkt = self.parse(blob)
+                except ValueError:
+                    self.corrupt[b] += 1
+                if pkt is not None and pkt.seq != self.expected:
+                    self.misordered[b] += 1
+                    pkt = None
+                if pkt is not None:
+                    self.received[b] += 1
+            out.append(pkt)
+        self.expected = (self.expected + 1) & 0xFFFF
+        return out

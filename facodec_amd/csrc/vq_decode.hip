@@ -23,6 +23,14 @@
 //   store     lane = frame: every row segment of the tile is written with consecutive lanes on consecutive frames.
 // The optional per-RVQ sums z_p / z_c / z_r (from_codes) are stored straight from the projection (lane = channel, TT
 // consecutive frames per lane); they are off the decode path.
+//
+// fac_vq_decode_masked is the same kernel body with MASKED = true: quantizer counts per (row, frame).  The tile's
+// counts (3 x TT int32, clamped to [0, n_q[r]]) are read once into LDS; in the projection a quantizer's term of frame t is
+// computed and added only when its index within its RVQ is below the frame's count -- the predicate is wave-uniform (it does not
+// depend on the channel), and a skipped term's __fadd_rn is not executed, so a frame's chain is exactly the chain of the unmasked
+// kernel launched with that frame's counts.  Gather, finish order, norm and store are untouched.
+#include <type_traits>
+
 #include "common.h"
 
 namespace fac {
@@ -46,7 +54,13 @@ struct VqDecArgs {
   int B, D, T, Kc, tt_log2;
 };
 
-__global__ __launch_bounds__(256) void vq_decode_kernel(VqDecArgs a) {
+struct VqDecMaskedArgs : VqDecArgs {
+  const int* n_use;                           // [b * n_use_bs + t * n_use_ts + r]
+  long long n_use_bs, n_use_ts;
+};
+
+template <bool MASKED>
+__global__ __launch_bounds__(256) void vq_decode_kernel(std::conditional_t<MASKED, VqDecMaskedArgs, VqDecArgs> a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int TT = 1 << a.tt_log2;
   const int XS = TT + 1;                                 // LDS row stride of the column block
@@ -55,11 +69,21 @@ __global__ __launch_bounds__(256) void vq_decode_kernel(VqDecArgs a) {
   float* rows = xs + (((long long)a.D * XS + 3) & ~3ll); // [nqt][16][8] codebook rows, 16-byte aligned
   float* red = rows + nqt * VD_TT * VD_CD;               // [2][4][16]
   float* stat = red + 2 * 4 * VD_TT;                     // [2][16]  mean, rstd
+  int* nu = reinterpret_cast<int*>(stat + 2 * VD_TT);    // [3][16]  MASKED only: the tile's quantizer counts
 
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * TT;
   const long long bofs = (long long)b * a.D * a.T;
+
+  if constexpr (MASKED) {
+    if (tid < 3 * TT) {
+      const int r = tid >> a.tt_log2, l = tid & (TT - 1);
+      const int t = min(t0 + l, a.T - 1);
+      const int n = a.n_use[(long long)b * a.n_use_bs + (long long)t * a.n_use_ts + r];
+      nu[r * VD_TT + l] = n < 0 ? 0 : (n > a.n_q[r] ? a.n_q[r] : n);
+    }
+  }
 
   // ---- gather the tile's codebook rows
   for (int i = tid; i < nqt * TT; i += 256) {
@@ -121,9 +145,10 @@ __global__ __launch_bounds__(256) void vq_decode_kernel(VqDecArgs a) {
         const int q = q0 + u;
         if (q >= nqt) break;
         const float* rq = rows + q * VD_TT * VD_CD;
+        const int qi = q - (r > 0 ? q_end[r - 1] : 0);   // MASKED: index within RVQ r (r is q's RVQ here)
 #pragma unroll
         for (int t = 0; t < VD_TT; ++t) {
-          if (t < TT) {
+          if (t < TT && (!MASKED || qi < nu[r * VD_TT + t])) {
             const float4 lo = *reinterpret_cast<const float4*>(rq + t * VD_CD);
             const float4 hi = *reinterpret_cast<const float4*>(rq + t * VD_CD + 4);
             float o = __fmul_rn(w[u][0], lo.x);
@@ -194,8 +219,10 @@ __global__ __launch_bounds__(256) void vq_decode_kernel(VqDecArgs a) {
 
 }  // namespace fac
 
-extern "C" int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream) {
-  using namespace fac;
+namespace fac {
+
+static int vq_decode_launch(const fac_vq_decode_desc* d, const int32_t* n_use, int64_t n_use_bs, int64_t n_use_ts,
+                            fac_stream_t stream) {
   FAC_REQUIRE(d && d->style && d->outs, "vq_decode: null pointer");
   FAC_REQUIRE(d->B > 0 && d->D > 0 && d->T > 0 && d->Kc > 0, "vq_decode: bad shape");
   FAC_REQUIRE(d->B <= 65535, "vq_decode: B too large");
@@ -208,13 +235,17 @@ extern "C" int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream) {
   FAC_REQUIRE(nqt <= FAC_VQ_DECODE_MAX_Q, "vq_decode: %d quantizers (at most %d)", nqt, FAC_VQ_DECODE_MAX_Q);
   for (int q = 0; q < nqt; ++q)
     FAC_REQUIRE(d->codebook[q] && d->w_out[q] && d->b_out[q], "vq_decode: null weight of quantizer %d", q);
+  if (n_use)
+    FAC_REQUIRE((d->B == 1 || n_use_bs > 0) && (d->T == 1 || n_use_ts > 0),
+                "vq_decode_masked: n_use strides (%lld, %lld) cannot address (B = %d, T = %d, 3)", (long long)n_use_bs,
+                (long long)n_use_ts, d->B, d->T);
   int tt_log2 = 0;
   while ((1 << tt_log2) < VD_TT && (1 << tt_log2) < d->T) ++tt_log2;
   const int TT = 1 << tt_log2;
-  const size_t lds = ((((size_t)d->D * (TT + 1) + 3) & ~(size_t)3) + (size_t)nqt * VD_TT * VD_CD + 2 * 4 * VD_TT + 2 * VD_TT) * 4;
+  const size_t lds = ((((size_t)d->D * (TT + 1) + 3) & ~(size_t)3) + (size_t)nqt * VD_TT * VD_CD + 2 * 4 * VD_TT + 2 * VD_TT +
+                      (n_use ? 3 * VD_TT : 0)) * 4;
   FAC_REQUIRE(lds <= FAC_LDS_MAX, "vq_decode: %d channels x %d frames do not fit LDS", d->D, TT);
-  allow_dynamic_lds<vq_decode_kernel>();
-  VqDecArgs a;
+  VqDecMaskedArgs a;
   for (int r = 0; r < 3; ++r) {
     a.codes[r] = reinterpret_cast<const long long*>(d->codes[r]);
     a.codes_bs[r] = d->codes_bs[r];
@@ -232,7 +263,28 @@ extern "C" int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream) {
   a.style = d->style;
   a.outs = d->outs;
   a.B = d->B; a.D = d->D; a.T = d->T; a.Kc = d->Kc; a.tt_log2 = tt_log2;
+  a.n_use = n_use;
+  a.n_use_bs = n_use_bs;
+  a.n_use_ts = n_use_ts;
   const int n_tiles = (d->T + TT - 1) / TT;
-  hipLaunchKernelGGL(vq_decode_kernel, dim3(n_tiles, d->B), dim3(256), lds, (hipStream_t)stream, a);
+  if (n_use) {
+    allow_dynamic_lds<vq_decode_kernel<true>>();
+    hipLaunchKernelGGL(vq_decode_kernel<true>, dim3(n_tiles, d->B), dim3(256), lds, (hipStream_t)stream, a);
+    return check_launch("vq_decode_masked");
+  }
+  allow_dynamic_lds<vq_decode_kernel<false>>();
+  hipLaunchKernelGGL(vq_decode_kernel<false>, dim3(n_tiles, d->B), dim3(256), lds, (hipStream_t)stream,
+                     static_cast<const VqDecArgs&>(a));
   return check_launch("vq_decode");
+}
+
+}  // namespace fac
+
+extern "C" int fac_vq_decode(const fac_vq_decode_desc* d, fac_stream_t stream) {
+  return fac::vq_decode_launch(d, nullptr, 0, 0, stream);
+}
+
+extern "C" int fac_vq_decode_masked(const fac_vq_decode_masked_desc* d, fac_stream_t stream) {
+  FAC_REQUIRE(d, "vq_decode_masked: null descriptor");
+  return fac::vq_decode_launch(&d->base, d->n_use, d->n_use_bs, d->n_use_ts, stream);
 }

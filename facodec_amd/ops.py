@@ -1039,16 +1039,20 @@ def vq_step(z_in, w_in_packed, b_in, codebook, w_out, w_out_scale, b_out, codes_
     _lib.check(_lib.load().fac_vq_fwd(C.byref(d), _stream()), "fac_vq_fwd")
 
 
-def vq_decode(codes, weights, style, Kc, out=None, z_out=(None, None, None)):
+def vq_decode(codes, weights, style, Kc, out=None, z_out=(None, None, None), n_use=None):
     """Codes of the prosody / content / residual RVQs -> decoder input (fac_vq_decode: from_codes of each RVQ, their sum, the
     timbre-conditioned LayerNorm).  codes: three int64 (B, n_r, T) tensors (any batch / row stride, unit frame stride) or None
     for an RVQ without quantizers; weights: per RVQ a list of n_r tuples (codebook (Kc, 8), out_proj weight_v (D, 8, 1),
     weight-norm scale (D) or None, bias (D)); style (B, 2D) = [gamma | beta].  z_out: optional (B, D, T) buffers for the
-    per-RVQ sums.  Codes are not range checked here (the kernel clamps them for the load)."""
+    per-RVQ sums.  Codes are not range checked here (the kernel clamps them for the load).
+    n_use: optional int32 (B, T, 3) on the device (any batch / frame stride, unit stride over the three counts): the number of
+    leading quantizers of each RVQ that frame (b, t) is decoded from (fac_vq_decode_masked) -- every frame then
+    equals, bit for bit, the frame of a call whose codes and weights are cut to those counts."""
     style = _dev(style, "style")
     B, D2 = style.shape
     D = D2 // 2
-    d = VqDecodeDesc()
+    md = _lib.VqDecodeMaskedDesc() if n_use is not None else None
+    d = md.base if md is not None else VqDecodeDesc()
     T, q = None, 0
     for r in range(3):
         c, ws = codes[r], weights[r]
@@ -1082,7 +1086,90 @@ def vq_decode(codes, weights, style, Kc, out=None, z_out=(None, None, None)):
         d.z[r] = zo.data_ptr() if zo is not None else None
     assert out.is_contiguous() and tuple(out.shape) == (B, D, T)
     d.B, d.D, d.T, d.Kc = B, D, T, Kc
+    if md is not None:
+        if not isinstance(n_use, torch.Tensor) or not n_use.is_cuda:
+            raise _lib.FacodecHipError(f"vq_decode: n_use must live on the GPU (got {getattr(n_use, 'device', type(n_use))}); there is no CPU path")
+        if n_use.dtype != torch.int32 or tuple(n_use.shape) != (B, T, 3) or n_use.stride(2) != 1:
+            raise ValueError(f"vq_decode: n_use must be int32 ({B}, {T}, 3) with unit stride over the counts, got {n_use.dtype} "
+                             f"{tuple(n_use.shape)} strides {tuple(n_use.stride())}")
+        md.n_use, md.n_use_bs, md.n_use_ts = n_use.data_ptr(), n_use.stride(0), n_use.stride(1)
+        _lib.check(_lib.load().fac_vq_decode_masked(C.byref(md), _stream()), "fac_vq_decode_masked")
+        return out
     _lib.check(_lib.load().fac_vq_decode(C.byref(d), _stream()), "fac_vq_decode")
+    return out
+
+
+class PlcState:
+    """Device-resident concealment state of B rows (fac_plc_select): last_codes (B, Q) int64, last_n (B, 3) int32, the gain g (B)
+    fp32 (1: nothing is faded) and run (B) int32, the concealed frames in a row."""
+
+    def __init__(self, B, n_q, device):
+        self.B, self.n_q = int(B), tuple(int(n) for n in n_q)
+        self.last_codes = torch.zeros(self.B, sum(self.n_q), dtype=torch.int64, device=device)
+        self.last_n = torch.zeros(self.B, 3, dtype=torch.int32, device=device)
+        self.g = torch.ones(self.B, dtype=torch.float32, device=device)
+        self.run = torch.zeros(self.B, dtype=torch.int32, device=device)
+
+
+def _plc_codes(d, name, codes, counts, B, k, what):
+    ptr, bs, qs = getattr(d, name), getattr(d, name + "_bs"), getattr(d, name + "_qs")
+    for r in range(3):
+        if counts[r] == 0:
+            continue
+        c = codes[r] if codes is not None else None
+        if not isinstance(c, torch.Tensor) or not c.is_cuda:
+            raise _lib.FacodecHipError(f"plc_select: {what} codes must live on the GPU (RVQ {r}: {getattr(c, 'device', type(c))}); there is no CPU path")
+        if c.dtype != torch.int64 or tuple(c.shape) != (B, counts[r], k) or (k > 1 and c.stride(2) != 1):
+            raise ValueError(f"plc_select: {what} codes of RVQ {r} must be int64 ({B}, {counts[r]}, {k}) with unit frame stride, got "
+                             f"{c.dtype} {tuple(c.shape)} strides {tuple(c.stride())}")
+        ptr[r], bs[r], qs[r] = c.data_ptr(), c.stride(0), c.stride(1)
+
+
+def plc_select(prim, red, status, state, dst, n_use, ramp, n_red=(0, 0, 0), hold=2, fade=6, recover=1):
+    """One push of the concealment state machine (fac_plc_select): per row, status (B) int32 (0 PRIMARY, 1 REDUNDANT,
+    2 LOST) picks what dst -- three int64 (B, n_q[r], k) tensors, possibly prim itself -- is filled with: prim, the redundant
+    codes red ((B, n_red[r], k), quantizers beyond n_red written as 0), or the state's last played frame.  Writes n_use (B, k, 3)
+    int32 for ops.vq_decode, ramp (B, k + 1) fp32 for plc_gain, and advances `state` (PlcState).  One launch, nothing read back."""
+    B, n_q = state.B, state.n_q
+    n_red = tuple(int(n) for n in n_red)
+    k = next(c for c, n in zip(prim, n_q) if n).shape[-1]
+    d = _lib.PlcSelectDesc()
+    _plc_codes(d, "prim", prim, n_q, B, k, "primary")
+    _plc_codes(d, "red", red, n_red, B, k, "redundant")
+    _plc_codes(d, "dst", dst, n_q, B, k, "destination")
+    for r in range(3):
+        d.n_q[r], d.n_red[r] = n_q[r], n_red[r]
+    for t, dt, shape, what in ((status, torch.int32, (B,), "status"), (n_use, torch.int32, (B, k, 3), "n_use"),
+                               (ramp, torch.float32, (B, k + 1), "ramp")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.FacodecHipError(f"plc_select: {what} must live on the GPU; there is no CPU path")
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError(f"plc_select: {what} must be {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    if not status.is_contiguous() or not ramp.is_contiguous() or n_use.stride(2) != 1:
+        raise ValueError("plc_select: status and ramp must be dense, n_use needs unit stride over the counts")
+    d.status, d.last_codes, d.last_n, d.g, d.run = status.data_ptr(), state.last_codes.data_ptr(), state.last_n.data_ptr(), \
+        state.g.data_ptr(), state.run.data_ptr()
+    d.n_use, d.n_use_bs, d.n_use_ts, d.ramp = n_use.data_ptr(), n_use.stride(0), n_use.stride(1), ramp.data_ptr()
+    d.B, d.k, d.hold, d.fade, d.recover = B, k, int(hold), int(fade), int(recover)
+    _lib.check(_lib.load().fac_plc_select(C.byref(d), _stream()), "fac_plc_select")
+
+
+def plc_gain(wave, ramp, out=None, frame=300):
+    """wave (B, 1, k frame) or (B, k frame) fp32 times the piecewise-linear gain through ramp (B, k + 1) (fac_plc_gain): sample n
+    of frame f is scaled by ramp[f] + (ramp[f + 1] - ramp[f]) * ((n + 1) / frame), each operation rounded on its own.  out may be
+    wave (in place); a row whose ramp is 1 everywhere comes back bit for bit."""
+    wave = _dev(wave, "wave")
+    ramp = _dev(ramp, "ramp")
+    B, k = ramp.shape[0], ramp.shape[1] - 1
+    if wave.shape[0] != B or wave.numel() != B * k * frame or (wave.shape[-1] > 1 and wave.stride(-1) != 1) or not ramp.is_contiguous():
+        raise ValueError(f"plc_gain: wave {tuple(wave.shape)} does not hold {B} rows of {k} x {frame} samples (ramp {tuple(ramp.shape)})")
+    if out is None:
+        out = torch.empty_like(wave, memory_format=torch.contiguous_format)
+    if out.shape != wave.shape or out.dtype != torch.float32 or not out.is_cuda or (out.shape[-1] > 1 and out.stride(-1) != 1):
+        raise ValueError(f"plc_gain: out must be a float32 device tensor of shape {tuple(wave.shape)}")
+    x_bs = wave.stride(0) if B > 1 else k * frame
+    y_bs = out.stride(0) if B > 1 else k * frame
+    _lib.check(_lib.load().fac_plc_gain(_ptr(wave), x_bs, _ptr(out), y_bs, _ptr(ramp), B, k, int(frame), _stream()), "fac_plc_gain")
     return out
 
 

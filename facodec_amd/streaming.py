@@ -907,6 +907,81 @@ class StreamingDecoder:
             return wave
 
 
+class LayeredDecoder(StreamingDecoder):
+    """StreamingDecoder whose quantizer counts may differ per stream, per push and per frame:
+
+        rx = LayeredDecoder(model, timbre)
+        wave = rx.prime(codes)                               # as StreamingDecoder (n_use= as in push)
+        wave = rx.push(codes, n_use)                         # n_use (B, k, 3) int32 on the device, or None: every quantizer
+
+    n_use[b, t, r] is the number of leading quantizers of RVQ r that frame t of stream b is decoded from (clamped to the
+    session's counts; the codes of the others are ignored).  The counts are copied into a static (B, max_frames, 3) buffer and
+    the hop's codes-to-latent launch is fac_vq_decode_masked on that buffer, so it sits inside the captured graphs, whose
+    keying is StreamingDecoder's.  With n_use=None, or full counts, the output is StreamingDecoder's bit for bit; a row decoded
+    with (a, b, c) throughout is, bit for bit, its row in a StreamingDecoder session primed with the codes cut to (a, b, c)."""
+
+    def __init__(self, model, timbre, use_graphs=True, max_frames=16):
+        super().__init__(model, timbre, use_graphs=use_graphs, max_frames=max_frames)
+        self._n_use = self._n_full = self._pending = None
+        self._static = False
+
+    def _step(self, k):
+        codes = [self._codes[r][:, :, :k] if self._n_q[r] else None for r in range(3)]
+        outs = ops.vq_decode(codes, self._wsel, self.style, self.q.prosody_quantizer.codebook_size, n_use=self._n_use[:, :k])
+        return self.dec.run(outs)
+
+    def _load(self, codes, k):
+        if self._n_use is None:
+            self._n_full = torch.tensor(self._n_q, dtype=torch.int32, device=self.device).expand(self.B, self.max_frames, 3).contiguous()
+            self._n_use = self._n_full.clone()
+        if self._static:
+            return
+        super()._load(codes, k)
+        self._n_use[:, :k].copy_(self._n_full[:, :k] if self._pending is None else self._pending)
+
+    def _check_n_use(self, codes, n_use):
+        if n_use is None:
+            return
+        k = codes[0].shape[-1]
+        if not isinstance(n_use, torch.Tensor) or n_use.dtype != torch.int32 or tuple(n_use.shape) != (self.B, k, 3) \
+                or n_use.device != codes[0].device:
+            raise ValueError(f"n_use must be an int32 (B={self.B}, k={k}, 3) tensor on the codes' device")
+
+    def prime(self, codes, n_use=None):
+        self._check(codes)
+        self._check_n_use(codes, n_use)
+        self._pending = n_use
+        try:
+            return super().prime(codes)
+        finally:
+            self._pending = None
+
+    def push(self, codes, n_use=None):
+        self._check(codes)
+        self._check_n_use(codes, n_use)
+        self._pending = n_use
+        try:
+            return super().push(codes)
+        finally:
+            self._pending = None
+
+    def buffers(self, k):
+        """The session's static buffers for a push of k frames: ([codes_p, codes_c, codes_r] views (B, n_q[r], k), n_use (B, k, 3)).
+        A caller that fills them on the device (fac_plc_select) plays them with push_buffers(k), without a copy."""
+        if self._n_q is None:
+            raise RuntimeError("call prime() first")
+        return [self._codes[r][:, :self._n_q[r], :k] for r in range(3)], self._n_use[:, :k]
+
+    def push_buffers(self, k):
+        """push() of what buffers(k) holds now."""
+        codes, _ = self.buffers(k)
+        self._static = True
+        try:
+            return super().push(codes)
+        finally:
+            self._static = False
+
+
 class StreamingResampler:
     """ops.resample one block at a time, over B parallel streams:
 
@@ -1123,13 +1198,24 @@ class CodePacketizer:
     bits / 32)) bytes instead of three int64 tensors); the codes may be a session's static graph buffers, they are read before
     packet() returns.  It sits outside the captured graphs.  A packet is b"FP", seq uint16 (wrapping, the same for all streams
     of a push), n_frames uint16, ceil(k Q bits / 8) payload bytes, CRC-32 (bitstream.write_packet).  codes with fewer entries
-    than three (StreamingConverter emits [p, c]) stand for n_q with trailing zeros."""
+    than three (StreamingConverter emits [p, c]) stand for n_q with trailing zeros.
 
-    def __init__(self, n_q, bits=10, codebook_size=1024):
+    redundancy = (rp, rc, rr), elementwise <= n_q (e.g. (1, 2, 0)): in-band redundancy.  Packets are then b"FQ"
+    (bitstream.write_packet_fec): call j carries its own codes and, behind them, the leading rp / rc / rr quantizers of call
+    j - 1 (none on the first call), so a receiver that waits one push (StreamingReceiver(delay=1)) can play a lost push at the
+    lower rate.  Two pack launches into one buffer, still one device-to-host copy.  With None the packets are the bytes of before."""
+
+    def __init__(self, n_q, bits=10, codebook_size=1024, redundancy=None):
         from . import bitstream
         self.n_q = tuple(int(n) for n in n_q) + (0,) * (3 - len(n_q))
         bitstream._check_layout(bits, self.n_q, "CodePacketizer")
         self.bits, self.codebook_size, self.seq = int(bits), int(codebook_size), 0
+        self.redundancy = None
+        if redundancy is not None:
+            self.redundancy = bitstream._check_red(redundancy, self.n_q, "CodePacketizer")
+            if not sum(self.redundancy):
+                raise ValueError("CodePacketizer: redundancy without a quantizer (pass None for plain packets)")
+        self._red_prev = None                    # (k, per-stream redundant payload bytes) of the previous call
 
     def header(self, timbre=None):
         from . import bitstream
@@ -1142,16 +1228,38 @@ class CodePacketizer:
         return [bitstream.write(head, tim[b].tobytes(), b"") for b in range(tim.shape[0])]
 
     def packet(self, codes):
-        from . import bitstream
         codes = list(codes) + [None] * (3 - len(codes))
         got = tuple(0 if c is None else int(c.shape[1]) for c in codes)
         if got != self.n_q:
             raise ValueError(f"codes with {got} rows, the packetizer was built for n_q = {self.n_q}")
         k = next(c for c in codes if c is not None).shape[-1]
-        rows = ops.pack_codes(codes, bits=self.bits).cpu().numpy()
+        if self.redundancy is None:
+            return self._emit(k, ops.pack_codes(codes, bits=self.bits).cpu().numpy())
+        # primary rows and this push's redundant layer (its leading quantizers: strided views of the same codes) side by side
+        # in one device buffer, one copy to the host
+        red = [c[:, :n] if n else None for c, n in zip(codes, self.redundancy)]
+        rb = ops.codes_row_bytes(k, sum(self.n_q), self.bits)
+        rb_red = ops.codes_row_bytes(k, sum(self.redundancy), self.bits)
+        dev = next(c for c in codes if c is not None).device
+        buf = torch.empty(next(c for c in codes if c is not None).shape[0], rb + rb_red, dtype=torch.uint8, device=dev)
+        ops.pack_codes(codes, bits=self.bits, out=buf[:, :rb])
+        ops.pack_codes(red, bits=self.bits, out=buf[:, rb:])
+        rows = buf.cpu().numpy()
+        return self._emit(k, rows[:, :rb], rows[:, rb:])
+
+    def _emit(self, k, rows, red_rows=None):
+        """Host part of packet(): the packed rows of this push (uint8 (B, >= payload bytes) arrays; red_rows: its redundant
+        layer, kept for the next call) -> one packet per stream."""
+        from . import bitstream
         n = bitstream.payload_bytes(k, sum(self.n_q), self.bits)
         seq, self.seq = self.seq, (self.seq + 1) & 0xFFFF
-        return [bitstream.write_packet(seq, k, rows[b, :n].tobytes()) for b in range(rows.shape[0])]
+        if self.redundancy is None:
+            return [bitstream.write_packet(seq, k, rows[b, :n].tobytes()) for b in range(rows.shape[0])]
+        k_prev, prev = self._red_prev if self._red_prev is not None else (0, [b""] * rows.shape[0])
+        n_red = bitstream.payload_bytes(k, sum(self.redundancy), self.bits)
+        self._red_prev = (k, [red_rows[b, :n_red].tobytes() for b in range(rows.shape[0])])
+        return [bitstream.write_packet_fec(seq, k, rows[b, :n].tobytes(), k_prev, self.redundancy, prev[b])
+                for b in range(rows.shape[0])]
 
 
 class CodeDepacketizer:
@@ -1193,6 +1301,180 @@ class CodeDepacketizer:
             raise ValueError("a packet without frames")
         rows = np.stack([np.frombuffer(p, dtype=np.uint8) for p in payloads])
         return ops.unpack_codes(ops.h2d(torch.from_numpy(rows), self.device), self.n_q, k, bits=self.bits)
+
+
+class StreamingReceiver:
+    """Receiver that keeps playing through packet loss: per tick one entry per stream, a packet or None, in; audio
+    out.  Streams are judged one by one -- a caller's lost packet does not touch its neighbours.
+
+        rx = StreamingReceiver(model, headers, delay=1)      # headers: CodePacketizer.header(timbre)
+        wave = rx.prime(packets)                             # call set-up is reliable: every stream's packet, >= rx.min_prime frames
+        wave = rx.tick(packets)                              # packets[b]: bytes or None -> (B, 1, 300 k)
+        wave = rx.flush()                                    # delay=1: the push still held
+
+    delay=0: a row whose packet arrived plays it (PRIMARY), any other row repeats its last frame (LOST).  delay=1: tick j plays
+    push j - 1, from its own packet (kept as bytes for one tick) if that arrived, else from the redundant layer in packet j
+    (REDUNDANT: the leading n_red quantizers, decoded at that lower rate), else LOST; the first tick after prime() returns None.
+    Concealment is fac_plc_select's state machine: a lost row repeats its last frame for `hold` frames at its gain, fades to
+    silence over `fade` frames and comes back within `recover` frames of the next good packet.  The defaults (25 ms, 75 ms, one
+    frame) follow the order of magnitude of G.711 Appendix I; they were not tuned by listening.
+
+    k, the frames of a tick, comes from any readable packet of the push being played (delay=1: or from the next packet's
+    n_red_frames); when no stream has one, pass k= (ValueError otherwise).  Per tick: one host-to-device copy (status words and
+    both payload rows in one buffer), ops.unpack_codes once (twice when a row is REDUNDANT), fac_plc_select, the LayeredDecoder
+    hop (a graph replay), fac_plc_gain in place -- no device-to-host copy and no synchronisation; `stats` comes from the host's
+    parsing: per stream received, corrupt, misordered (packets), recovered, concealed (frames).  `last_status` is the status
+    list of the last tick.  With graphs the returned wave is a static buffer, valid until the next call."""
+
+    def __init__(self, model, header_blobs, delay=0, hold=2, fade=6, recover=1, use_graphs=True, max_frames=16, device="cuda"):
+        from . import bitstream
+        from . import _lib
+        if delay not in (0, 1):
+            raise ValueError(f"delay = {delay}: 0 (play at once) or 1 (wait one push for the redundant layer); no deeper reorder buffer")
+        if hold < 0 or fade < 1 or recover < 1:
+            raise ValueError(f"hold >= 0, fade >= 1, recover >= 1 (got {hold}, {fade}, {recover})")
+        if not 1 <= max_frames <= _lib.PLC_MAX_FRAMES:
+            raise ValueError(f"max_frames = {max_frames} (1 .. {_lib.PLC_MAX_FRAMES})")
+        head = CodeDepacketizer(header_blobs, device=device)
+        self.n_q, self.bits, self.B, self.device = tuple(head.n_q), head.bits, head.B, head.device
+        self.delay, self.policy = delay, (int(hold), int(fade), int(recover))
+        self.reader = bitstream.LossyPacketReader(self.B, self.n_q, self.bits)
+        self.dec = LayeredDecoder(model, head.timbre, use_graphs=use_graphs, max_frames=max_frames)
+        self.min_prime, self.max_frames = self.dec.min_prime, int(max_frames)
+        self.state = ops.PlcState(self.B, self.n_q, self.device)
+        self.n_red = (0, 0, 0)
+        self._red = None
+        self._ramp = {}
+        self._held = None
+        self.recovered, self.concealed = [0] * self.B, [0] * self.B
+        self.last_status = None
+
+    @property
+    def stats(self):
+        rd = self.reader
+        return [dict(received=rd.received[b], recovered=self.recovered[b], concealed=self.concealed[b], corrupt=rd.corrupt[b],
+                     misordered=rd.misordered[b]) for b in range(self.B)]
+
+    def prime(self, packets):
+        if self.dec._n_q is not None:
+            raise RuntimeError("prime() must be the first call")
+        packets = list(packets)
+        if len(packets) != self.B or any(p is None for p in packets):
+            raise ValueError(f"prime() needs one packet per stream ({self.B}); call set-up is reliable")
+        seq0 = self.reader.expected
+        parsed = self.reader.feed(packets)
+        if any(p is None for p in parsed):
+            raise ValueError(f"prime(): the packets of streams {[b for b, p in enumerate(parsed) if p is None]} are corrupt or not seq {seq0}")
+        k = parsed[0].n_frames
+        if any(p.n_frames != k for p in parsed):
+            raise ValueError(f"prime(): the streams' packets disagree on n_frames: {[p.n_frames for p in parsed]}")
+        if k < self.min_prime:
+            raise ValueError(f"prime() needs at least {self.min_prime} frames, got {k}")
+        self.n_red = parsed[0].n_red
+        if sum(self.n_red):
+            self._red = [torch.zeros(self.B, max(n, 1), self.max_frames, dtype=torch.int64, device=self.device)[:, :n] for n in self.n_red]
+        status = [0] * self.B
+        buf, n1, _ = self._stage(status, [p.payload for p in parsed], None, k)
+        wave = self.dec.prime(ops.unpack_codes(buf[1], self.n_q, k, bits=self.bits))
+        dst, n_use = self.dec.buffers(k)
+        ops.plc_select(dst, None, buf[0], self.state, dst, n_use, self._ramp_buf(k), (0, 0, 0), *self.policy)
+        self.last_status = status
+        return wave
+
+    def _ramp_buf(self, k):
+        if k not in self._ramp:
+            self._ramp[k] = torch.empty(self.B, k + 1, dtype=torch.float32, device=self.device)
+        return self._ramp[k]
+
+    def _stage(self, status, prim, red, k):
+        """One host buffer [B status words | B rows of (primary payload | redundant payload)], one copy to the device ->
+        ((status (B) int32, rows (B, n1 + n2) uint8) device views, n1, n2)."""
+        import numpy as np
+        from . import bitstream
+        n1 = bitstream.payload_bytes(k, sum(self.n_q), self.bits)
+        n2 = bitstream.payload_bytes(k, sum(self.n_red), self.bits) if red is not None else 0
+        host = np.zeros(4 * self.B + self.B * (n1 + n2), dtype=np.uint8)
+        host[:4 * self.B].view("<i4")[:] = status
+        rows = host[4 * self.B:].reshape(self.B, n1 + n2)
+        for b in range(self.B):
+            if prim[b] is not None:
+                rows[b, :n1] = np.frombuffer(prim[b], dtype=np.uint8)
+            if red is not None and red[b] is not None:
+                rows[b, n1:] = np.frombuffer(red[b], dtype=np.uint8)
+        dev = ops.h2d(torch.from_numpy(host), self.device)
+        return (dev[:4 * self.B].view(torch.int32), dev[4 * self.B:].view(self.B, n1 + n2)), n1, n2
+
+    def _play(self, prim, red, k):
+        """prim[b] / red[b]: the Packet a row is played from, or None.  A packet of another frame count than k is of no use."""
+        from . import _lib
+        status, p_rows, r_rows = [], [], []
+        for b in range(self.B):
+            p, r = prim[b], red[b] if red is not None else None
+            if p is not None and p.n_frames == k:
+                st = _lib.PLC_PRIMARY
+            elif r is not None and r.n_red_frames == k and r.n_red == self.n_red and sum(self.n_red):
+                st = _lib.PLC_REDUNDANT
+                self.recovered[b] += k
+            else:
+                st = _lib.PLC_LOST
+                self.concealed[b] += k
+            status.append(st)
+            p_rows.append(p.payload if st == _lib.PLC_PRIMARY else None)
+            r_rows.append(r.red_payload if st == _lib.PLC_REDUNDANT else None)
+        any_red = _lib.PLC_REDUNDANT in status
+        (st_dev, rows), n1, n2 = self._stage(status, p_rows, r_rows if any_red else None, k)
+        dst, n_use = self.dec.buffers(k)
+        ops.unpack_codes(rows[:, :n1] if n2 else rows, self.n_q, k, bits=self.bits, out=dst)
+        red_codes = None
+        if any_red:
+            red_codes = [c[:, :, :k] for c in self._red]
+            ops.unpack_codes(rows[:, n1:], self.n_red, k, bits=self.bits, out=red_codes)
+        ramp = self._ramp_buf(k)
+        ops.plc_select(dst, red_codes, st_dev, self.state, dst, n_use, ramp, self.n_red if any_red else (0, 0, 0), *self.policy)
+        wave = self.dec.push_buffers(k)
+        self.last_status = status
+        return ops.plc_gain(wave, ramp, out=wave)
+
+    def _frames(self, prim, red, k):
+        n = next((p.n_frames for p in prim if p is not None), None)
+        if n is None and red is not None:
+            n = next((r.n_red_frames for r in red if r is not None and r.n_red_frames), None)
+        if n is None:
+            n = k
+        if n is None:
+            raise ValueError("no stream has a readable packet for this push: pass k=, the frames to conceal")
+        if not 1 <= n <= self.max_frames:
+            raise ValueError(f"a push of {n} frames (1 .. max_frames = {self.max_frames})")
+        return int(n)
+
+    def tick(self, packets, k=None):
+        if self.dec._n_q is None:
+            raise RuntimeError("call prime() first")
+        rd = self.reader
+        snap = (rd.expected, list(rd.received), list(rd.corrupt), list(rd.misordered))
+        parsed = rd.feed(packets)
+        if self.delay == 0:
+            prim, red = parsed, None
+        else:
+            prim, red = self._held, parsed
+            if prim is None:
+                self._held = parsed
+                return None                               # the first tick after prime(): push 1 is held, nothing is due yet
+        try:
+            k = self._frames(prim, red, k)
+        except ValueError:                                # nothing was played: the tick did not happen
+            rd.expected, rd.received, rd.corrupt, rd.misordered = snap
+            raise
+        if self.delay:
+            self._held = parsed
+        return self._play(prim, red, k)
+
+    def flush(self, k=None):
+        """delay=1: plays the push still held (its rows PRIMARY or LOST) -> wave, or None when nothing is held."""
+        if self._held is None:
+            return None
+        held, self._held = self._held, None
+        return self._play(held, None, self._frames(held, None, k))
 
 
 # ------------------------------------------------------------------------------------ streams that join and leave (DESIGN.md 26)

@@ -1075,6 +1075,81 @@ int fac_stoi_select(const fac_stoi_desc* d, fac_stream_t stream);
 int fac_stoi_bands(const fac_stoi_desc* d, fac_stream_t stream);
 int fac_stoi_score(const fac_stoi_desc* d, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Surviving packet loss (csrc/vq_decode.hip, csrc/plc.hip).  This comment is the normative definition.
+ *
+ * fac_vq_decode_masked: fac_vq_decode with quantizer counts per row and frame.  n_use[b*n_use_bs + t*n_use_ts + r] (int32 on
+ * the device) is the number of LEADING quantizers of RVQ r that contribute to frame (b, t), clamped to [0, base.n_q[r]].
+ *   RULE: for every (b, t), outs[b, :, t] and the optional z[r][b, :, t] equal, bit for bit, what fac_vq_decode gives for
+ *   that frame when called with n_q = n_use[b, t, :] (and the first n_q[r] code rows and weight sets of each RVQ).
+ * The per-RVQ chain is 0 + z_q_0 + z_q_1 + ..., then (z_p + z_c) + z_r, then the LayerNorm; a skipped quantizer's add is not
+ * executed (it does not add a zero).  Codes of skipped quantizers are ignored: they may hold anything (they are still loaded,
+ * under the clamp of fac_vq_decode, so they must be addressable).  n_use == NULL is fac_vq_decode.  Same layout as
+ * fac_vq_decode: one workgroup per (row, tile of <= 16 frames); the tile's counts are read once into LDS and the predicate is
+ * per (quantizer, frame), uniform over the channels.  Refused before any launch: what fac_vq_decode refuses, and a non-NULL
+ * n_use whose strides cannot address (B, T, 3): n_use_bs <= 0 with B > 1, or n_use_ts <= 0 with T > 1.
+ *
+ * fac_plc_select: per-row substitution of one push of k <= FAC_PLC_MAX_FRAMES frames, from device-resident state
+ *   last_codes (B, Q) int64   the codes last played, quantizers in RVQ order, Q = n_q[0] + n_q[1] + n_q[2]
+ *   last_n (B, 3) int32       the quantizer counts they were played with
+ *   g (B) fp32                the gain at the end of the last emitted sample (initially 1)
+ *   run (B) int32             concealed frames in a row (initially 0)
+ * and status (B) int32 on the device: 0 PRIMARY, 1 REDUNDANT, 2 LOST; any other value counts as LOST, and so does REDUNDANT
+ * when there is no redundant layer (n_red all 0).  Per row b, for every frame f < k:
+ *   PRIMARY    dst = prim;  n_use[b, f, :] = n_q;  then last_codes = the codes of frame k - 1, last_n = n_q.
+ *   REDUNDANT  quantizer i of RVQ r: dst = red when i < n_red[r], else 0 (which the mask ignores);  n_use[b, f, :] = n_red;
+ *              then last_codes of the quantizers inside n_red = their codes of frame k - 1 (the others keep theirs), last_n = n_red.
+ *   LOST       dst = last_codes for every frame;  n_use[b, f, :] = last_n;  last_codes and last_n unchanged.
+ * Gain, fp32, round-to-nearest, in exactly this order:  ramp[b, 0] = g;  per frame f = 0 .. k - 1
+ *   LOST       run += 1;  target = run <= hold ? g : max(0, g - 1.0f / (float)fade)
+ *   otherwise  run = 0;   target = min(1, g + 1.0f / (float)recover)
+ *   ramp[b, f + 1] = g = target.
+ * dst may be the prim buffers themselves.  One thread per (row, quantizer) walks the k frames, one thread per row does the
+ * counts and the gain: every word is written by exactly one thread, plain vector stores, no atomics, nothing read that
+ * another thread of the launch writes.  n_use is (B, k, 3) with strides n_use_bs / n_use_ts, ramp is dense (B, k + 1).
+ * Refused before any launch: a NULL descriptor, status or state pointer, n_use or ramp; B < 1; k outside
+ * 1 .. FAC_PLC_MAX_FRAMES; Q outside 1 .. FAC_VQ_DECODE_MAX_Q or a negative count; n_red[r] > n_q[r]; a NULL prim or dst with
+ * n_q[r] > 0; a NULL red with n_red[r] > 0; hold < 0, fade < 1, recover < 1; n_use strides that cannot address (B, k, 3).
+ *
+ * fac_plc_gain: y[b, f * frame + n] = x[b, f * frame + n] * gain,  gain = ramp[b, f] + (ramp[b, f + 1] - ramp[b, f]) * t,
+ * t = (float)(n + 1) / (float)frame (frame = 300 for the shipped model), every operation a separate fp32 round-to-nearest
+ * (no fused multiply-add).  Stateless, one thread per sample, y may be x.  A row whose ramp is 1 everywhere has gain == 1.0f
+ * exactly: y is x bit for bit.  x and y are B rows of k * frame samples with pitches x_bs, y_bs.  Refused: NULL pointers,
+ * B, k or frame < 1, a pitch below k * frame, B * k * frame >= 2^31.
+ * ---------------------------------------------------------------------------------------- */
+#define FAC_PLC_MAX_FRAMES 16
+#define FAC_PLC_PRIMARY 0
+#define FAC_PLC_REDUNDANT 1
+#define FAC_PLC_LOST 2
+typedef struct fac_vq_decode_masked_desc {
+  fac_vq_decode_desc base;
+  const int32_t* n_use;     /* (B, T, 3) counts, or NULL (== fac_vq_decode) */
+  int64_t n_use_bs, n_use_ts;
+} fac_vq_decode_masked_desc;
+int fac_vq_decode_masked(const fac_vq_decode_masked_desc* d, fac_stream_t stream);
+
+typedef struct fac_plc_select_desc {
+  const int64_t* prim[3];   /* primary codes (B, n_q[r], k): prim[r][b*prim_bs[r] + i*prim_qs[r] + f] */
+  int64_t prim_bs[3], prim_qs[3];
+  const int64_t* red[3];    /* redundant codes (B, n_red[r], k), NULL when n_red[r] == 0 */
+  int64_t red_bs[3], red_qs[3];
+  int64_t* dst[3];          /* written: (B, n_q[r], k), may be prim */
+  int64_t dst_bs[3], dst_qs[3];
+  int32_t n_q[3], n_red[3];
+  const int32_t* status;    /* (B) */
+  int64_t* last_codes;      /* (B, Q) state */
+  int32_t* last_n;          /* (B, 3) state */
+  float* g;                 /* (B) state */
+  int32_t* run;             /* (B) state */
+  int32_t* n_use;           /* written: (B, k, 3) */
+  int64_t n_use_bs, n_use_ts;
+  float* ramp;              /* written: (B, k + 1) dense */
+  int32_t B, k, hold, fade, recover, reserved;
+} fac_plc_select_desc;
+int fac_plc_select(const fac_plc_select_desc* d, fac_stream_t stream);
+int fac_plc_gain(const float* x, int64_t x_bs, float* y, int64_t y_bs, const float* ramp, int B, int k, int frame,
+                 fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
