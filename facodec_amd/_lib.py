@@ -33,7 +33,7 @@ class ConvDesc(C.Structure):
         ("x_p8", _p), ("x_p8_plane_bytes", _i64), ("y2_p8", _p), ("y2_p8_plane_bytes", _i64),
         ("pw_split", C.c_int32), ("split_rows", C.c_int32),
         ("gate_cond", _p), ("gate_cond_bs", _i64),
-        ("keep_tile160", C.c_int32),
+        ("keep_tile160", C.c_int32), ("gsplit_p8_cols", C.c_int32),
     ]
 
 
@@ -201,6 +201,7 @@ SIGNATURES = {
     "fac_pack_convtr_w": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "fac_conv1d_fwd": (_i, [C.POINTER(ConvDesc), _p]),
     "fac_conv1d_variant": (_i, [C.POINTER(ConvDesc), C.c_char_p, _i]),
+    "fac_gsplit_p8_tile_cols": (_i, [_i64, _i64, _i64, _i]),
     "fac_snake_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "fac_lstm_to_time_major": (_i, [_p, _p, _i, _i, _i, _p]),
     "fac_lstm_from_time_major": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -138,6 +138,8 @@ static int conv_plan(const fac_conv_desc* d, ConvArgs& a, ConvKernel& k) {
   if (d->w_k1) { k = CK_FUSED_RU; return FAC_OK; }
   a.gflat = 0;
   a.grt = 0;
+  a.gs_ncb = 0;
+  a.gs_cols_req = 0;
   // few-output-channel 9- / 3-tap convs (two-level taps included) with split weights of fac_pack_conv_w_split2
   if (d->w_split && (a.KV == 9 || a.KV == 3) && d->C_out <= 32 && conv_bsplit2_ok(a)) {
     a.w = reinterpret_cast<const float*>(d->w_split);
@@ -153,6 +155,12 @@ static int conv_plan(const fac_conv_desc* d, ConvArgs& a, ConvKernel& k) {
       !conv_skinny_ok(a, d->ws, d->ws_bytes)) {
     a.w = reinterpret_cast<const float*>(d->w_split);
     k = CK_GSPLIT;
+    if (d->x_p8) {
+      FAC_REQUIRE(d->gsplit_p8_cols == 0 || d->gsplit_p8_cols == -1 || d->gsplit_p8_cols == 128 || d->gsplit_p8_cols == 256,
+                  "conv1d: gsplit_p8_cols must be 0, -1, 128 or 256 (got %d)", d->gsplit_p8_cols);
+      a.gs_cols_req = d->gsplit_p8_cols;
+      a.gs_ncb = conv_gsplit_p8_ncb(a);     // > 0: the form that reads its input fragments straight from the P8 planes
+    }
     return FAC_OK;
   }
   if (a.rp > 1) {
@@ -215,7 +223,7 @@ extern "C" int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream) {
     case CK_CIN1: return conv_dispatch_cin1(a, s);
     case CK_THIN: return conv_dispatch_thin(a, d->ws, s);
     case CK_PW: return conv_dispatch_pw(a, s);
-    case CK_GSPLIT: return conv_dispatch_gsplit(a, s);
+    case CK_GSPLIT: return a.gs_ncb ? conv_dispatch_gsplit_p8(a, s) : conv_dispatch_gsplit(a, s);
     case CK_BSPLIT2: return conv_dispatch_bsplit2(a, s);
     case CK_PWS: return conv_dispatch_pws(a, s);
     case CK_PWT: return conv_dispatch_pwt(a, s);
@@ -254,7 +262,8 @@ extern "C" int fac_conv1d_variant(const fac_conv_desc* d, char* name, int name_l
     case CK_THIN: snprintf(name, name_len, "conv1d_thin_kernel (VALU, C_out<=8, split channels)"); break;
     case CK_PW: snprintf(name, name_len, "conv1d_pw_kernel (k=1 streaming, W in LDS)"); break;
     case CK_GSPLIT:
-      snprintf(name, name_len, "conv1d_gemm_split_kernel<%d> 128x128 (bf16x3 split GEMM, fp32-grade)", a.stride > 1 ? 2 : a.K);
+      if (a.gs_ncb) snprintf(name, name_len, "conv1d_gemm_split_kernel<%d> 64x%d (bf16x3 split GEMM, fp32-grade, P8 fragments)", a.stride > 1 ? 2 : a.K, 64 * a.gs_ncb);
+      else snprintf(name, name_len, "conv1d_gemm_split_kernel<%d> 128x128 (bf16x3 split GEMM, fp32-grade)", a.stride > 1 ? 2 : a.K);
       break;
     case CK_BSPLIT2: snprintf(name, name_len, "conv1d_bsplit2_kernel<%d,%d> 32x512 (bf16x3 split, fp32-grade)", a.KV, a.stride); break;
     case CK_PWS: snprintf(name, name_len, "conv1d_pws_kernel (k=1 streaming, W planes in LDS, bf16x3 split, fp32-grade)"); break;

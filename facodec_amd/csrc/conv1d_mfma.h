@@ -72,6 +72,8 @@ struct ConvArgs {
                // ConvTranspose1d, fac_conv_desc.row_phases); the all-waves epilogue interleaves them into contiguous runs
   const float* gate_cond;      // FAC_ACT_GATE: per-clip conditioning row (2 * (C_out / 2) values) added before the gate, or NULL
   long long gate_cond_bs;      // floats between the rows of two clips
+  int gs_ncb;  // conv1d_gemm_split_p8.hip: 64-column blocks per workgroup tile (4 or 2); 0 = the 128 x 128 form of conv1d_gemm_split.hip
+  int gs_cols_req;             // fac_conv_desc.gsplit_p8_cols
 };
 
 // largest tap offset of a (possibly two-level) conv
@@ -706,6 +708,10 @@ bool conv_bsplit2_ok(const ConvArgs& a);
 int conv_dispatch_bsplit2(ConvArgs& a, hipStream_t s);
 bool conv_gsplit_ok(const ConvArgs& a);
 int conv_dispatch_gsplit(ConvArgs& a, hipStream_t s);
+// the form of the split GEMM for P8 inputs (conv1d_gemm_split_p8.hip): 64 x (64 * NCB) tiles, input fragments straight from the planes.
+// conv_gsplit_p8_ncb: the NCB (4 or 2) a launch the split GEMM takes runs with on that form, 0 = it stays on the 128 x 128 form.
+int conv_gsplit_p8_ncb(const ConvArgs& a);
+int conv_dispatch_gsplit_p8(ConvArgs& a, hipStream_t s);
 bool conv_bsplit_ok(const ConvArgs& a);
 bool conv_bsplit_p8_ok(const ConvArgs& a);   // ... and the launch takes a P8 input (wide shape: C_in >= 64, C_in % 16 == 0)
 int conv_dispatch_bsplit(ConvArgs& a, hipStream_t s);

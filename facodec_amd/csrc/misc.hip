@@ -646,7 +646,7 @@ __global__ __launch_bounds__(256) void logdiff_rms_bwd_kernel(const float* __res
 
 using namespace fac;
 
-extern "C" int fac_version(void) { return 5; }   // 3: fac_conv_desc.row_phases, fac_adamw_step_masked, fac_pack_convtr_w_rows; 4: fac_conv_desc.gate_cond; 5: .keep_tile160
+extern "C" int fac_version(void) { return 6; }   // 3: fac_conv_desc.row_phases, fac_adamw_step_masked, fac_pack_convtr_w_rows; 4: fac_conv_desc.gate_cond; 5: .keep_tile160; 6: .gsplit_p8_cols
 extern "C" const char* fac_last_error(void) { return fac::g_err; }
 
 #define EW_LAUNCH(kern, n, ...)                                                         \

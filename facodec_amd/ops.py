@@ -577,6 +577,7 @@ def conv_desc(B, c_in, t_in, c_out, k, stride=1, dilation=1, pad_left=None, pad_
     d.K1, d.dilation2, d.split_rows = k1, dilation2, split_rows
     d.pw_split = 1 if (BF16_SPLIT and PW_SPLIT and (k == 1 or (PW_TAPS and k == 4 and stride == 2))) else 0
     d.keep_tile160 = 0 if K1_COLUMN_TILES else 1
+    d.gsplit_p8_cols = GSPLIT_P8_COLS
     return d
 
 
@@ -662,6 +663,7 @@ def convtr_desc(B, c_in, t_in, c_out, stride, c_out_pad, causal=True, has_histor
     d.n_phase, d.y_tstride, d.act, d.w_batched, d.w_bs = stride, stride, ACT_NONE, 0, 0
     # non-causal: trim ceil(s/2) on the left, floor(s/2) on the right (dac/model/encodec.py:265-269)
     d.phase_shift = 0 if causal else stride - stride // 2
+    d.gsplit_p8_cols = GSPLIT_P8_COLS
     if rows or split:
         if not causal or has_history:
             raise _lib.FacodecHipError("the all-phases ConvTranspose1d launch is causal and offline only")
@@ -723,6 +725,11 @@ PW_TAPS = True
 # k = 1 fp32 launches of 129 .. 160 columns per clip whose 128 x 160 tiles would be fewer than 256 workgroups (the style path's
 # 1025 -> 80, 80 -> 512, 20 -> 256 at 32 clips) on five 128 x 32 tiles per clip (conv1d_api.hip: select_variant); False: the wide tile
 K1_COLUMN_TILES = True
+# Split GEMM launches with a P8 input on the form that reads its input fragments straight from the planes, 64 x 256 / 64 x 128 tiles,
+# two workgroups per CU (conv1d_gemm_split_p8.hip; which shapes: conv_gsplit_p8_ncb there).  fac_conv_desc.gsplit_p8_cols: 0 = the
+# library chooses; -1 = every such launch stays on the 128 x 128 form, what the tree launched before that form existed; 256 / 128 =
+# that tile on every such launch (tests) -- the same bits whichever.
+GSPLIT_P8_COLS = 0
 
 
 def pack_conv_for(layout, v, g, stride=1, k1=0, scale=None):

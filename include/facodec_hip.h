@@ -168,7 +168,8 @@ typedef struct fac_conv_desc {
    * staging waves and the MFMAs of the same SIMD do not overlap.
    *   x_p8  : the INPUT in P8 (then `x` may be NULL); taken by the K = 3 / 5 / 7 split kernel (C_in % 16 == 0) and by the 1- / 2-tap
    *           split GEMM kernel (plain, strided and all-phases transposed launches; C_in % 8 == 0), where both operands then move by
-   *           LDS-DMA.
+   *           LDS-DMA -- or, on the shapes where that measured faster, the input fragments go straight from the planes into registers
+   *           (see gsplit_p8_cols below; the same bits).
    *   y2_p8 : reserved -- the pre-activated second output snake(y, alpha_y2) in P8 instead of (or beside) fp32 `y2`.  No kernel
    *           writes it: fac_conv1d_fwd / fac_conv1d_variant refuse every descriptor that sets it (FAC_ERR_ARG, "P8 operands given
    *           but the launch does not run on a kernel that takes them"; without alpha_y2, "y2_p8 needs alpha_y2").  Leave it NULL. */
@@ -197,9 +198,19 @@ typedef struct fac_conv_desc {
    * five 128 x 32 tiles per clip because B * ceil(C_out / 128) wide tiles are fewer than 256 workgroups.  For A/B runs and for the
    * test that holds the two forms against each other; ignored by every other launch. */
   int32_t keep_tile160;
+  /* Optional (0 = the library's choice): the form of the split GEMM kernel for a launch with a P8 input.  -1 keeps the 128 x 128
+   * form (conv1d_gemm_split.hip) for a shape that would otherwise run on the form that reads its input fragments straight from the
+   * P8 planes (64-row tiles, two workgroups per CU: conv1d_gemm_split_p8.hip); 256 / 128 take that form with so many columns per
+   * tile, whatever the library would choose.  Every form gives the same bits.  For A/B runs and for the tests that hold the forms
+   * against each other; any other value is an error, and launches without a P8 input ignore the field. */
+  int32_t gsplit_p8_cols;
 } fac_conv_desc;
 
 int fac_conv1d_fwd(const fac_conv_desc* d, fac_stream_t stream);
+/* Columns per tile (256 or 128) the P8-fragment form of the split GEMM picks for a launch of `rows` output rows over `cols` columns
+ * in each of `ranges` column ranges (clips; 1 when flattened) on `slots` co-resident workgroups (two per CU): the cheaper of the two
+ * by rounds of `slots` workgroups x columns per tile, ties to 256.  Host arithmetic only; 0 for a non-positive argument. */
+int fac_gsplit_p8_tile_cols(int64_t rows, int64_t cols, int64_t ranges, int slots);
 /* x (B, C, T) fp32 [-> snake(x, alpha) when alpha != NULL] -> the P8 planes described at fac_conv_desc.x_p8
  * (out: 3 planes of (B * (C / 8) * T + 1) * 16 bytes one after the other, the zero unit included).  C % 8 == 0. */
 int fac_to_p8(const float* x, const float* alpha, void* out, int B, int C, int T, fac_stream_t stream);
