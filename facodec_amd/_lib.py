@@ -80,6 +80,34 @@ class PlcSelectDesc(C.Structure):
     ]
 
 
+VAD_MAX_FRAME, VAD_MAX_WINDOW = 4096, 2048          # FAC_VAD_MAX_FRAME, FAC_VAD_MAX_WINDOW
+SID_PASS, SID_STORE, SID_FILL = 0, 1, 2
+
+
+class VadEnergyDesc(C.Structure):
+    _fields_ = [
+        ("carry_in", _p), ("carry_out", _p), ("x", _p), ("lens", _p), ("e", _p),
+        ("x_bs", _i64), ("e_bs", _i64), ("f0", _i64),
+        ("B", C.c_int32), ("k", C.c_int32), ("frame", C.c_int32), ("carry_n", C.c_int32), ("is_final", C.c_int32), ("R", C.c_int32),
+    ]
+
+
+class VadDecideDesc(C.Structure):
+    _fields_ = [
+        ("e", _p), ("lens", _p), ("flags", _p), ("ring", _p),
+        ("e_bs", _i64), ("flags_bs", _i64), ("ring_bs", _i64), ("f0", _i64),
+        ("margin", C.c_double), ("thr_abs", C.c_double),
+        ("B", C.c_int32), ("n_new", C.c_int32), ("R", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("frame", C.c_int32),
+    ]
+
+
+class SidApplyDesc(C.Structure):
+    _fields_ = [
+        ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3), ("n_q", C.c_int32 * 3), ("B", C.c_int32),
+        ("mode", _p), ("sid_codes", _p), ("k", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class CodesPackDesc(C.Structure):
     _fields_ = [
         ("codes", _p * 3), ("codes_bs", _i64 * 3), ("codes_qs", _i64 * 3), ("n_q", C.c_int32 * 3),
@@ -254,6 +282,10 @@ SIGNATURES = {
     "fac_vq_decode_masked": (_i, [C.POINTER(VqDecodeMaskedDesc), _p]),
     "fac_plc_select": (_i, [C.POINTER(PlcSelectDesc), _p]),
     "fac_plc_gain": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _p]),
+    "fac_vad_energy": (_i, [C.POINTER(VadEnergyDesc), _p]),
+    "fac_vad_decide": (_i, [C.POINTER(VadDecideDesc), _p]),
+    "fac_vad_take": (_i, [_p, _i64, _i, _i64, _i, _p, _i64, _i, _p]),
+    "fac_sid_apply": (_i, [C.POINTER(SidApplyDesc), _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),
     "fac_codes_unpack": (_i, [C.POINTER(CodesUnpackDesc), _p]),
     "fac_codes_row_bytes": (_i64, [_i, _i, _i]),

@@ -29,6 +29,10 @@ Packet with in-band redundancy, per stream:
     ..  I   CRC-32 of every preceding byte
 
 LossyPacketReader reads both kinds per stream and never raises for a loss; what is played for one is StreamingReceiver's business.
+
+SID packet: "silence follows".  It is the packet that would have been sent with the second magic byte in lower
+case -- b"Fp" for the b"FP" layout, b"Fq" for b"FQ" -- and nothing else changed (the CRC covers the body, so it differs too).
+read_packet / read_packet_fec refuse it like any unknown magic; LossyPacketReader(dtx=True) reads all four.
 """
 import struct
 import zlib
@@ -88,13 +92,20 @@ def payload_bytes(F, Q, bits):
     return (int(F) * int(Q) * int(bits) + 7) // 8
 
 
-def bitrate(n_q, bits, frame_rate=80, redundancy=None):
+def bitrate(n_q, bits, frame_rate=80, redundancy=None, dtx_silence=None, sid_every=8):
     """Payload bits per second for quantizer counts n_q = (n_p, n_c, n_r) (or their sum): Q * bits * frame_rate.  redundancy =
-    (rp, rc, rr) (or their sum) adds the share of the in-band redundant copy: (Q + R) * bits * frame_rate."""
+    (rp, rc, rr) (or their sum) adds the share of the in-band redundant copy: (Q + R) * bits * frame_rate.  dtx_silence = the
+    fraction of pushes without an active frame under discontinuous transmission: of those only one in sid_every
+    is sent, so the rate (then a float) is that times (1 - dtx_silence) + dtx_silence / sid_every."""
     Q = sum(n_q) if isinstance(n_q, (tuple, list)) else int(n_q)
     if redundancy is not None:
         Q += sum(redundancy) if isinstance(redundancy, (tuple, list)) else int(redundancy)
-    return Q * bits * frame_rate
+    rate = Q * bits * frame_rate
+    if dtx_silence is None:
+        return rate
+    if not 0.0 <= dtx_silence <= 1.0 or int(sid_every) < 1:
+        raise ValueError(f"bitrate: dtx_silence = {dtx_silence} (0 .. 1), sid_every = {sid_every} (>= 1)")
+    return rate * ((1.0 - dtx_silence) + dtx_silence / int(sid_every))
 
 
 def _check_layout(bits, n_q, what):
@@ -173,23 +184,26 @@ def read(blob):
 
 
 # ------------------------------------------------------------------------------------ packets of the streaming pair
-def write_packet(seq, n_frames, payload):
-    """One push of one stream: b"FP", seq (taken modulo 65536), n_frames, payload, CRC-32."""
+PACKET_MAGIC_SID = b"Fp"                      # a SID packet: "silence follows" 
+
+
+def write_packet(seq, n_frames, payload, sid=False):
+    """One push of one stream: b"FP" (sid: b"Fp"), seq (taken modulo 65536), n_frames, payload, CRC-32."""
     if not 0 <= n_frames <= 0xFFFF:
         raise ValueError(f"packet: n_frames = {n_frames} does not fit 16 bits")
-    body = _PHEAD.pack(PACKET_MAGIC, seq & 0xFFFF, n_frames) + bytes(payload)
+    body = _PHEAD.pack(PACKET_MAGIC_SID if sid else PACKET_MAGIC, seq & 0xFFFF, n_frames) + bytes(payload)
     return body + struct.pack("<I", zlib.crc32(body))
 
 
-def read_packet(blob, Q, bits):
-    """-> (seq, n_frames, payload bytes).  ValueError for a short packet, a wrong magic, a CRC failure, or a payload whose
-    length is not payload_bytes(n_frames, Q, bits)."""
+def read_packet(blob, Q, bits, _magic=PACKET_MAGIC):
+    """-> (seq, n_frames, payload bytes).  ValueError for a short packet, a wrong magic (a SID packet's included), a CRC failure,
+    or a payload whose length is not payload_bytes(n_frames, Q, bits)."""
     blob = bytes(blob)
     if len(blob) < PACKET_OVERHEAD:
         raise ValueError(f"packet: truncated ({len(blob)} bytes)")
     magic, seq, n_frames = _PHEAD.unpack_from(blob)
-    if magic != PACKET_MAGIC:
-        raise ValueError(f"packet: wrong magic {magic!r} (expected {PACKET_MAGIC!r})")
+    if magic != _magic:
+        raise ValueError(f"packet: wrong magic {magic!r} (expected {_magic!r})")
     crc, = struct.unpack_from("<I", blob, len(blob) - 4)
     if zlib.crc32(blob[:-4]) != crc:
         raise ValueError("packet: CRC mismatch (corrupt packet)")
@@ -233,12 +247,14 @@ class PacketReader:
 
 # ------------------------------------------------------------------------------------ packets that survive a loss
 FEC_MAGIC = b"FQ"
+FEC_MAGIC_SID = b"Fq"
 _QHEAD = struct.Struct("<2sHHH3B")
 FEC_OVERHEAD = _QHEAD.size + 4               # 15 bytes around the two payloads
 assert _QHEAD.size == 11
 
-Packet = namedtuple("Packet", "seq n_frames payload n_red_frames n_red red_payload")
-Packet.__doc__ = """A parsed packet of either kind; an b"FP" packet has n_red_frames = 0, n_red = (0, 0, 0), red_payload = b""."""
+Packet = namedtuple("Packet", "seq n_frames payload n_red_frames n_red red_payload sid", defaults=(False,))
+Packet.__doc__ = """A parsed packet of either kind; an b"FP" packet has n_red_frames = 0, n_red = (0, 0, 0), red_payload = b"".
+sid: a SID packet (b"Fp" / b"Fq"), which only LossyPacketReader(dtx=True) reads."""
 
 
 def _check_red(n_red, n_q, what):
@@ -248,29 +264,29 @@ def _check_red(n_red, n_q, what):
     return n_red
 
 
-def write_packet_fec(seq, n_frames, payload, n_red_frames=0, n_red=(0, 0, 0), red_payload=b""):
-    """One push of one stream with the previous push's redundant layer: b"FQ", seq (modulo 65536), n_frames, n_red_frames, n_red,
-    primary payload, redundant payload, CRC-32.  The payload lengths are the caller's (read_packet_fec checks them against the
-    layout it is handed)."""
+def write_packet_fec(seq, n_frames, payload, n_red_frames=0, n_red=(0, 0, 0), red_payload=b"", sid=False):
+    """One push of one stream with the previous push's redundant layer: b"FQ" (sid: b"Fq"), seq (modulo 65536), n_frames,
+    n_red_frames, n_red, primary payload, redundant payload, CRC-32.  The payload lengths are the caller's (read_packet_fec
+    checks them against the layout it is handed)."""
     if not 0 <= n_frames <= 0xFFFF or not 0 <= n_red_frames <= 0xFFFF:
         raise ValueError(f"packet: n_frames = {n_frames} / n_red_frames = {n_red_frames} do not fit 16 bits")
     n_red = tuple(int(n) for n in n_red)
     if len(n_red) != 3 or any(not 0 <= n <= MAX_Q for n in n_red):
         raise ValueError(f"packet: redundant quantizer counts {n_red} (three counts, 0..{MAX_Q})")
-    body = _QHEAD.pack(FEC_MAGIC, seq & 0xFFFF, n_frames, n_red_frames, *n_red) + bytes(payload) + bytes(red_payload)
+    body = _QHEAD.pack(FEC_MAGIC_SID if sid else FEC_MAGIC, seq & 0xFFFF, n_frames, n_red_frames, *n_red) + bytes(payload) + bytes(red_payload)
     return body + struct.pack("<I", zlib.crc32(body))
 
 
-def read_packet_fec(blob, n_q, bits):
+def read_packet_fec(blob, n_q, bits, _magic=FEC_MAGIC):
     """-> Packet(seq, n_frames, payload, n_red_frames, n_red, red_payload) for the stream layout n_q = (n_p, n_c, n_r), bits.
-    ValueError for a short packet, a wrong magic, a CRC failure, n_red beyond n_q, redundant frames without redundant
+    ValueError for a short packet, a wrong magic (a SID packet's included), a CRC failure, n_red beyond n_q, redundant frames without redundant
     quantizers, or a length that is not 15 + payload_bytes(n_frames, Q, bits) + payload_bytes(n_red_frames, R, bits)."""
     blob = bytes(blob)
     if len(blob) < FEC_OVERHEAD:
         raise ValueError(f"packet: truncated ({len(blob)} bytes)")
     magic, seq, n_frames, n_red_frames, rp, rc, rr = _QHEAD.unpack_from(blob)
-    if magic != FEC_MAGIC:
-        raise ValueError(f"packet: wrong magic {magic!r} (expected {FEC_MAGIC!r})")
+    if magic != _magic:
+        raise ValueError(f"packet: wrong magic {magic!r} (expected {_magic!r})")
     crc, = struct.unpack_from("<I", blob, len(blob) - 4)
     if zlib.crc32(blob[:-4]) != crc:
         raise ValueError("packet: CRC mismatch (corrupt packet)")
@@ -281,7 +297,8 @@ def read_packet_fec(blob, n_q, bits):
     if len(blob) - FEC_OVERHEAD != n1 + n2:
         raise ValueError(f"packet: {len(blob) - FEC_OVERHEAD} payload bytes, {n_frames} frames x {sum(n_q)} x {bits} bits and "
                          f"{n_red_frames} redundant frames x {sum(n_red)} x {bits} bits need {n1} + {n2}")
-    return Packet(seq, n_frames, blob[_QHEAD.size:_QHEAD.size + n1], n_red_frames, n_red, blob[_QHEAD.size + n1:-4])
+    return Packet(seq, n_frames, blob[_QHEAD.size:_QHEAD.size + n1], n_red_frames, n_red, blob[_QHEAD.size + n1:-4],
+                  _magic == FEC_MAGIC_SID)
 
 
 class LossyPacketReader:
@@ -294,9 +311,11 @@ class LossyPacketReader:
     Every feed() is one push: the expected seq advances by one (modulo 65536) whatever arrived.  A packet that does not parse
     (truncation, magic, CRC, a length that disagrees with the layout) counts in corrupt[b], one with another seq than the expected
     in misordered[b], a good one in received[b]; the first two are treated as missing.  feed() never raises for a loss (only for
-    a list that has not one entry per stream)."""
+    a list that has not one entry per stream).  dtx=True: SID packets (b"Fp", b"Fq") parse too, as Packets with sid = True;
+    with dtx=False they count as corrupt, as any unknown magic does."""
 
-    def __init__(self, n_streams, n_q, bits, first_seq=0):
+    def __init__(self, n_streams, n_q, bits, first_seq=0, dtx=False):
+        self.dtx = bool(dtx)
         self.n_streams, self.n_q, self.bits = int(n_streams), tuple(int(n) for n in n_q), int(bits)
         _check_layout(self.bits, self.n_q, "LossyPacketReader")
         self.expected = first_seq & 0xFFFF
@@ -305,10 +324,11 @@ class LossyPacketReader:
     def parse(self, blob):
         """One packet of either kind -> Packet; ValueError as read_packet / read_packet_fec."""
         blob = bytes(blob)
-        if blob[:2] == FEC_MAGIC:
-            return read_packet_fec(blob, self.n_q, self.bits)
-        seq, n_frames, payload = read_packet(blob, sum(self.n_q), self.bits)
-        return Packet(seq, n_frames, payload, 0, (0, 0, 0), b"")
+        sid = self.dtx and blob[:2] in (PACKET_MAGIC_SID, FEC_MAGIC_SID)
+        if blob[:2] == (FEC_MAGIC_SID if sid else FEC_MAGIC):
+            return read_packet_fec(blob, self.n_q, self.bits, blob[:2])
+        seq, n_frames, payload = read_packet(blob, sum(self.n_q), self.bits, PACKET_MAGIC_SID if sid else PACKET_MAGIC)
+        return Packet(seq, n_frames, payload, 0, (0, 0, 0), b"", sid)
 
     def feed(self, packets):
         packets = list(packets)

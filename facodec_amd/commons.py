@@ -785,6 +785,66 @@ def loudness_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SA
     return out
 
 
+def active_segments(flags, frame, length):
+    """flags: one clip's 0 / 1 frame flags (host sequence) -> [(start_sample, end_sample)] of its runs of active frames, the last
+    end clipped to the clip's length.  Host only."""
+    segs, start = [], None
+    for f, a in enumerate(list(flags) + [0]):
+        if a and start is None:
+            start = f
+        elif not a and start is not None:
+            segs.append((start * frame, min(f * frame, int(length))))
+            start = None
+    return segs
+
+
+@torch.no_grad()
+def vad_clips(waves, max_batch_samples=MAX_BATCH_SAMPLES, **vad):
+    """Voice activity of clips of different lengths -> per clip, in the caller's order, dict(flags (F_i,) uint8 on
+    the host, F_i = ceil(T_i / frame); segments [(start_sample, end_sample)], the runs of active frames clipped to the clip).
+    The clips (T_i,) or (1, T_i), float32 on the GPU at the model's rate, go through plan_groups' zero-padded groups with their
+    lengths: one ops.vad call (two launches) and one device-to-host copy of the flags per group, the run lengths are computed
+    on the host; a clip gets what it gets alone.  **vad: ops.vad's frame, window, hangover, margin_db, floor_db -- whose
+    defaults were not tuned by listening."""
+    from . import ops
+    frame = ops.vad_params(**vad)[0]                                # ValueError: the parameters
+    waves = list(waves)
+    if not waves:
+        return []
+    _need_gpu(waves, "clips")
+    for w in waves:
+        if not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = [int(w.shape[-1]) for w in waves]
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), batch.device)
+        flags = ops.vad(batch, lens=lens, **vad)[0].cpu().numpy()
+        for j, i in enumerate(group):
+            fl = flags[j, :-(-lengths[i] // frame)].copy()
+            out[i] = dict(flags=fl, segments=active_segments(fl.tolist(), frame, lengths[i]))
+    return out
+
+
+@torch.no_grad()
+def trim_clips(waves, pad_frames=0, max_batch_samples=MAX_BATCH_SAMPLES, **vad):
+    """Every clip cut to its speech: the slice (a view) from its first to its last active frame, widened by pad_frames frames on
+    either side and kept within the clip; a clip without an active frame gives an empty tensor.  vad_clips does the work."""
+    from . import ops
+    frame = ops.vad_params(**vad)[0]
+    waves = list(waves)
+    out = []
+    for w, r in zip(waves, vad_clips(waves, max_batch_samples, **vad)):
+        if not r["segments"]:
+            out.append(w[..., :0])
+            continue
+        a = max(0, r["segments"][0][0] - int(pad_frames) * frame)
+        b = min(int(w.shape[-1]), r["segments"][-1][1] + int(pad_frames) * frame)
+        out.append(w[..., a:b])
+    return out
+
+
 SCORE_METRICS = ("si_sdr", "stoi", "estoi")
 
 

@@ -1180,6 +1180,110 @@ def plc_gain(wave, ramp, out=None, frame=300):
     return out
 
 
+# --------------------------------------------------------------------------------- voice activity
+def vad_params(frame=300, window=120, hangover=16, margin_db=6.0, floor_db=-70.0):
+    """-> (frame, W, H, margin, thr_abs) of fac_vad_decide: margin = 10 ** (margin_db / 10) (a linear power ratio above 1) and
+    thr_abs = frame * 10 ** (floor_db / 10) (a per-frame energy sum), both in Python floats.  The defaults -- 1.5 s of minimum
+    statistics, 200 ms of hangover, 6 dB over the noise floor, -70 dBFS absolute -- were not tuned by listening."""
+    frame, W, H = int(frame), int(window), int(hangover)
+    if not 1 <= frame <= _lib.VAD_MAX_FRAME:
+        raise ValueError(f"vad: frame = {frame} outside 1 .. {_lib.VAD_MAX_FRAME}")
+    if not 1 <= W <= _lib.VAD_MAX_WINDOW or not 0 <= H <= _lib.VAD_MAX_WINDOW:
+        raise ValueError(f"vad: window = {W} (1 .. {_lib.VAD_MAX_WINDOW}), hangover = {H} (0 .. {_lib.VAD_MAX_WINDOW})")
+    margin = 10.0 ** (float(margin_db) / 10.0)
+    if not margin > 1.0:
+        raise ValueError(f"vad: margin_db = {margin_db} (above 0 dB)")
+    return frame, W, H, margin, frame * 10.0 ** (float(floor_db) / 10.0)
+
+
+def vad_energy(x, e, frame, f0=0, R=None, lens=None, carry_in=None, carry_n=0, carry_out=None, final=True):
+    """fac_vad_energy: frame energies of x (B, k) float32 behind the carry into e (B, >= R) float64 (ring of R columns, first
+    frame at column f0 % R) -> the number of frames written."""
+    B, k = x.shape
+    R = e.shape[1] if R is None else int(R)
+    d = _lib.VadEnergyDesc()
+    d.carry_in = carry_in.data_ptr() if carry_in is not None else None
+    d.carry_out = carry_out.data_ptr() if carry_out is not None else None
+    d.x, d.lens, d.e = x.data_ptr(), (_lens(lens, B).data_ptr() if lens is not None else None), e.data_ptr()
+    d.x_bs, d.e_bs, d.f0 = (x.stride(0) if B > 1 else k), (e.stride(0) if B > 1 else e.shape[1]), int(f0)
+    d.B, d.k, d.frame, d.carry_n, d.is_final, d.R = B, k, int(frame), int(carry_n), 1 if final else 0, R
+    _lib.check(_lib.load().fac_vad_energy(C.byref(d), _stream()), "fac_vad_energy")
+    total = int(carry_n) + k
+    return total // frame + (1 if final and total % frame else 0)
+
+
+def vad_decide(e, f0, n_new, W, H, margin, thr_abs, frame, R=None, lens=None, flags=None, ring=None):
+    """fac_vad_decide over the energy ring e (B, >= R) float64: flags (B, >= n_new) uint8 (any row pitch) and / or the flag ring
+    (B, >= R) uint8 for frames f0 .. f0 + n_new - 1."""
+    B = e.shape[0]
+    R = e.shape[1] if R is None else int(R)
+    d = _lib.VadDecideDesc()
+    d.e, d.lens = e.data_ptr(), (_lens(lens, B).data_ptr() if lens is not None else None)
+    d.e_bs = e.stride(0) if B > 1 else e.shape[1]
+    for name, t, n in (("flags", flags, n_new), ("ring", ring, R)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"vad_decide: {name} must be uint8 ({B}, >= {n}) on the GPU with dense rows, got {t.dtype} {tuple(t.shape)}")
+        setattr(d, name, t.data_ptr())
+        setattr(d, name + "_bs", t.stride(0) if B > 1 else t.shape[1])
+    d.f0, d.margin, d.thr_abs = int(f0), float(margin), float(thr_abs)
+    d.B, d.n_new, d.R, d.W, d.H, d.frame = B, int(n_new), R, int(W), int(H), int(frame)
+    _lib.check(_lib.load().fac_vad_decide(C.byref(d), _stream()), "fac_vad_decide")
+
+
+def vad(x, lens=None, frame=300, window=120, hangover=16, margin_db=6.0, floor_db=-70.0):
+    """Voice activity of x (B, T) or (B, 1, T) float32 on the GPU -> (flags (B, F) uint8, energy (B, F) float64), F = ceil(T /
+    frame) frames of `frame` samples (the last one may be partial).  energy is the fp64 sum over the frame of the squared
+    pre-emphasised signal x[n] - 0.97 x[n - 1]; a frame is raw-active when its energy exceeds thr_abs = frame * 10 ** (floor_db /
+    10) and margin = 10 ** (margin_db / 10) times the minimum energy of the last `window` frames, and active when any of the
+    last hangover + 1 frames is raw-active (fac_vad_energy, fac_vad_decide: two launches, the arithmetic is pinned in
+    include/facodec_hip.h).  lens (B,) int32 on the device: row b is its first lens[b] samples, the frames behind are energy 0
+    and flag 0.  The defaults (1.5 s, 200 ms, 6 dB, -70 dBFS) were not tuned by listening."""
+    frame, W, H, margin, thr_abs = vad_params(frame, window, hangover, margin_db, floor_db)
+    x = _rows(x, "vad")
+    B, T = x.shape
+    F = -(-T // frame)
+    e = torch.empty(B, F, device=x.device, dtype=torch.float64)
+    flags = torch.empty(B, F, device=x.device, dtype=torch.uint8)
+    if B == 0 or F == 0:
+        return flags, e
+    vad_energy(x, e, frame, lens=lens)
+    vad_decide(e, 0, F, W, H, margin, thr_abs, frame, lens=lens, flags=flags)
+    return flags, e
+
+
+def vad_take(ring, f0, k, out):
+    """fac_vad_take: out (B, k) uint8 (any row pitch, e.g. the tail columns of another buffer) = columns (f0 + j) % R of ring."""
+    B, R = ring.shape
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (B, k) or (k > 1 and out.stride(1) != 1):
+        raise ValueError(f"vad_take: out must be uint8 ({B}, {k}) on the GPU with dense rows, got {getattr(out, 'dtype', type(out))} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    _lib.check(_lib.load().fac_vad_take(_ptr(ring), ring.stride(0) if B > 1 else R, R, int(f0), int(k), _ptr(out),
+                                        out.stride(0) if B > 1 else k, B, _stream()), "fac_vad_take")
+    return out
+
+
+def sid_apply(dst, mode, sid_codes, n_q):
+    """fac_sid_apply on the three code buffers dst (B, n_q[r], k) int64: per row mode (B) int32 on the device = kind | phase << 8
+    | sid_k << 16 -- 0 PASS, 1 STORE (sid_codes[b, q, :k] = dst), 2 FILL (dst[b, q, f] = sid_codes[b, q, (phase + f) % sid_k]).
+    sid_codes (B, Q, 16) int64 is the device state.  One launch, nothing read back."""
+    n_q = tuple(int(n) for n in n_q)
+    B = mode.shape[0]
+    k = next(c for c, n in zip(dst, n_q) if n).shape[-1]
+    d = _lib.SidApplyDesc()
+    _plc_codes(d, "dst", dst, n_q, B, k, "sid_apply destination")
+    for r in range(3):
+        d.n_q[r] = n_q[r]
+    if not mode.is_cuda or mode.dtype != torch.int32 or mode.dim() != 1 or not mode.is_contiguous():
+        raise ValueError(f"sid_apply: mode must be dense int32 ({B},) on the GPU, got {mode.dtype} {tuple(mode.shape)}")
+    if not sid_codes.is_cuda or sid_codes.dtype != torch.int64 or tuple(sid_codes.shape) != (B, sum(n_q), _lib.PLC_MAX_FRAMES) \
+            or not sid_codes.is_contiguous():
+        raise ValueError(f"sid_apply: sid_codes must be contiguous int64 ({B}, {sum(n_q)}, {_lib.PLC_MAX_FRAMES}) on the GPU")
+    d.B, d.k, d.mode, d.sid_codes = B, k, mode.data_ptr(), sid_codes.data_ptr()
+    _lib.check(_lib.load().fac_sid_apply(C.byref(d), _stream()), "fac_sid_apply")
+
+
 def codes_row_bytes(T, Q, bits=10):
     """Bytes of one row of pack_codes' buffer: 4 * ceil(ceil(T Q bits / 8) / 4) (fac_codes_row_bytes)."""
     return int(_lib.load().fac_codes_row_bytes(int(T), int(Q), int(bits)))

@@ -1116,6 +1116,94 @@ class LoudnessMeter:
         return self._gate(0)
 
 
+class VoiceActivity:
+    """Voice activity detection over B parallel streams, one block at a time:
+
+        vad = VoiceActivity(B)                               # frames of 300 samples: the codec's frames
+        vad.push(block)                                      # (B, 1, k) or (B, k) float32 on the GPU, any k >= 1
+        flags = vad.take(n)                                  # (B, n) uint8: the next n frames not yet taken
+        vad.finish()                                         # decides the partial last frame
+
+    For any chunking of the signal, flags and energies are those of ops.vad on the whole signal, bit for bit.  push is two
+    launches -- fac_vad_energy, which also moves the unprocessed tail (under one frame) from one carry buffer into the other,
+    and fac_vad_decide -- or one when the block completes no frame; nothing is read back and, in the steady state, nothing is
+    allocated.  `frames` counts the frames decided so far (on the host).  Energies and flags live in device rings of `ring`
+    frames; a push may complete at most ring - window - hangover frames, and take() can only reach frames still in the ring.
+    take(n, out=) gathers into the caller's (B, n) uint8 buffer of any row pitch, e.g. CodePacketizer.active_view().  The
+    defaults (1.5 s of minimum statistics, 200 ms of hangover, 6 dB over the floor, -70 dBFS) were not tuned by listening."""
+
+    def __init__(self, B, frame=300, window=120, hangover=16, margin_db=6.0, floor_db=-70.0, ring=256, device="cuda"):
+        self.frame, self.window, self.hangover, self.margin, self.thr_abs = ops.vad_params(frame, window, hangover, margin_db, floor_db)
+        self.B, self.R, self.device = int(B), int(ring), torch.device(device)
+        if self.B < 1:
+            raise ValueError(f"VoiceActivity: B = {B}")
+        if self.R < self.window + self.hangover + 1:
+            raise ValueError(f"VoiceActivity: ring = {ring} below window + hangover + 1 = {self.window + self.hangover + 1}")
+        self.frames = self.taken = 0
+        self._carry = [torch.zeros(self.B, self.frame, device=self.device, dtype=torch.float32) for _ in range(2)]
+        self._carry_n = self._cur = 0
+        self._e = torch.zeros(self.B, self.R, device=self.device, dtype=torch.float64)
+        self._flags = torch.zeros(self.B, self.R, device=self.device, dtype=torch.uint8)
+        self._done = False
+
+    def _run(self, x, final):
+        k = x.shape[-1]
+        total = self._carry_n + k
+        n_new = total // self.frame + (1 if final and total % self.frame else 0)
+        if n_new > self.R - self.window - self.hangover:
+            raise ValueError(f"a push that completes {n_new} frames; ring = {self.R} holds window + hangover + "
+                             f"{self.R - self.window - self.hangover}")
+        src, dst = self._carry[self._cur], self._carry[1 - self._cur]
+        ops.vad_energy(x, self._e, self.frame, f0=self.frames, R=self.R, carry_in=src, carry_n=self._carry_n, carry_out=dst, final=final)
+        self._cur, self._carry_n = 1 - self._cur, (0 if final else total % self.frame)
+        if n_new:
+            ops.vad_decide(self._e, self.frames, n_new, self.window, self.hangover, self.margin, self.thr_abs, self.frame, R=self.R,
+                           ring=self._flags)
+            self.frames += n_new
+
+    def push(self, block):
+        if self._done:
+            raise RuntimeError("push() after finish()")
+        x = ops._rows(block, "VoiceActivity.push")
+        if x.shape[0] != self.B or x.shape[1] < 1:
+            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
+        self._run(x, False)
+
+    def finish(self):
+        """Decides the partial last frame, if there is one; the session takes no more audio."""
+        if not self._done and self._carry_n:
+            # the unprocessed tail is the block; the carry keeps only the sample before it
+            tail = self._carry[self._cur][:, 1:1 + self._carry_n]
+            self._carry_n = 0
+            self._run(tail, True)
+        self._done = True
+
+    def _window(self, n):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"take({n}): at least one frame")
+        if self.taken + n > self.frames:
+            raise ValueError(f"take({n}): only {self.frames - self.taken} decided frames are not yet taken")
+        if self.taken < self.frames - self.R:
+            raise ValueError(f"take({n}): frame {self.taken} has left the ring of {self.R} (frames decided: {self.frames})")
+        return n
+
+    def take(self, n, out=None):
+        n = self._window(n)
+        if out is None:
+            out = torch.empty(self.B, n, device=self.device, dtype=torch.uint8)
+        ops.vad_take(self._flags, self.taken, n, out)
+        self.taken += n
+        return out
+
+    def energies(self, n):
+        """(B, n) float64: the energies of the last n decided frames (a copy out of the ring; for tests and meters)."""
+        if not 1 <= n <= min(self.frames, self.R):
+            raise ValueError(f"energies({n}): {min(self.frames, self.R)} frames are in the ring")
+        idx = torch.arange(self.frames - n, self.frames, device=self.device) % self.R
+        return self._e[:, idx]
+
+
 class ResampledSession:
     """A StreamingCodec / StreamingConverter / StreamingDecoder that takes its audio at `in_rate` and gives it at `out_rate`:
 
@@ -1203,9 +1291,17 @@ class CodePacketizer:
     redundancy = (rp, rc, rr), elementwise <= n_q (e.g. (1, 2, 0)): in-band redundancy.  Packets are then b"FQ"
     (bitstream.write_packet_fec): call j carries its own codes and, behind them, the leading rp / rc / rr quantizers of call
     j - 1 (none on the first call), so a receiver that waits one push (StreamingReceiver(delay=1)) can play a lost push at the
-    lower rate.  Two pack launches into one buffer, still one device-to-host copy.  With None the packets are the bytes of before."""
+    lower rate.  Two pack launches into one buffer, still one device-to-host copy.  With None the packets are the bytes of before.
 
-    def __init__(self, n_q, bits=10, codebook_size=1024, redundancy=None):
+    dtx = dict(sid_every=8): discontinuous transmission.  packet(codes, active) then takes the push's voice
+    activity flags, (B, k) uint8 on the device (VoiceActivity.take), which ride in the tail columns of the pack buffer: still one
+    device-to-host copy -- and none of the flags on their own when VoiceActivity.take(k, out=tx.active_view(B, k, device)) wrote
+    them there.  Per stream: a push with any active frame is a normal packet; of a run of pushes without one, the first and
+    then every sid_every-th are SID packets (the same bytes with the magic's second letter in lower case: "silence follows"), the
+    others are None: nothing is sent.  seq advances and the redundant layer is kept on every call, whatever is emitted.  With
+    dtx=None (and no `active`) every byte is the byte of before."""
+
+    def __init__(self, n_q, bits=10, codebook_size=1024, redundancy=None, dtx=None):
         from . import bitstream
         self.n_q = tuple(int(n) for n in n_q) + (0,) * (3 - len(n_q))
         bitstream._check_layout(bits, self.n_q, "CodePacketizer")
@@ -1216,6 +1312,31 @@ class CodePacketizer:
             if not sum(self.redundancy):
                 raise ValueError("CodePacketizer: redundancy without a quantizer (pass None for plain packets)")
         self._red_prev = None                    # (k, per-stream redundant payload bytes) of the previous call
+        self.sid_every = None
+        if dtx is not None:
+            dtx = dict(dtx)
+            self.sid_every = int(dtx.pop("sid_every", 8))
+            if dtx or self.sid_every < 1:
+                raise ValueError(f"CodePacketizer: dtx = dict(sid_every >= 1), got sid_every = {self.sid_every} and {sorted(dtx)}")
+        self._silent = None                      # per stream: pushes without an active frame in a row
+        self._buf = {}                           # dtx: (B, k, device) -> the pack buffer, codes in front, flags in the tail
+
+    def _pack_buf(self, B, k, device):
+        key = (int(B), int(k), torch.device(device))
+        if key not in self._buf:
+            rb = ops.codes_row_bytes(k, sum(self.n_q), self.bits)
+            rb_red = ops.codes_row_bytes(k, sum(self.redundancy), self.bits) if self.redundancy is not None else 0
+            # rows of whole words (fac_codes_pack's row stride): the k flags are padded up to a multiple of 4 bytes
+            self._buf[key] = (torch.zeros(key[0], rb + rb_red + (key[1] + 3) // 4 * 4, dtype=torch.uint8, device=key[2]), rb, rb_red)
+        return self._buf[key]
+
+    def active_view(self, B, k, device="cuda"):
+        """dtx: the (B, k) uint8 tail columns of the pack buffer of pushes of k frames -- where packet(codes, active) wants the
+        flags.  Pass it as VoiceActivity.take(k, out=...) and then as `active`: no copy is made."""
+        if self.sid_every is None:
+            raise ValueError("active_view(): the packetizer was built without dtx=")
+        buf, rb, rb_red = self._pack_buf(B, k, device)
+        return buf[:, rb + rb_red:rb + rb_red + int(k)]
 
     def header(self, timbre=None):
         from . import bitstream
@@ -1227,12 +1348,14 @@ class CodePacketizer:
                     codebook_size=self.codebook_size, timbre_dim=tim.shape[1], stream=True)
         return [bitstream.write(head, tim[b].tobytes(), b"") for b in range(tim.shape[0])]
 
-    def packet(self, codes):
+    def packet(self, codes, active=None):
         codes = list(codes) + [None] * (3 - len(codes))
         got = tuple(0 if c is None else int(c.shape[1]) for c in codes)
         if got != self.n_q:
             raise ValueError(f"codes with {got} rows, the packetizer was built for n_q = {self.n_q}")
         k = next(c for c in codes if c is not None).shape[-1]
+        if active is not None:
+            return self._packet_dtx(codes, active, k)
         if self.redundancy is None:
             return self._emit(k, ops.pack_codes(codes, bits=self.bits).cpu().numpy())
         # primary rows and this push's redundant layer (its leading quantizers: strided views of the same codes) side by side
@@ -1247,19 +1370,53 @@ class CodePacketizer:
         rows = buf.cpu().numpy()
         return self._emit(k, rows[:, :rb], rows[:, rb:])
 
-    def _emit(self, k, rows, red_rows=None):
+    def _packet_dtx(self, codes, active, k):
+        if self.sid_every is None:
+            raise ValueError("packet(codes, active): the packetizer was built without dtx=")
+        first = next(c for c in codes if c is not None)
+        B = first.shape[0]
+        if not isinstance(active, torch.Tensor) or not active.is_cuda or active.dtype != torch.uint8 or tuple(active.shape) != (B, k):
+            raise ValueError(f"active must be a uint8 ({B}, {k}) tensor on the GPU (VoiceActivity.take), got "
+                             f"{getattr(active, 'dtype', type(active))} {tuple(getattr(active, 'shape', ()))}")
+        buf, rb, rb_red = self._pack_buf(B, k, first.device)
+        ops.pack_codes(codes, bits=self.bits, out=buf[:, :rb])
+        if rb_red:
+            ops.pack_codes([c[:, :n] if n else None for c, n in zip(codes, self.redundancy)], bits=self.bits, out=buf[:, rb:rb + rb_red])
+        tail = buf[:, rb + rb_red:rb + rb_red + k]
+        if active.data_ptr() != tail.data_ptr() or active.stride() != tail.stride():
+            tail.copy_(active)                                   # device to device; active_view() avoids it
+        rows = buf.cpu().numpy()
+        return self._emit(k, rows[:, :rb], rows[:, rb:rb + rb_red] if rb_red else None, rows[:, rb + rb_red:rb + rb_red + k])
+
+    def _emit(self, k, rows, red_rows=None, active_rows=None):
         """Host part of packet(): the packed rows of this push (uint8 (B, >= payload bytes) arrays; red_rows: its redundant
-        layer, kept for the next call) -> one packet per stream."""
+        layer, kept for the next call; active_rows: its (B, k) voice activity flags under dtx) -> one entry per stream: a
+        packet, or None for a suppressed push."""
         from . import bitstream
+        B = rows.shape[0]
         n = bitstream.payload_bytes(k, sum(self.n_q), self.bits)
         seq, self.seq = self.seq, (self.seq + 1) & 0xFFFF
+        kind = [0] * B                                           # 0 normal, 1 SID, None suppressed
+        if self.sid_every is not None:
+            if self._silent is None:
+                self._silent = [0] * B
+            for b in range(B):
+                if active_rows is None or active_rows[b, :k].any():
+                    self._silent[b] = 0
+                else:
+                    self._silent[b] += 1
+                    kind[b] = 1 if (self._silent[b] - 1) % self.sid_every == 0 else None
+        elif active_rows is not None:
+            raise ValueError("voice activity flags for a packetizer built without dtx=")
         if self.redundancy is None:
-            return [bitstream.write_packet(seq, k, rows[b, :n].tobytes()) for b in range(rows.shape[0])]
-        k_prev, prev = self._red_prev if self._red_prev is not None else (0, [b""] * rows.shape[0])
+            return [None if kind[b] is None else bitstream.write_packet(seq, k, rows[b, :n].tobytes(), sid=bool(kind[b]))
+                    for b in range(B)]
+        k_prev, prev = self._red_prev if self._red_prev is not None else (0, [b""] * B)
         n_red = bitstream.payload_bytes(k, sum(self.redundancy), self.bits)
-        self._red_prev = (k, [red_rows[b, :n_red].tobytes() for b in range(rows.shape[0])])
-        return [bitstream.write_packet_fec(seq, k, rows[b, :n].tobytes(), k_prev, self.redundancy, prev[b])
-                for b in range(rows.shape[0])]
+        self._red_prev = (k, [red_rows[b, :n_red].tobytes() for b in range(B)])
+        return [None if kind[b] is None else
+                bitstream.write_packet_fec(seq, k, rows[b, :n].tobytes(), k_prev, self.redundancy, prev[b], sid=bool(kind[b]))
+                for b in range(B)]
 
 
 class CodeDepacketizer:
@@ -1303,6 +1460,35 @@ class CodeDepacketizer:
         return ops.unpack_codes(ops.h2d(torch.from_numpy(rows), self.device), self.n_q, k, bits=self.bits)
 
 
+def dtx_row():
+    """Host state of one receiver row under discontinuous transmission."""
+    return dict(in_dtx=False, since=0, sid_k=0, phase=0)
+
+
+def dtx_step(row, arrived, k, sid_timeout=24):
+    """One tick of one row of the receiver's DTX state machine, host only.  arrived: "normal" (a valid packet is played), "sid"
+    (a valid SID packet is played), "redundant" (the push is played from the redundant layer) or None (nothing playable).
+    Advances `row` (dtx_row()) and -> (fac_sid_apply's mode word, comfort): comfort is True when the push is k comfort frames,
+    i.e. played as PRIMARY from the stored SID codes; False with arrived None is today's concealment (a timed-out row has then
+    left DTX)."""
+    from . import _lib
+    if arrived == "normal":
+        row["in_dtx"] = False
+        return _lib.SID_PASS, False
+    if arrived == "sid":
+        row.update(in_dtx=True, since=0, sid_k=int(k), phase=0)
+        return _lib.SID_STORE | int(k) << 16, False
+    if arrived == "redundant":
+        return _lib.SID_PASS, False
+    if row["in_dtx"] and row["since"] < sid_timeout:
+        mode = _lib.SID_FILL | row["phase"] << 8 | row["sid_k"] << 16
+        row["since"] += 1
+        row["phase"] = (row["phase"] + int(k)) % row["sid_k"]
+        return mode, True
+    row["in_dtx"] = False
+    return _lib.SID_PASS, False
+
+
 class StreamingReceiver:
     """Receiver that keeps playing through packet loss: per tick one entry per stream, a packet or None, in; audio
     out.  Streams are judged one by one -- a caller's lost packet does not touch its neighbours.
@@ -1324,9 +1510,18 @@ class StreamingReceiver:
     both payload rows in one buffer), ops.unpack_codes once (twice when a row is REDUNDANT), fac_plc_select, the LayeredDecoder
     hop (a graph replay), fac_plc_gain in place -- no device-to-host copy and no synchronisation; `stats` comes from the host's
     parsing: per stream received, corrupt, misordered (packets), recovered, concealed (frames).  `last_status` is the status
-    list of the last tick.  With graphs the returned wave is a static buffer, valid until the next call."""
+    list of the last tick.  With graphs the returned wave is a static buffer, valid until the next call.
 
-    def __init__(self, model, header_blobs, delay=0, hold=2, fade=6, recover=1, use_graphs=True, max_frames=16, device="cuda"):
+    dtx=True: the receiving half of discontinuous transmission (the sender is CodePacketizer(dtx=...)).  A SID
+    packet plays as it is and its k frames of codes are kept on the device; from then on a row for which nothing playable
+    arrives is not concealed: it plays comfort frames -- those codes, cycled, through the unchanged decoder at gain 1 -- for up
+    to sid_timeout pushes after the last SID packet (counted in stats[b]["comfort"], not in "concealed").  A normal packet ends
+    that; a row that times out fades through the concealment above, so a dead link still goes silent.  One more small launch
+    per tick (fac_sid_apply, between the unpack and fac_plc_select); its mode words ride in the same staging buffer: still one
+    host-to-device copy.  sid_timeout = 24 pushes (three refreshes at the sender's default) was not tuned by listening."""
+
+    def __init__(self, model, header_blobs, delay=0, hold=2, fade=6, recover=1, use_graphs=True, max_frames=16, device="cuda",
+                 dtx=False, sid_timeout=24):
         from . import bitstream
         from . import _lib
         if delay not in (0, 1):
@@ -1338,7 +1533,13 @@ class StreamingReceiver:
         head = CodeDepacketizer(header_blobs, device=device)
         self.n_q, self.bits, self.B, self.device = tuple(head.n_q), head.bits, head.B, head.device
         self.delay, self.policy = delay, (int(hold), int(fade), int(recover))
-        self.reader = bitstream.LossyPacketReader(self.B, self.n_q, self.bits)
+        self.dtx, self.sid_timeout = bool(dtx), int(sid_timeout)
+        if self.dtx and self.sid_timeout < 0:
+            raise ValueError(f"sid_timeout = {sid_timeout} (>= 0 pushes)")
+        self.reader = bitstream.LossyPacketReader(self.B, self.n_q, self.bits, dtx=self.dtx)
+        self._dtx_rows = [dtx_row() for _ in range(self.B)] if self.dtx else None
+        self._sid_codes = torch.zeros(self.B, sum(self.n_q), _lib.PLC_MAX_FRAMES, dtype=torch.int64, device=self.device) if self.dtx else None
+        self.comfort = [0] * self.B
         self.dec = LayeredDecoder(model, head.timbre, use_graphs=use_graphs, max_frames=max_frames)
         self.min_prime, self.max_frames = self.dec.min_prime, int(max_frames)
         self.state = ops.PlcState(self.B, self.n_q, self.device)
@@ -1352,8 +1553,12 @@ class StreamingReceiver:
     @property
     def stats(self):
         rd = self.reader
-        return [dict(received=rd.received[b], recovered=self.recovered[b], concealed=self.concealed[b], corrupt=rd.corrupt[b],
-                     misordered=rd.misordered[b]) for b in range(self.B)]
+        out = [dict(received=rd.received[b], recovered=self.recovered[b], concealed=self.concealed[b], corrupt=rd.corrupt[b],
+                    misordered=rd.misordered[b]) for b in range(self.B)]
+        if self.dtx:
+            for b in range(self.B):
+                out[b]["comfort"] = self.comfort[b]
+        return out
 
     def prime(self, packets):
         if self.dec._n_q is not None:
@@ -1374,9 +1579,13 @@ class StreamingReceiver:
         if sum(self.n_red):
             self._red = [torch.zeros(self.B, max(n, 1), self.max_frames, dtype=torch.int64, device=self.device)[:, :n] for n in self.n_red]
         status = [0] * self.B
-        buf, n1, _ = self._stage(status, [p.payload for p in parsed], None, k)
+        mode = [dtx_step(self._dtx_rows[b], "sid" if p.sid else "normal", k, self.sid_timeout)[0] for b, p in enumerate(parsed)] \
+            if self.dtx else None
+        buf, n1, _ = self._stage(status, [p.payload for p in parsed], None, k, mode)
         wave = self.dec.prime(ops.unpack_codes(buf[1], self.n_q, k, bits=self.bits))
         dst, n_use = self.dec.buffers(k)
+        if self.dtx:                                      # a stream that starts in silence: its first packet is a SID packet
+            ops.sid_apply(dst, buf[2], self._sid_codes, self.n_q)
         ops.plc_select(dst, None, buf[0], self.state, dst, n_use, self._ramp_buf(k), (0, 0, 0), *self.policy)
         self.last_status = status
         return wave
@@ -1386,45 +1595,65 @@ class StreamingReceiver:
             self._ramp[k] = torch.empty(self.B, k + 1, dtype=torch.float32, device=self.device)
         return self._ramp[k]
 
-    def _stage(self, status, prim, red, k):
+    def _stage(self, status, prim, red, k, mode=None):
         """One host buffer [B status words | B rows of (primary payload | redundant payload)], one copy to the device ->
-        ((status (B) int32, rows (B, n1 + n2) uint8) device views, n1, n2)."""
+        ((status (B) int32, rows (B, n1 + n2) uint8) device views, n1, n2).  mode (dtx): B more words behind the status words,
+        and a third view, mode (B) int32, in the result."""
         import numpy as np
         from . import bitstream
         n1 = bitstream.payload_bytes(k, sum(self.n_q), self.bits)
         n2 = bitstream.payload_bytes(k, sum(self.n_red), self.bits) if red is not None else 0
-        host = np.zeros(4 * self.B + self.B * (n1 + n2), dtype=np.uint8)
+        nw = 4 * self.B * (1 if mode is None else 2)
+        host = np.zeros(nw + self.B * (n1 + n2), dtype=np.uint8)
         host[:4 * self.B].view("<i4")[:] = status
-        rows = host[4 * self.B:].reshape(self.B, n1 + n2)
+        if mode is not None:
+            host[4 * self.B:nw].view("<i4")[:] = mode
+        rows = host[nw:].reshape(self.B, n1 + n2)
         for b in range(self.B):
             if prim[b] is not None:
                 rows[b, :n1] = np.frombuffer(prim[b], dtype=np.uint8)
             if red is not None and red[b] is not None:
                 rows[b, n1:] = np.frombuffer(red[b], dtype=np.uint8)
         dev = ops.h2d(torch.from_numpy(host), self.device)
-        return (dev[:4 * self.B].view(torch.int32), dev[4 * self.B:].view(self.B, n1 + n2)), n1, n2
+        views = (dev[:4 * self.B].view(torch.int32), dev[nw:].view(self.B, n1 + n2))
+        if mode is not None:
+            views += (dev[4 * self.B:nw].view(torch.int32),)
+        return views, n1, n2
 
     def _play(self, prim, red, k):
         """prim[b] / red[b]: the Packet a row is played from, or None.  A packet of another frame count than k is of no use."""
         from . import _lib
-        status, p_rows, r_rows = [], [], []
+        status, p_rows, r_rows, mode = [], [], [], ([] if self.dtx else None)
         for b in range(self.B):
             p, r = prim[b], red[b] if red is not None else None
+            arrived = None
             if p is not None and p.n_frames == k:
-                st = _lib.PLC_PRIMARY
+                st, arrived = _lib.PLC_PRIMARY, "sid" if p.sid else "normal"
             elif r is not None and r.n_red_frames == k and r.n_red == self.n_red and sum(self.n_red):
-                st = _lib.PLC_REDUNDANT
-                self.recovered[b] += k
+                st, arrived = _lib.PLC_REDUNDANT, "redundant"
             else:
                 st = _lib.PLC_LOST
+            comfort = False
+            if self.dtx:
+                word, comfort = dtx_step(self._dtx_rows[b], arrived, k, self.sid_timeout)
+                mode.append(word)
+            if comfort:                                       # the stored SID codes, cycled: played like a packet that arrived
+                st = _lib.PLC_PRIMARY
+                self.comfort[b] += k
+            elif st == _lib.PLC_REDUNDANT:
+                self.recovered[b] += k
+            elif st == _lib.PLC_LOST:
                 self.concealed[b] += k
             status.append(st)
-            p_rows.append(p.payload if st == _lib.PLC_PRIMARY else None)
+            p_rows.append(p.payload if arrived in ("normal", "sid") else None)
             r_rows.append(r.red_payload if st == _lib.PLC_REDUNDANT else None)
         any_red = _lib.PLC_REDUNDANT in status
-        (st_dev, rows), n1, n2 = self._stage(status, p_rows, r_rows if any_red else None, k)
+        staged, n1, n2 = self._stage(status, p_rows, r_rows if any_red else None, k, mode)
+        st_dev, rows = staged[0], staged[1]
         dst, n_use = self.dec.buffers(k)
         ops.unpack_codes(rows[:, :n1] if n2 else rows, self.n_q, k, bits=self.bits, out=dst)
+        if self.dtx:
+            ops.sid_apply(dst, staged[2], self._sid_codes, self.n_q)
         red_codes = None
         if any_red:
             red_codes = [c[:, :, :k] for c in self._red]

@@ -1161,6 +1161,95 @@ int fac_plc_select(const fac_plc_select_desc* d, fac_stream_t stream);
 int fac_plc_gain(const float* x, int64_t x_bs, float* y, int64_t y_bs, const float* ramp, int B, int k, int frame,
                  fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voice activity, silent-push suppression, comfort frames (csrc/vad.hip).  This comment is the normative
+ * definition.  Every operation below is an IEEE fp64 operation with one round-to-nearest each; nothing is fused.
+ *
+ * fac_vad_energy: per row b the signal is the virtual concatenation [carry | block]:
+ *   carry_in (B, frame) fp32, dense   element 0 is the sample BEFORE the first unprocessed one (0 at the start of a signal),
+ *                                      elements 1 .. carry_n the unprocessed tail of earlier calls; NULL: carry_n = 0 and that
+ *                                      sample is 0 (the offline call)
+ *   x (B, k) fp32, pitch x_bs         this call's samples
+ * Unprocessed sample s (s = 0 is the first) belongs to frame s / frame of this call.  n_whole = (carry_n + k) / frame whole
+ * frames are processed, and the partial one behind them when is_final != 0 and (carry_n + k) % frame != 0.  For frame i:
+ *   d[n] = (double)v[n] - 0.97 * (double)v[n - 1]                    v[-1] of frame 0 is the sample before (carry element 0)
+ *   lane l of 64 adds d[n] * d[n] for n = l, l + 64, l + 128, ... < frame (only samples that exist) in increasing n, starting
+ *   from 0.0;  then for dist = 32, 16, 8, 4, 2, 1 every lane replaces its sum by  own + sum of lane (l XOR dist);  E = lane 0.
+ *   e[b * e_bs + (f0 + i) % R] = E.          f0: the global index of this call's first frame; a plain (B, F) array is R >= F, f0 = 0.
+ * lens (B) int32, NULL or (only without carry buffers) the rows' lengths in samples: samples at and behind lens[b] do not
+ * exist, frames at or past ceil(lens[b] / frame) get E = 0.
+ * carry_out (B, frame), NULL or a buffer OTHER than carry_in: written with the carry of the next call, element 0 the last
+ * processed sample (or carry_in's element 0 when no whole frame was processed), then the (carry_n + k) % frame unprocessed
+ * ones; the host alternates two buffers, so no word is read by one thread and written by another in one launch.
+ * Refused before any launch: a NULL descriptor, x or e; B outside 1 .. 65535; frame outside 1 .. FAC_VAD_MAX_FRAME; k < 1;
+ * carry_n outside 0 .. frame - 1, or > 0 without carry_in; carry_out == carry_in; lens with a carry buffer; x_bs < k or
+ * e_bs < R with B > 1; f0 < 0; R below the frames of the call.
+ *
+ * fac_vad_decide: flags for the n_new frames f0 .. f0 + n_new - 1 from the energy ring e (B, R) (frame g at column g % R):
+ *   N[f]      = min E[g] over g = max(0, f - W + 1) .. f
+ *   raw[f]    = E[f] > thr_abs  &&  E[f] > margin * N[f]
+ *   active[f] = raw[g] for any g = max(0, f - H) .. f;  with lens, frames at or past ceil(lens[b] / frame) are 0.
+ * All windows are finite, there is no recurrence: a flag depends on the W + H energies up to its frame and nothing older.
+ * flags (NULL or uint8, pitch flags_bs): flags[b * flags_bs + i] = active[f0 + i];  ring (NULL or uint8 (B, R), pitch ring_bs):
+ * ring[b * ring_bs + (f0 + i) % R] = the same.  One workgroup per (row, 256 frames): energies of the tile and its W - 1 + H
+ * older neighbours in LDS, raw of the tile and its H older neighbours in LDS, barrier, flags.
+ * Refused before any launch: a NULL descriptor or e; flags and ring both NULL; B outside 1 .. 65535; n_new < 1; W outside
+ * 1 .. FAC_VAD_MAX_WINDOW; H outside 0 .. FAC_VAD_MAX_WINDOW; margin <= 1; thr_abs < 0; f0 < 0; frame outside
+ * 1 .. FAC_VAD_MAX_FRAME; R < min(f0 + n_new, W + H + n_new) (a ring that has not wrapped yet holds every frame); pitches
+ * below R (e, ring) or n_new (flags) with B > 1.
+ *
+ * fac_vad_take: out[b * out_bs + j] = ring[b * ring_bs + (f0 + j) % R] for j < k: the gather behind VoiceActivity.take(out=).
+ *
+ * fac_sid_apply: the receiver's comfort frames.  Device state: sid_codes (B, Q, FAC_PLC_MAX_FRAMES) int64, the codes of the
+ * last silence descriptor of every row.  mode (B) int32 on the device is kind | phase << 8 | sid_k << 16:
+ *   FAC_SID_PASS   the row is not touched (and so is a row of any other kind value)
+ *   FAC_SID_STORE  sid_codes[b, q, f] = dst[b, q, f] for f < k
+ *   FAC_SID_FILL   dst[b, q, f] = sid_codes[b, q, (phase + f) % sid_k] for f < k;  sid_k outside 1 .. FAC_PLC_MAX_FRAMES: not touched
+ * dst are the three code buffers (B, n_q[r], k) of fac_plc_select, q runs over the quantizers in RVQ order.  phase and sid_k
+ * are the host's (they are deterministic).  One thread per (row, quantizer): every word has one writer.  Refused before any
+ * launch: a NULL descriptor, mode or sid_codes; B < 1; k outside 1 .. FAC_PLC_MAX_FRAMES; Q outside 1 .. FAC_VQ_DECODE_MAX_Q
+ * or a negative count; a NULL dst with n_q[r] > 0; strides that cannot address (B, n_q[r], k).
+ * ---------------------------------------------------------------------------------------- */
+#define FAC_VAD_MAX_FRAME 4096
+#define FAC_VAD_MAX_WINDOW 2048
+#define FAC_SID_PASS 0
+#define FAC_SID_STORE 1
+#define FAC_SID_FILL 2
+typedef struct fac_vad_energy_desc {
+  const float* carry_in;    /* (B, frame) or NULL */
+  float* carry_out;         /* (B, frame) or NULL, never carry_in */
+  const float* x;           /* (B, k), pitch x_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  double* e;                /* written: (B, R), pitch e_bs */
+  int64_t x_bs, e_bs, f0;
+  int32_t B, k, frame, carry_n, is_final, R;
+} fac_vad_energy_desc;
+int fac_vad_energy(const fac_vad_energy_desc* d, fac_stream_t stream);
+
+typedef struct fac_vad_decide_desc {
+  const double* e;          /* (B, R), pitch e_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  uint8_t* flags;           /* written: (B, n_new), pitch flags_bs; or NULL */
+  uint8_t* ring;            /* written: (B, R), pitch ring_bs; or NULL */
+  int64_t e_bs, flags_bs, ring_bs, f0;
+  double margin, thr_abs;
+  int32_t B, n_new, R, W, H, frame;
+} fac_vad_decide_desc;
+int fac_vad_decide(const fac_vad_decide_desc* d, fac_stream_t stream);
+int fac_vad_take(const uint8_t* ring, int64_t ring_bs, int R, int64_t f0, int k, uint8_t* out, int64_t out_bs, int B,
+                 fac_stream_t stream);
+
+typedef struct fac_sid_apply_desc {
+  int64_t* dst[3];          /* (B, n_q[r], k): dst[r][b*dst_bs[r] + i*dst_qs[r] + f] */
+  int64_t dst_bs[3], dst_qs[3];
+  int32_t n_q[3];
+  int32_t B;
+  const int32_t* mode;      /* (B) */
+  int64_t* sid_codes;       /* (B, Q, FAC_PLC_MAX_FRAMES) state */
+  int32_t k, reserved;
+} fac_sid_apply_desc;
+int fac_sid_apply(const fac_sid_apply_desc* d, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
