@@ -305,54 +305,15 @@ __global__ __launch_bounds__(512, 2) void conv1d_bsplit2_kernel(ConvArgs a) {
     float* yg = a.y ? a.y + (long long)b * a.y_bs : nullptr;
     float* y2g = a.y2 ? a.y2 + (long long)b * a.y_bs : nullptr;
     const float* rg = a.res ? a.res + (long long)b * a.y_bs : nullptr;
-    const bool vec_ok = (a.y_cs & 3) == 0 && (a.y_bs & 3) == 0 && (!yg || (reinterpret_cast<unsigned long long>(a.y) & 15) == 0) &&
-                        (!y2g || (reinterpret_cast<unsigned long long>(a.y2) & 15) == 0) &&
-                        (!rg || (reinterpret_cast<unsigned long long>(a.res) & 15) == 0);
+    const bool vec_ok = epi_vec_ok(a.y, a.y2, a.res, a.y_cs, a.y_bs);
     for (int q = tid; q < B2_CO * QPR; q += 512) {
       const int row = q / QPR, tq = q - row * QPR;
       const int co = co0 + row, t = t0 + 4 * tq;
       if (co >= a.C_out || t >= a.T_out) continue;
       const float4 av = *reinterpret_cast<const float4*>(tile + row * EP + 4 * tq);
       float v[4] = {av.x, av.y, av.z, av.w};
-      const float bs = a.bias ? a.bias[co] : 0.f;
-      const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-      const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-      const long long o = (long long)co * a.y_cs + t;
-      const bool full = vec_ok && t + 3 < a.T_out;
-      float rv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (rg) {
-        if (full) {
-          const float4 r4 = *reinterpret_cast<const float4*>(rg + o);
-          rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) rv[i] = t + i < a.T_out ? rg[o + i] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float x = v[i] + bs;
-        if (a.alpha_out) x = snake_apply(x, al, inv);
-        if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-        v[i] = x + rv[i];
-      }
-      float w[4] = {0.f, 0.f, 0.f, 0.f};
-      if (y2g) {
-        const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
-      }
-      if (full) {
-        if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w[0], w[1], w[2], w[3]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (t + i >= a.T_out) continue;
-          if (yg) yg[o + i] = v[i];
-          if (y2g) y2g[o + i] = w[i];
-        }
-      }
+      epi_quad(v, epi_row_load(true, co, a.bias, a.alpha_out, y2g ? a.alpha2 : nullptr), a.alpha_out != nullptr, a.act, yg, y2g, rg,
+               (long long)co * a.y_cs + t, 1, epi_first(a.T_out - t), vec_ok && t + 3 < a.T_out);
     }
   }
 }

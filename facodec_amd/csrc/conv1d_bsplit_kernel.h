@@ -30,19 +30,7 @@ __host__ __device__ constexpr int bs_slots(int K, int G) { return (G * K + 1) & 
 // divided ONCE per tile row instead of once per quad: lane l of each aligned group of 16 lanes holds the row that group visits in
 // iteration l of the quad loop (the loop steps by a multiple of 16 quads over rows of a multiple of 16 quads, so the 16 lanes of a group
 // always share a row, and a tile takes at most 16 iterations); iteration j fetches lane j of the own group through the LDS crossbar
-// (ds_bpermute_b32: no memory, no barrier).  Every lane of the wave must be active at the fetch.
-struct EpiRow {
-  float bs, al, inv, a2, i2;
-};
-__device__ __forceinline__ EpiRow epi_row_load(bool valid, int co, const float* bias, const float* alpha, const float* alpha2) {
-  EpiRow r = {0.f, 0.f, 0.f, 0.f, 0.f};
-  if (valid) {
-    if (bias) r.bs = bias[co];
-    if (alpha) { r.al = alpha[co]; r.inv = snake_inv(r.al); }
-    if (alpha2) { r.a2 = alpha2[co]; r.i2 = snake_inv(r.a2); }
-  }
-  return r;
-}
+// (ds_bpermute_b32: no memory, no barrier).  Every lane of the wave must be active at the fetch.  EpiRow / epi_row_load: conv1d_epilogue.h.
 __device__ __forceinline__ float epi_row_get(float mine, int lane, int j) {
   return __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & 48) + j) << 2, __float_as_int(mine)));
 }

@@ -478,9 +478,8 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
     const int ch0 = (row0 / GS_ROWS) * cpt;
     const long long u_tot = n_total * rp;                   // outputs per (clip | batch) row
     const long long u0 = (long long)n0 * rp;
-    const bool al_ok = (a.y_cs & 3) == 0 && (a.y_bs & 3) == 0 && (!a.y || (reinterpret_cast<unsigned long long>(a.y) & 15) == 0) &&
-                       (!a.y2 || (reinterpret_cast<unsigned long long>(a.y2) & 15) == 0) &&
-                       (!a.res || (reinterpret_cast<unsigned long long>(a.res) & 15) == 0) && (!flat || (a.T_out & 3) == 0);
+    const bool al_ok = (!flat || (a.T_out & 3) == 0) && epi_vec_ok(a.y, a.y2, a.res, a.y_cs, a.y_bs);
+    const bool has_alpha = a.alpha_out != nullptr;
     for (int q = tid; q < cpt * QPR; q += NTH) {
       const int cl = q / QPR, uq = q - cl * QPR;
       const int co = ch0 + cl;
@@ -502,66 +501,23 @@ __global__ __launch_bounds__(512, 2) void conv1d_gemm_split_kernel(ConvArgs a) {
       if (flat) {
         const long long bb = u / a.T_out, tt = u - bb * a.T_out;
         o = bb * a.y_bs + (long long)co * a.y_cs + tt;
-        const long long in_clip = a.T_out - tt;
-        lim = lim < in_clip ? lim : in_clip;
+        lim = lim < a.T_out - tt ? lim : a.T_out - tt;
       } else {
         o = (long long)b * a.y_bs + (long long)co * a.y_cs + u;
       }
-      const bool full = al_ok && lim >= 4;
-      const float bs = a.bias ? a.bias[co] : 0.f;
-      const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-      const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-      if (!full && flat && lim < 4) {
-        // ragged quad of the flattened layout (T_out % 4 != 0): sample by sample
+      const EpiRow row = epi_row_load(true, co, a.bias, a.alpha_out, a.y2 ? a.alpha2 : nullptr);
+      if (flat && lim < 4) {
+        // ragged quad of the flattened layout (T_out % 4 != 0): sample by sample, each with its own (clip, time)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const long long ui = u + i;
           if (ui >= u_tot) continue;
-          const long long bb = ui / a.T_out, tt = ui - bb * a.T_out;
-          const long long oi = bb * a.y_bs + (long long)co * a.y_cs + tt;
-          float x = v[i] + bs;
-          if (a.alpha_out) x = snake_apply(x, al, inv);
-          if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-          if (a.res) x += a.res[oi];
-          if (a.y) a.y[oi] = x;
-          if (a.y2) { const float a2 = a.alpha2[co]; a.y2[oi] = snake_apply(x, a2, snake_inv(a2)); }
+          const long long bi = ui / a.T_out, ti = ui - bi * a.T_out;
+          epi_one(v[i], row, has_alpha, a.act, a.y, a.y2, a.res, bi * a.y_bs + (long long)co * a.y_cs + ti);
         }
         continue;
       }
-      float rv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (a.res) {
-        if (full) {
-          const float4 r4 = *reinterpret_cast<const float4*>(a.res + o);
-          rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) rv[i] = i < lim ? a.res[o + i] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float x = v[i] + bs;
-        if (a.alpha_out) x = snake_apply(x, al, inv);
-        if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-        v[i] = x + rv[i];
-      }
-      float w[4] = {0.f, 0.f, 0.f, 0.f};
-      if (a.y2) {
-        const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
-      }
-      if (full) {
-        if (a.y) *reinterpret_cast<float4*>(a.y + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (a.y2) *reinterpret_cast<float4*>(a.y2 + o) = make_float4(w[0], w[1], w[2], w[3]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (i >= lim) continue;
-          if (a.y) a.y[o + i] = v[i];
-          if (a.y2) a.y2[o + i] = w[i];
-        }
-      }
+      epi_quad(v, row, has_alpha, a.act, a.y, a.y2, a.res, o, 1, epi_first(lim), al_ok && lim >= 4);
     }
   }
 }

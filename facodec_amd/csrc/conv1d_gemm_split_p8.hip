@@ -45,7 +45,7 @@ __device__ __forceinline__ void gp_dma16(const unsigned char* src, unsigned lds)
 
 typedef const __attribute__((address_space(1))) bf16x8 glb_bf16x8;
 
-// ---- epilogue: one lane = 4 consecutive output samples of one channel (the 128 x 128 form's value chain, element for element).
+// ---- epilogue: one lane = 4 consecutive output samples of one channel (the value chain of conv1d_epilogue.h, as the 128 x 128 form).
 // RPT: row_phases as a compile-time constant (0: taken from a.rp).  Rows of the packed tile are (channel cl, phase p), p fastest,
 // 128 / rp channels per 128 rows; this workgroup holds rows [h64, h64 + 64) of them, so a channel may straddle the two workgroups of
 // a packed tile (rp = 5: channel 12 is rows 60 .. 64): each emits the samples whose rows it owns.
@@ -64,9 +64,8 @@ __device__ __forceinline__ void gp_epilogue(const ConvArgs& a, const float* tile
   const int nq = (cl_hi - cl_lo + 1) * QPR;
   const long long u_tot = n_total * rp;                   // outputs per (clip | batch) row
   const long long u0 = (long long)n0 * rp;
-  const bool al_ok = (a.y_cs & 3) == 0 && (a.y_bs & 3) == 0 && (!a.y || (reinterpret_cast<unsigned long long>(a.y) & 15) == 0) &&
-                     (!a.y2 || (reinterpret_cast<unsigned long long>(a.y2) & 15) == 0) &&
-                     (!a.res || (reinterpret_cast<unsigned long long>(a.res) & 15) == 0) && (!flat || (a.T_out & 3) == 0);
+  const bool al_ok = epi_vec_ok(a.y, a.y2, a.res, a.y_cs, a.y_bs) && (!flat || (a.T_out & 3) == 0);
+  const bool has_alpha = a.alpha_out != nullptr;
   for (int q = tid; q < nq; q += 256) {
     const int cq = q / QPR, uq = q - cq * QPR;
     const int cl = cl_lo + cq;
@@ -74,85 +73,43 @@ __device__ __forceinline__ void gp_epilogue(const ConvArgs& a, const float* tile
     const long long u = u0 + 4 * uq;
     if (co >= a.C_out || u >= u_tot) continue;
     float v[4];
-    bool own[4] = {true, true, true, true};
+    unsigned own = 15u;                                    // samples whose tile rows this workgroup holds
     if (RPT == 1) {
       const float4 av = *reinterpret_cast<const float4*>(tile + (cl - h64) * EP + 4 * uq);
       v[0] = av.x; v[1] = av.y; v[2] = av.z; v[3] = av.w;
     } else {
+      own = 0u;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ul = 4 * uq + i, tl = ul / rp, p = ul - tl * rp;
         const int lr = cl * rp + p - h64;
-        own[i] = lr >= 0 && lr < GP_ROWS;
-        v[i] = own[i] ? tile[lr * EP + tl] : 0.f;
+        const bool mine = lr >= 0 && lr < GP_ROWS;
+        own |= (unsigned)mine << i;
+        v[i] = mine ? tile[lr * EP + tl] : 0.f;
       }
     }
-    const bool own_all = own[0] && own[1] && own[2] && own[3];
+    const EpiRow row = epi_row_load(true, co, a.bias, a.alpha_out, a.y2 ? a.alpha2 : nullptr);
     // output address of sample u (flat: u -> (clip, time); a quad never straddles clips when T_out % 4 == 0)
     long long o, lim = u_tot - u;
     if (flat) {
       const long long bb = u / a.T_out, tt = u - bb * a.T_out;
       o = bb * a.y_bs + (long long)co * a.y_cs + tt;
-      const long long in_clip = a.T_out - tt;
-      lim = lim < in_clip ? lim : in_clip;
+      lim = lim < a.T_out - tt ? lim : a.T_out - tt;
+      if (lim < 4) {
+        // ragged quad of the flattened layout (T_out % 4 != 0): sample by sample, each with its own (clip, time)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long ui = u + i;
+          if (ui >= u_tot || !(own >> i & 1)) continue;
+          const long long bi = ui / a.T_out, ti = ui - bi * a.T_out;
+          epi_one(v[i], row, has_alpha, a.act, a.y, a.y2, a.res, bi * a.y_bs + (long long)co * a.y_cs + ti);
+        }
+        continue;
+      }
     } else {
       o = (long long)b * a.y_bs + (long long)co * a.y_cs + u;
     }
-    const bool full = al_ok && lim >= 4 && own_all;
-    const float bs = a.bias ? a.bias[co] : 0.f;
-    const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-    const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-    if (flat && lim < 4) {
-      // ragged quad of the flattened layout (T_out % 4 != 0): sample by sample
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long long ui = u + i;
-        if (ui >= u_tot || !own[i]) continue;
-        const long long bb = ui / a.T_out, tt = ui - bb * a.T_out;
-        const long long oi = bb * a.y_bs + (long long)co * a.y_cs + tt;
-        float x = v[i] + bs;
-        if (a.alpha_out) x = snake_apply(x, al, inv);
-        if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-        if (a.res) x += a.res[oi];
-        if (a.y) a.y[oi] = x;
-        if (a.y2) { const float a2 = a.alpha2[co]; a.y2[oi] = snake_apply(x, a2, snake_inv(a2)); }
-      }
-      continue;
-    }
-    float rv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (a.res) {
-      if (full) {
-        const float4 r4 = *reinterpret_cast<const float4*>(a.res + o);
-        rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rv[i] = (i < lim && own[i]) ? a.res[o + i] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float x = v[i] + bs;
-      if (a.alpha_out) x = snake_apply(x, al, inv);
-      if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-      v[i] = x + rv[i];
-    }
-    float w[4] = {0.f, 0.f, 0.f, 0.f};
-    if (a.y2) {
-      const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
-    }
-    if (full) {
-      if (a.y) *reinterpret_cast<float4*>(a.y + o) = make_float4(v[0], v[1], v[2], v[3]);
-      if (a.y2) *reinterpret_cast<float4*>(a.y2 + o) = make_float4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (i >= lim || !own[i]) continue;
-        if (a.y) a.y[o + i] = v[i];
-        if (a.y2) a.y2[o + i] = w[i];
-      }
-    }
+    epi_quad(v, row, has_alpha, a.act, a.y, a.y2, a.res, o, 1, epi_first(lim) & own, al_ok && lim >= 4 && own == 15u);
   }
 }
 

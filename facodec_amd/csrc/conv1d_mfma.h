@@ -23,6 +23,7 @@
 // and the compiler can run the ds_reads ahead of the MFMAs.
 #pragma once
 #include "common.h"
+#include "conv1d_epilogue.h"
 
 namespace fac {
 
@@ -513,10 +514,8 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? CONV_WPE : 3)) 
     float* yg = a.y ? a.y + (long long)b * a.y_bs : nullptr;
     float* y2g = a.y2 ? a.y2 + (long long)b * a.y_bs : nullptr;
     const float* rg = a.res ? a.res + (long long)b * a.y_bs : nullptr;
-    const bool vec_ok = a.y_tstride == 1 && (a.y_cs & 3) == 0 && (a.y_bs & 3) == 0 &&
-                        (!yg || (reinterpret_cast<unsigned long long>(a.y) & 15) == 0) &&
-                        (!y2g || (reinterpret_cast<unsigned long long>(a.y2) & 15) == 0) &&
-                        (!rg || (reinterpret_cast<unsigned long long>(a.res) & 15) == 0);
+    const bool vec_ok = a.y_tstride == 1 && epi_vec_ok(a.y, a.y2, a.res, a.y_cs, a.y_bs);
+    const bool has_alpha = a.alpha_out != nullptr;
     if (a.rp > 1) {
       // ---- all-phases transposed conv: tile rows = (channel cl, phase p), p fastest; a lane emits four CONSECUTIVE output
       // samples u = t * rp + p of one channel (gathered from rp rows of the accumulator tile), so y / y2 leave as 16-byte
@@ -536,40 +535,8 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? CONV_WPE : 3)) 
           const int ul = 4 * uq + i, tl = ul / rp, p = ul - tl * rp;
           v[i] = smem[(cl * rp + p) * EP + tl];
         }
-        const float bs = a.bias ? a.bias[co] : 0.f;
-        const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-        const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-        const long long o = (long long)co * a.y_cs + u;
-        const bool full = vec_ok && u + 3 < T_tot;
-        float rv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (rg) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) rv[i] = u + i < T_tot ? rg[o + i] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float x = v[i] + bs;
-          if (a.alpha_out) x = snake_apply(x, al, inv);
-          if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-          v[i] = x + rv[i];
-        }
-        float w[4] = {0.f, 0.f, 0.f, 0.f};
-        if (y2g) {
-          const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
-        }
-        if (full) {
-          if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0], v[1], v[2], v[3]);
-          if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w[0], w[1], w[2], w[3]);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if (u + i >= T_tot) continue;
-            if (yg) yg[o + i] = v[i];
-            if (y2g) y2g[o + i] = w[i];
-          }
-        }
+        epi_quad(v, epi_row_load(true, co, a.bias, a.alpha_out, y2g ? a.alpha2 : nullptr), has_alpha, a.act, yg, y2g, rg,
+                 (long long)co * a.y_cs + u, 1, epi_first(T_tot - u), vec_ok && u + 3 < T_tot);
       }
     } else
     for (int q = tid; q < CO_TILE * QPR; q += NTH) {
@@ -578,45 +545,8 @@ __global__ __launch_bounds__((WM * WN + 4) * 64, (WM * WN == 4 ? CONV_WPE : 3)) 
       if (co >= a.C_out || t >= a.T_out) continue;
       const float4 av = *reinterpret_cast<const float4*>(smem + row * EP + 4 * tq);
       float v[4] = {av.x, av.y, av.z, av.w};
-      const float bs = a.bias ? a.bias[co] : 0.f;
-      const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-      const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-      const long long o = (long long)co * a.y_cs + (long long)t * a.y_tstride + y_off;
-      const bool full = vec_ok && t + 3 < a.T_out;
-      float rv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (rg) {
-        if (full) {
-          const float4 r4 = *reinterpret_cast<const float4*>(rg + o);
-          rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) rv[i] = t + i < a.T_out ? rg[o + (long long)i * a.y_tstride] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float x = v[i] + bs;
-        if (a.alpha_out) x = snake_apply(x, al, inv);
-        if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-        v[i] = x + rv[i];
-      }
-      float w[4] = {0.f, 0.f, 0.f, 0.f};
-      if (y2g) {
-        const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = snake_apply(v[i], a2, i2);
-      }
-      if (full) {
-        if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w[0], w[1], w[2], w[3]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (t + i >= a.T_out) continue;
-          if (yg) yg[o + (long long)i * a.y_tstride] = v[i];
-          if (y2g) y2g[o + (long long)i * a.y_tstride] = w[i];
-        }
-      }
+      epi_quad(v, epi_row_load(true, co, a.bias, a.alpha_out, y2g ? a.alpha2 : nullptr), has_alpha, a.act, yg, y2g, rg,
+               (long long)co * a.y_cs + (long long)t * a.y_tstride + y_off, a.y_tstride, epi_first(a.T_out - t), vec_ok && t + 3 < a.T_out);
     }
   }
 }

@@ -178,9 +178,7 @@ __global__ __launch_bounds__(256) void conv1d_cin1_kernel(ConvArgs a) {
   const float win[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
   float* yg = a.y ? a.y + (long long)b * a.y_bs : nullptr;
   float* y2g = a.y2 ? a.y2 + (long long)b * a.y_bs : nullptr;
-  const bool full = t + 3 < a.T_out && (a.y_cs & 3) == 0 && (a.y_bs & 3) == 0 &&
-                    (!yg || (reinterpret_cast<unsigned long long>(a.y) & 15) == 0) &&
-                    (!y2g || (reinterpret_cast<unsigned long long>(a.y2) & 15) == 0);
+  const bool full = t + 3 < a.T_out && epi_vec_ok(a.y, a.y2, nullptr, a.y_cs, a.y_bs);
   for (int co = 0; co < a.C_out; ++co) {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -190,34 +188,8 @@ __global__ __launch_bounds__(256) void conv1d_cin1_kernel(ConvArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = fmaf(w, win[k + j], v[j]);
     }
-    const float bs = a.bias ? a.bias[co] : 0.f;
-    const float al = a.alpha_out ? a.alpha_out[co] : 0.f;
-    const float inv = a.alpha_out ? snake_inv(al) : 0.f;
-    float w2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float x = v[j] + bs;
-      if (a.alpha_out) x = snake_apply(x, al, inv);
-      if (a.act != FAC_ACT_NONE) x = apply_act_slow(x, a.act);
-      v[j] = x;
-    }
-    if (y2g) {
-      const float a2 = a.alpha2[co], i2 = snake_inv(a2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w2[j] = snake_apply(v[j], a2, i2);
-    }
-    const long long o = (long long)co * a.y_cs + t;
-    if (full) {
-      if (yg) *reinterpret_cast<float4*>(yg + o) = make_float4(v[0], v[1], v[2], v[3]);
-      if (y2g) *reinterpret_cast<float4*>(y2g + o) = make_float4(w2[0], w2[1], w2[2], w2[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (t + j >= a.T_out) continue;
-        if (yg) yg[o + j] = v[j];
-        if (y2g) y2g[o + j] = w2[j];
-      }
-    }
+    epi_quad<false>(v, epi_row_load(true, co, a.bias, a.alpha_out, y2g ? a.alpha2 : nullptr), a.alpha_out != nullptr, a.act, yg, y2g,
+                    nullptr, (long long)co * a.y_cs + t, 1, epi_first(a.T_out - t), full);
   }
 }
 

@@ -36,14 +36,9 @@ struct SkinnyGeom {
   int co_tiles;
 };
 
-// element e of a 128 x 32 tile (e = m*1024 + r*64 + lane: accumulator m, MFMA register r, lane) -> output
-__device__ __forceinline__ void skinny_emit(const ConvArgs& a, int e, float v, int co0, int cb, int phase, int ncol) {
-  const int ln = e & 63, ri = (e >> 6) & 15, m = e >> 10;
-  const int co = co0 + 4 * ((ri & 3) + 8 * (ri >> 2) + 4 * (ln >> 5)) + m;
-  const int c2 = cb * 32 + (ln & 31);
-  if (co >= a.C_out || c2 >= ncol) return;
-  const int b2 = c2 / a.T_out, t2 = c2 - b2 * a.T_out;
-  v += a.bias ? a.bias[co] : 0.f;
+// What both kernels end in, for one output whose bias is already in v: the two halves of FAC_ACT_WN_RES_SKIP, or the epilogue of
+// conv1d_epilogue.h.
+__device__ __forceinline__ void skinny_tail(const ConvArgs& a, float v, int co, int b2, int t2, int phase) {
   if (a.act == FAC_ACT_WN_RES_SKIP) {        // first half: x += rs (res = x, may alias y); second half: out (= y2) += rs
     const int half = a.C_out >> 1;
     if (co < half) {
@@ -55,12 +50,20 @@ __device__ __forceinline__ void skinny_emit(const ConvArgs& a, int e, float v, i
     }
     return;
   }
-  if (a.alpha_out) { const float al = a.alpha_out[co]; v = snake_apply(v, al, snake_inv(al)); }
-  if (a.act != FAC_ACT_NONE) v = apply_act_slow(v, a.act);
-  const long long o = (long long)b2 * a.y_bs + (long long)co * a.y_cs + (long long)t2 * a.y_tstride + phase;
-  if (a.res) v += a.res[o];
-  if (a.y) a.y[o] = v;
-  if (a.y2) { const float al2 = a.alpha2[co]; a.y2[o] = snake_apply(v, al2, snake_inv(al2)); }
+  EpiRow row = epi_row_load(true, co, nullptr, a.alpha_out, a.y2 ? a.alpha2 : nullptr);
+  row.bs = -0.f;                             // the bias is in v: v + -0.f is v for every v (+0.f would turn -0.f into +0.f)
+  epi_one(v, row, a.alpha_out != nullptr, a.act, a.y, a.y2, a.res,
+          (long long)b2 * a.y_bs + (long long)co * a.y_cs + (long long)t2 * a.y_tstride + phase);
+}
+
+// element e of a 128 x 32 tile (e = m*1024 + r*64 + lane: accumulator m, MFMA register r, lane) -> output
+__device__ __forceinline__ void skinny_emit(const ConvArgs& a, int e, float v, int co0, int cb, int phase, int ncol) {
+  const int ln = e & 63, ri = (e >> 6) & 15, m = e >> 10;
+  const int co = co0 + 4 * ((ri & 3) + 8 * (ri >> 2) + 4 * (ln >> 5)) + m;
+  const int c2 = cb * 32 + (ln & 31);
+  if (co >= a.C_out || c2 >= ncol) return;
+  const int b2 = c2 / a.T_out, t2 = c2 - b2 * a.T_out;
+  skinny_tail(a, v + (a.bias ? a.bias[co] : 0.f), co, b2, t2, phase);
 }
 
 // U = weight rows a wave has in flight per round trip (one float4 + one B value per lane each)
@@ -333,22 +336,7 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvArgs a) {
     a.y[(long long)b2 * a.y_bs + (long long)co * a.y_cs + t2] = __fmul_rn(tanhf(v), sigmoid_f(sv));
     return;
   }
-  const long long o = (long long)b2 * a.y_bs + (long long)co * a.y_cs + (long long)t2 * a.y_tstride + phase;
-  if (a.act == FAC_ACT_WN_RES_SKIP) {
-    if (co < half) {
-      const long long o = (long long)b2 * a.y_bs + (long long)co * a.y_cs + t2;
-      a.y[o] = __fadd_rn(a.res[o], v);
-    } else {
-      const long long o = (long long)b2 * a.y_bs + (long long)(co - half) * a.y_cs + t2;
-      a.y2[o] = __fadd_rn(a.y2[o], v);
-    }
-    return;
-  }
-  if (a.alpha_out) { const float al = a.alpha_out[co]; v = snake_apply(v, al, snake_inv(al)); }
-  if (a.act != FAC_ACT_NONE) v = apply_act_slow(v, a.act);
-  if (a.res) v += a.res[o];
-  if (a.y) a.y[o] = v;
-  if (a.y2) { const float al2 = a.alpha2[co]; a.y2[o] = snake_apply(v, al2, snake_inv(al2)); }
+  skinny_tail(a, v, co, b2, t2, phase);
 }
 
 // 8 or 4 channels per workgroup, or 0: not a shape for this kernel

@@ -1,5 +1,6 @@
 """The forward conv (ops.conv1d / ops.conv1d_flat -> fac_conv1d_fwd) against float64: the Snake prologue and every fused epilogue,
-kernel by kernel.
+kernel by kernel.  The kernels whose accumulators reach all waves through an fp32 tile share one epilogue (conv1d_epilogue.h); the
+table still names every kernel family, because the gather of the quad, the output address and the ownership of a sample differ.
 
 One table (BASES x the operand / alignment variants each kernel admits -> CASES) names, for every case, the weight layout, the
 operands and the kernel fac_conv1d_variant must name; the CPU-only tests walk it without a GPU, the GPU test runs it.  Weights are
@@ -52,6 +53,9 @@ The fused ResidualUnit keeps h = snake(conv7 + b7) in registers, so it is held t
 #   1.1e-7 / 8.6e-8 (tanh 7.9e-8 / 3.0e-8), pw 9.8e-8 / 8.4e-8, pws 6.1e-8 / 5.5e-8, pwt 1.2e-7 / 1.0e-7, narrow 7.1e-8 / 3.0e-8, thin 7.2e-8 / 3.0e-8, cin1
 #   8.3e-8 / 3.3e-8, split reduction 9.7e-8 / 5.4e-8 (log-mel), single launch 2.8e-7 / 8.3e-8; fused ResidualUnit y2 9.2e-8 / 7.8e-8.
 #   The `y` of every launch that adds only alpha_y2 was bit-identical to the plain launch's: no kernel needed the composite bound.
+# Ragged flattened quads (test_ragged_flattened_quads_against_fp64), measured on the commit before conv1d_epilogue.h and again with it,
+# the same figures on the 128 x 128 and on the 64 x 128 form: Step A 0.104 of the bound; Step B full y 9.1e-8 / 9.1e-8, y2 1.0e-7 /
+# 9.7e-8, tanh_res 6.6e-8 / 6.6e-8; the `y` of the launch that adds only alpha_y2 bit-identical to the plain launch's.
 # Split against fp32 route (max error / max |c64|), 25 pairs: split 1.3e-7 .. 6.8e-7, fp32 1.8e-7 .. 9.9e-7; worst pair 4.8e-7
 # against 3.8e-7 (96-row split taps), next 6.8e-7 against 6.4e-7 (split GEMM, k = 2).
 # Wall time of this file's GPU tests together with tests/test_convtr_fwd.py: 48 s for 489 cases, the slowest 2.3 s (the streaming
@@ -116,7 +120,9 @@ def _b(name, B, ci, co, T, T_odd, k, s=1, d=1, mode=REFLECT, causal=True, layout
     return Base(name, B, ci, co, T, T_odd, k, s, d, mode, causal, layout, rows, k1, dil2, kern, form, prologue, admits, pw_split, flat, lowplane)
 
 
-# The epilogue forms of the sources, each written out separately (conv1d_mfma.h has three; row_phases is tests/test_convtr_fwd.py's)
+# The epilogue forms of the sources.  mfma_all_waves, gemm_split, bsplit2 and cin1 call the one quad epilogue of conv1d_epilogue.h
+# (skinny and gemv its one-sample form) around gathers and address arithmetic of their own; bsplit (packed pairs), mfma_per_wave and
+# the streaming and VALU kernels each keep theirs (conv1d_mfma.h has three forms; row_phases is tests/test_convtr_fwd.py's)
 FORMS = {"mfma_per_wave", "mfma_all_waves", "bsplit", "bsplit2", "gemm_split", "pw", "pws", "pwt", "narrow", "thin", "cin1", "skinny", "gemv"}
 
 BASES = [
@@ -710,6 +716,67 @@ def test_conv_fwd_epilogue_against_fp64(cid, cuda):
     if o.y2:
         y2_64 = snake(y.double(), inp.alpha_y2)
         _bar(f"conv_fwd_map_{cid}_y2", y2, y2_64, snake(y, inp.alpha_y2), scale=_channel_scale(y2_64))
+
+
+# ------------------------------------------------------------------------------------------------ ragged flattened quads
+@functools.lru_cache(maxsize=1)
+def _ragged_flat_inputs():
+    """The shape of test_gemm_split_p8_fragments.test_k1_flattened: K = 1, B 3, C_in 72 (ragged last chunk), C_out 136, T 347 =
+    1 041 flattened columns, T % 4 = 3: quads straddle the clip boundaries and the last tile is ragged.  (inputs, c64, mag)."""
+    B, ci, co, T = 3, 72, 136, 347
+    gen = torch.Generator().manual_seed(4700)
+    x = torch.randn(B, ci, T, generator=gen)
+    w = torch.randn(co, ci, 1, generator=gen) / ci ** 0.5
+    bias = torch.randn(co, generator=gen) * 0.5
+    alpha_out, alpha_y2 = _alpha(co, gen), _alpha(co, gen)
+    w[1] *= 1e6                                                 # the row whose alphas are 1e-6
+    res = torch.randn(B, co, T, generator=gen)
+    c64 = F.conv1d(x.double(), w.double()) + bias.double().view(1, -1, 1)
+    mag = F.conv1d(x.double().abs(), w.double().abs()) + bias.double().abs().view(1, -1, 1)
+    return Inputs(x, w, bias, None, alpha_out, alpha_y2, res), c64, mag
+
+
+@gpu
+@pytest.mark.parametrize("cols,tile", [(-1, " 128x128 "), (128, " 64x128 ")], ids=["128x128", "64x128"])
+def test_ragged_flattened_quads_against_fp64(cols, tile, cuda, monkeypatch):
+    """The sample-by-sample branch of the two split-GEMM forms (flattened quads that end inside a clip) against float64, on P8 planes:
+    the 128 x 128 form and the 64 x 128 form, whose row ownership mask is live at 136 rows.  Both forms call one helper
+    (conv1d_epilogue.h), so their equality (test_gemm_split_p8_fragments) says nothing about it.  Step A and Step B as above."""
+    inp, c64, mag = _ragged_flat_inputs()
+    co, ci = inp.w.shape[0], inp.w.shape[1]
+    T = inp.x.shape[-1]
+    assert T % 4 == 3
+    monkeypatch.setattr(ops, "GSPLIT_P8_COLS", cols)
+    ws = ops.pack_gemm_weight_split(inp.w.to(cuda))
+    p8 = ops.to_p8(inp.x.to(cuda))
+
+    def launch(o):
+        with _Spy() as spy:
+            got = ops.conv1d(p8, None, co, 1, pad_left=0, pad_mode=ZERO, t_out=T, w_split=ws, bias=inp.bias.to(cuda),
+                             alpha_out=inp.alpha_out.to(cuda) if o.aout else None, act=o.act, res=inp.res.to(cuda) if o.res else None,
+                             alpha_y2=inp.alpha_y2.to(cuda) if o.y2 else None)
+            torch.cuda.synchronize()
+        assert len(spy.launched) == 1
+        name = ops.conv_variant(spy.launched[0])[1]
+        assert "conv1d_gemm_split_kernel<1>" in name and tile in name, name
+        y, y2 = got if o.y2 else (got, None)
+        return y.cpu(), (y2.cpu() if y2 is not None else None)
+
+    c_gpu, _ = launch(OPS["plain"])
+    assert c_gpu.shape == c64.shape
+    _sum_bound(f"conv_fwd_sum_ragged_flat_{cols}", c_gpu, c64, mag, ci, extra=3.0)
+    y, _ = launch(OPS["y2"])
+    assert torch.equal(y, c_gpu), "the launch with alpha_y2 does not share the plain launch's accumulator bits"
+    for oname in ("full", "tanh_res"):
+        o = OPS[oname]
+        y, y2 = launch(o)
+        alpha_out = inp.alpha_out if o.aout else None
+        r64 = epilogue_ref(c_gpu, alpha_out, o.act, inp.res, torch.float64)
+        r32 = epilogue_ref(c_gpu, alpha_out, o.act, inp.res, torch.float32)
+        _bar(f"conv_fwd_map_ragged_flat_{cols}_{oname}_y", y, r64, r32, scale=_channel_scale(r64))
+        if o.y2:
+            y2_64 = snake(y.double(), inp.alpha_y2)
+            _bar(f"conv_fwd_map_ragged_flat_{cols}_{oname}_y2", y2, y2_64, snake(y, inp.alpha_y2), scale=_channel_scale(y2_64))
 
 
 # ------------------------------------------------------------------------------------------------ fused ResidualUnit
