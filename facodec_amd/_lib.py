@@ -101,6 +101,27 @@ class VadDecideDesc(C.Structure):
     ]
 
 
+AGC_MAX_WINDOW, AGC_MAX_LOOKAHEAD = 1024, 1024       # FAC_AGC_MAX_WINDOW, FAC_AGC_MAX_LOOKAHEAD
+
+
+class AgcGainsDesc(C.Structure):
+    _fields_ = [
+        ("e", _p), ("lens", _p), ("j_start", _p), ("G", _p), ("g", _p),
+        ("e_bs", _i64), ("g_bs", _i64), ("j0", _i64),
+        ("target_db", C.c_double), ("max_boost_db", C.c_double), ("max_cut_db", C.c_double),
+        ("B", C.c_int32), ("n_new", C.c_int32), ("R", C.c_int32), ("W", C.c_int32), ("S", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class AgcApplyDesc(C.Structure):
+    _fields_ = [
+        ("carry_in", _p), ("carry_out", _p), ("x", _p), ("lens", _p), ("j_start", _p), ("g", _p), ("y", _p),
+        ("x_bs", _i64), ("g_bs", _i64), ("y_bs", _i64), ("n0", _i64),
+        ("ceiling", C.c_double),
+        ("B", C.c_int32), ("k", C.c_int32), ("n_out", C.c_int32), ("S", C.c_int32), ("LA", C.c_int32), ("R", C.c_int32),
+    ]
+
+
 class SidApplyDesc(C.Structure):
     _fields_ = [
         ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3), ("n_q", C.c_int32 * 3), ("B", C.c_int32),
@@ -286,6 +307,10 @@ SIGNATURES = {
     "fac_vad_decide": (_i, [C.POINTER(VadDecideDesc), _p]),
     "fac_vad_take": (_i, [_p, _i64, _i, _i64, _i, _p, _i64, _i, _p]),
     "fac_sid_apply": (_i, [C.POINTER(SidApplyDesc), _p]),
+    "fac_agc_gains": (_i, [C.POINTER(AgcGainsDesc), _p]),
+    "fac_agc_apply": (_i, [C.POINTER(AgcApplyDesc), _p]),
+    "fac_true_peak_ws_bytes": (_i64, [_i, _i]),
+    "fac_true_peak": (_i, [C.POINTER(ResampleDesc), _p, _p, _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),
     "fac_codes_unpack": (_i, [C.POINTER(CodesUnpackDesc), _p]),
     "fac_codes_row_bytes": (_i64, [_i, _i, _i]),

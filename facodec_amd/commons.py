@@ -785,6 +785,35 @@ def loudness_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SA
     return out
 
 
+@torch.no_grad()
+def level_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SAMPLES, **parameters):
+    """Causal level control (ops.level) of clips of different lengths -> per clip, in the caller's order,
+    ops.Levelled(y (T_i + lookahead,) float32, G (T_i // S,) float64 dB, g (T_i // S,) float64), on the device.  The clips (T_i,)
+    or (1, T_i), float32 on the GPU at sample_rate (a multiple of 10), go through plan_groups' zero-padded groups with their
+    lengths: one ops.level call (three C calls) per group, nothing is read back; a clip comes out as the single-clip call gives
+    it, whatever it is grouped with.  **parameters: ops.level's target_db, window, max_boost_db, max_cut_db,
+    ceiling_db, lookahead -- whose defaults were not tuned by listening."""
+    from . import ops
+    p = ops.agc_params(sample_rate, **parameters)                   # ValueError: the rate, the parameters
+    waves = list(waves)
+    if not waves:
+        return []
+    _need_gpu(waves, "clips")
+    for w in waves:
+        if not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = [int(w.shape[-1]) for w in waves]
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), batch.device)
+        r = ops.level(batch, sample_rate, lens=lens, **parameters)
+        for j, i in enumerate(group):
+            n = lengths[i] // p.S
+            out[i] = ops.Levelled(r.y[j, :lengths[i] + p.LA], r.G[j, :n], r.g[j, :n])
+    return out
+
+
 def active_segments(flags, frame, length):
     """flags: one clip's 0 / 1 frame flags (host sequence) -> [(start_sample, end_sample)] of its runs of active frames, the last
     end clipped to the clip's length.  Host only."""

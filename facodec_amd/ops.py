@@ -1843,6 +1843,167 @@ def normalize_loudness(x, target_db=-16.0, rate=24000, lens=None):
     return y, L, g
 
 
+# --------------------------------------------------------------------------------- level control
+AgcParams = namedtuple("AgcParams", "S W target_db max_boost_db max_cut_db ceiling LA")
+Levelled = namedtuple("Levelled", "y G g")
+
+
+def agc_params(rate=24000, target_db=-23.0, window=30, max_boost_db=30.0, max_cut_db=30.0, ceiling_db=-1.0, lookahead=120):
+    """-> AgcParams(S, W, target_db, max_boost_db, max_cut_db, ceiling, LA) of fac_agc_gains / fac_agc_apply: S = rate / 10, the
+    window in sub-blocks of 100 ms, ceiling = 10 ** (ceiling_db / 20) (linear, a Python float: the kernel and a restatement of
+    it take the same bits), the look-ahead in samples.  The defaults -- a 3 s window levelled to -23 LUFS, +-30 dB of gain, a
+    sample-peak ceiling of -1 dBFS 5 ms ahead -- were not tuned by listening."""
+    S = _kweight_tables(rate)[0]                                    # ValueError: the rate
+    W, LA = int(window), int(lookahead)
+    if not 4 <= W <= _lib.AGC_MAX_WINDOW:
+        raise ValueError(f"agc: window = {W} outside 4 .. {_lib.AGC_MAX_WINDOW} sub-blocks")
+    if not 1 <= LA <= _lib.AGC_MAX_LOOKAHEAD:
+        raise ValueError(f"agc: lookahead = {LA} outside 1 .. {_lib.AGC_MAX_LOOKAHEAD} samples")
+    target_db, max_boost_db, max_cut_db = float(target_db), float(max_boost_db), float(max_cut_db)
+    if not (math.isfinite(target_db) and 0.0 <= max_boost_db < math.inf and 0.0 <= max_cut_db < math.inf):
+        raise ValueError(f"agc: target_db = {target_db}, max_boost_db = {max_boost_db}, max_cut_db = {max_cut_db} (finite, limits not negative)")
+    ceiling = 10.0 ** (float(ceiling_db) / 20.0)
+    if not 0.0 < ceiling < math.inf:
+        raise ValueError(f"agc: ceiling_db = {ceiling_db}")
+    return AgcParams(S, W, target_db, max_boost_db, max_cut_db, ceiling, LA)
+
+
+def _f64_rows(t, B, n, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < n \
+            or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what} must be float64 ({B}, >= {n}) on the GPU with dense rows, got {getattr(t, 'dtype', type(t))} "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+    return t
+
+
+def _i64_rows(t, B, what):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or tuple(t.shape) != (B,) or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous int64 ({B},) on the GPU")
+    return t
+
+
+def agc_gains(e, p, j0=0, n_new=None, R=None, lens=None, j_start=None, G=None, g=None):
+    """fac_agc_gains over the sub-block energies e (B, >= R) float64 (sub-block j at column j % R; a plain array is R = its
+    width, j0 = 0) with p = agc_params(...): the gains of sub-blocks j0 .. j0 + n_new - 1 -> (G dB, g linear), float64 (B, R)
+    written at columns j % R (allocated when not given).  lens (B,) int32: the rows' lengths in samples, sub-blocks that are
+    not complete get G = 0, g = 1.  j_start (B,) int64: the first sub-block of every row's current stream."""
+    if not isinstance(e, torch.Tensor) or not e.is_cuda:
+        raise _lib.FacodecHipError(f"agc_gains: e must live on the GPU (got {getattr(e, 'device', type(e))}); there is no CPU path")
+    B = e.shape[0]
+    R = e.shape[1] if R is None else int(R)
+    n_new = R - int(j0) if n_new is None else int(n_new)
+    e = _f64_rows(e, B, R, "agc_gains: e")
+    if G is None:
+        G = torch.zeros(B, R, device=e.device, dtype=torch.float64)
+    if g is None:
+        g = torch.ones(B, R, device=e.device, dtype=torch.float64)
+    G, g = _f64_rows(G, B, R, "agc_gains: G"), _f64_rows(g, B, R, "agc_gains: g")
+    if G.stride(0) != g.stride(0) and B > 1:
+        raise ValueError("agc_gains: G and g must have the same row pitch")
+    if B == 0 or n_new == 0:
+        return G, g
+    d = _lib.AgcGainsDesc()
+    d.e, d.lens = e.data_ptr(), (_lens(lens, B).data_ptr() if lens is not None else None)
+    j_start = _i64_rows(j_start, B, "agc_gains: j_start")
+    d.j_start = j_start.data_ptr() if j_start is not None else None
+    d.G, d.g = G.data_ptr(), g.data_ptr()
+    d.e_bs, d.g_bs, d.j0 = (e.stride(0) if B > 1 else e.shape[1]), (g.stride(0) if B > 1 else g.shape[1]), int(j0)
+    d.target_db, d.max_boost_db, d.max_cut_db = p.target_db, p.max_boost_db, p.max_cut_db
+    d.B, d.n_new, d.R, d.W, d.S = B, n_new, R, p.W, p.S
+    _lib.check(_lib.load().fac_agc_gains(C.byref(d), _stream()), "fac_agc_gains")
+    return G, g
+
+
+def agc_apply(x, g, p, n0=0, R=None, lens=None, j_start=None, carry_in=None, carry_out=None, flush=True, k=None, out=None):
+    """fac_agc_apply: x (B, k) float32 gained by the ramp between the decided gains g (B, >= R) float64 (g_j at column j % R) and
+    limited to p.ceiling with p.LA samples of look-ahead -> y (B, n_out) float32, n_out = k + LA with flush (the signal ends
+    with this block) and k without; y runs LA samples behind x.  n0: the absolute index of x[:, 0].  carry_in / carry_out
+    (B, 2 LA) float64, two different buffers of a stream; lens (B,) int32 only without them.  k = 0 with flush is the flush of
+    a stream alone (x may be None).  out: a preallocated (B, >= n_out) float32 buffer with dense rows."""
+    if not isinstance(g, torch.Tensor) or not g.is_cuda:
+        raise _lib.FacodecHipError(f"agc_apply: g must live on the GPU (got {getattr(g, 'device', type(g))}); there is no CPU path")
+    if x is not None:
+        x = _rows(x, "agc_apply")
+    B = g.shape[0]
+    k = (x.shape[1] if x is not None else 0) if k is None else int(k)
+    R = g.shape[1] if R is None else int(R)
+    g = _f64_rows(g, B, R, "agc_apply: g")
+    n_out = k + p.LA if flush else k
+    if out is None:
+        out = torch.empty(B, n_out, device=g.device, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_out or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"agc_apply: out must be float32 ({B}, >= {n_out}) on the GPU with dense rows")
+    if B == 0 or n_out == 0:
+        return out[:, :n_out]
+    for t, name in ((carry_in, "carry_in"), (carry_out, "carry_out")):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (B, 2 * p.LA) or not t.is_contiguous()):
+            raise ValueError(f"agc_apply: {name} must be contiguous float64 ({B}, {2 * p.LA}) on the GPU")
+    d = _lib.AgcApplyDesc()
+    d.carry_in = carry_in.data_ptr() if carry_in is not None else None
+    d.carry_out = carry_out.data_ptr() if carry_out is not None else None
+    d.x = x.data_ptr() if x is not None and k > 0 else None
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    j_start = _i64_rows(j_start, B, "agc_apply: j_start")
+    d.j_start = j_start.data_ptr() if j_start is not None else None
+    d.g, d.y = g.data_ptr(), out.data_ptr()
+    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
+    d.g_bs, d.y_bs, d.n0 = (g.stride(0) if B > 1 else g.shape[1]), (out.stride(0) if B > 1 else out.shape[1]), int(n0)
+    d.ceiling = p.ceiling
+    d.B, d.k, d.n_out, d.S, d.LA, d.R = B, k, n_out, p.S, p.LA, R
+    _lib.check(_lib.load().fac_agc_apply(C.byref(d), _stream()), "fac_agc_apply")
+    return out[:, :n_out]
+
+
+def level(x, rate=24000, lens=None, target_db=-23.0, window=30, max_boost_db=30.0, max_cut_db=30.0, ceiling_db=-1.0, lookahead=120):
+    """Causal level control of x (B, T) or (B, 1, T) float32 on the GPU -> Levelled(y (B, T + lookahead) or
+    (B, 1, T + lookahead) float32, G (B, n) float64 dB, g (B, n) float64 linear), n = T // S completed sub-blocks of S = rate / 10
+    samples: what streaming.AutoGain gives for the same signal.  Sub-block j's gain G[:, j] is the clamped distance from
+    target_db of the two-gate BS.1770 loudness of the last `window` sub-blocks up to j; sample n in sub-block j is multiplied by
+    the ramp from g[j - 2] to g[j - 1] (only completed sub-blocks: causal, continuous), then a peak limiter with `lookahead`
+    samples keeps every sample at or under 10 ** (ceiling_db / 20); y is the levelled signal `lookahead` samples late, so row b
+    holds lens[b] + lookahead samples and zeros behind.  Three C calls (fac_kweight_energy, fac_agc_gains, fac_agc_apply), no
+    host read; the arithmetic is pinned in include/facodec_hip.h.  The defaults were not tuned by listening."""
+    p = agc_params(rate, target_db, window, max_boost_db, max_cut_db, ceiling_db, lookahead)
+    x2 = _rows(x, "level")
+    B, T = x2.shape
+    n = T // p.S
+    dev = x2.device
+    if B == 0 or T == 0:
+        y = torch.zeros(B, T + p.LA, device=dev, dtype=torch.float32)
+        G, g = torch.zeros(B, n, device=dev, dtype=torch.float64), torch.ones(B, n, device=dev, dtype=torch.float64)
+    else:
+        en = loudness_energies(x2, rate, lens=lens)
+        G = torch.zeros(B, max(n, 1), device=dev, dtype=torch.float64)
+        g = torch.ones(B, max(n, 1), device=dev, dtype=torch.float64)
+        if n:
+            agc_gains(en.e, p, 0, n, R=n, lens=lens, G=G, g=g)
+        y = agc_apply(x2, g, p, lens=lens, flush=True)
+        G, g = G[:, :n], g[:, :n]
+    return Levelled(y.view(x.shape[:-1] + (T + p.LA,)), G, g)
+
+
+def true_peak(x, rate=24000, lens=None, quality="best"):
+    """True peak of x (B, T) or (B, 1, T) float32 on the GPU -> (B,) float32: max |y| of the signal oversampled 4 x with the
+    project's polyphase filter (dsp.resample_table(rate, 4 rate, quality)), computed without writing the oversampled signal
+    (fac_true_peak: fac_resample's arithmetic and order): equal to resample(x, rate, 4 * rate, lens, quality).abs().amax(-1) bit
+    for bit.  lens (B,) int32 on the device: row b is x[b, :lens[b]].  A meter: the limiter's ceiling is a sample-peak ceiling."""
+    resample_table(rate, 4 * int(rate), quality)                    # ValueError: quality, rate
+    x2 = _rows(x, "true_peak")
+    B, T = x2.shape
+    peak = torch.zeros(B, device=x2.device, dtype=torch.float32)
+    if B == 0 or T == 0:
+        return peak
+    geo, table, offs = _resample_device_table(rate, 4 * int(rate), quality, x2.device)
+    n_out = -(-T * geo["n"] // geo["o"])
+    ws = torch.empty(_lib.load().fac_true_peak_ws_bytes(B, n_out) // 4, device=x2.device, dtype=torch.float32)
+    d = resample_desc(geo, table, offs, x2, x2, n_out, lens=_lens(lens, B) if lens is not None else None)
+    d.y, d.y_bs = None, 0
+    _lib.check(_lib.load().fac_true_peak(C.byref(d), _ptr(peak), _ptr(ws), _stream()), "fac_true_peak")
+    return peak
+
+
 # --------------------------------------------------------------------------------- objective scores (DESIGN.md 27)
 STOI_RATE = 10000
 StoiGeometry = namedtuple("StoiGeometry", "n_frames ws_bytes_per_row energy_frames scan_block band_frames score_segments")

@@ -1068,7 +1068,7 @@ class LoudnessMeter:
     is full, the scratch grows only with the largest block seen.  momentary() is the last 400 ms, short_term() the last 3 s,
     both ungated and counting what lies before the stream's start as silence; integrated() is the two-gate loudness of
     everything pushed so far.  `peak` holds max |x| so far.  A session's caller can level its input with it or watch its output;
-    the sessions themselves do not use it."""
+    the sessions themselves do not use it (AutoGain / LevelledSession below level a session's input)."""
 
     def __init__(self, B, rate=MODEL_RATE, device="cuda", seconds=60):
         self.S = ops._kweight_tables(rate)[0]                 # ValueError: the rate
@@ -1202,6 +1202,158 @@ class VoiceActivity:
             raise ValueError(f"energies({n}): {min(self.frames, self.R)} frames are in the ring")
         idx = torch.arange(self.frames - n, self.frames, device=self.device) % self.R
         return self._e[:, idx]
+
+
+class AutoGain:
+    """Causal level control over B parallel streams, one block at a time:
+
+        agc = AutoGain(B)                                    # rate 24000, -23 LUFS over 3 s, ceiling -1 dBFS, 120 samples ahead
+        y = agc.push(block)                                  # (B, 1, k) or (B, k) float32 on the GPU, any k >= 1 -> the same shape
+        tail = agc.finish()                                  # the last `lookahead` samples
+
+    The pushes and finish(), concatenated, are ops.level of the whole signal: `lookahead` zeros' worth of delay (`latency`
+    seconds), then the levelled signal.  For the same gains the samples are the offline call's bit for bit, for any chunking;
+    the gains themselves agree to fp64 rounding (the K-weighting filter's chunk boundaries move with the blocks, as in
+    LoudnessMeter).  push is at most three launches' worth of C calls -- fac_kweight_energy, carrying the filter state and the
+    position inside the current 100 ms sub-block; fac_agc_gains when the block completes a sub-block; fac_agc_apply, which
+    also moves the last 2 * lookahead gained samples from one carry buffer into the other -- reads nothing back and allocates
+    nothing but its output once the scratch has seen the largest block.  Energies and gains live in device rings of `ring`
+    sub-blocks; a push that crosses the end of the ring (once every ring / 10 seconds), or is longer than ring - window - 2
+    sub-blocks, is run as two or more.  It runs eagerly, outside the sessions' captured graphs.
+
+    reset(rows) restarts the given rows on the device, so that a pool can hand a slot to a new stream: filter state, limiter
+    carry, energies and gains of those rows are cleared and their window and ramp start over at the next line of the 100 ms
+    grid, which all rows share.  Called when `samples` is a multiple of the sub-block (rate / 10), the rows then equal a fresh
+    stream bit for bit; in between, the samples up to the next grid line pass at unit gain and are not measured.  The other
+    rows are not touched.  The defaults were not tuned by listening."""
+
+    def __init__(self, B, rate=MODEL_RATE, target_db=-23.0, window=30, max_boost_db=30.0, max_cut_db=30.0, ceiling_db=-1.0,
+                 lookahead=120, ring=256, device="cuda"):
+        self.p = ops.agc_params(rate, target_db, window, max_boost_db, max_cut_db, ceiling_db, lookahead)
+        self.B, self.rate, self.R, self.device = int(B), int(rate), int(ring), torch.device(device)
+        if self.B < 1:
+            raise ValueError(f"AutoGain: B = {B}")
+        if self.R < self.p.W + 8:
+            raise ValueError(f"AutoGain: ring = {ring} below window + 8 = {self.p.W + 8}")
+        self.S, self.lookahead, self.latency = self.p.S, self.p.LA, self.p.LA / self.rate
+        self.samples = 0
+        f64 = dict(device=self.device, dtype=torch.float64)
+        self._e = torch.zeros(self.B, self.R, **f64)
+        self._G = torch.zeros(self.B, self.R, **f64)
+        self._g = torch.ones(self.B, self.R, **f64)
+        self._state = torch.zeros(self.B, 4, **f64)
+        self._j_start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
+        self._carry = [torch.zeros(self.B, 2 * self.p.LA, **f64) for _ in range(2)]
+        self._cur = 0
+        self.peak = torch.zeros(self.B, device=self.device, dtype=torch.float32)
+        self._ws = None
+        self._done = False
+
+    @property
+    def decided(self):
+        """Sub-blocks whose gain is decided (on the host)."""
+        return self.samples // self.S
+
+    def _run(self, x):
+        k = x.shape[1]
+        j0, offset = divmod(self.samples, self.S)
+        need = ops._lib.load().fac_kweight_ws_bytes(self.B, k)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        ops.loudness_energies(x, self.rate, state=self._state, offset=offset, out=self._e[:, j0 % self.R:], peak=self.peak,
+                              state_out=self._state, ws=self._ws)
+        n_new = (self.samples + k) // self.S - j0
+        if n_new:
+            ops.agc_gains(self._e, self.p, j0, n_new, R=self.R, j_start=self._j_start, G=self._G, g=self._g)
+        src, dst = self._carry[self._cur], self._carry[1 - self._cur]
+        y = ops.agc_apply(x, self._g, self.p, n0=self.samples, R=self.R, j_start=self._j_start, carry_in=src, carry_out=dst, flush=False)
+        self._cur ^= 1
+        self.samples += k
+        return y
+
+    def push(self, block):
+        if self._done:
+            raise RuntimeError("push() after finish()")
+        x = ops._rows(block, "AutoGain.push")
+        if x.shape[0] != self.B or x.shape[1] < 1:
+            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
+        parts, t, k = [], 0, x.shape[1]
+        while t < k:
+            j0, offset = divmod(self.samples, self.S)
+            room = min(self.R - j0 % self.R, self.R - self.p.W - 2) * self.S - offset      # up to the ring's end, and within its reach
+            n = min(k - t, room)
+            parts.append(self._run(x[:, t:t + n]))
+            t += n
+        y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return y.view(block.shape)
+
+    def finish(self):
+        """(B, lookahead) float32: the samples the limiter was still holding back; the stream takes no more audio."""
+        if self._done:
+            raise RuntimeError("finish() twice")
+        self._done = True
+        return ops.agc_apply(None, self._g, self.p, n0=self.samples, R=self.R, j_start=self._j_start, carry_in=self._carry[self._cur],
+                             flush=True, k=0)
+
+    def gains(self, n):
+        """-> (G (B, n) float64 dB, g (B, n) float64 linear) of the last n decided sub-blocks (a copy out of the rings; for tests
+        and meters)."""
+        if not 1 <= n <= min(self.decided, self.R):
+            raise ValueError(f"gains({n}): {min(self.decided, self.R)} decided gains are in the ring")
+        idx = torch.arange(self.decided - n, self.decided, device=self.device) % self.R
+        return self._G[:, idx], self._g[:, idx]
+
+    def reset(self, rows):
+        """Puts the given rows (indices on the host) back into the state of a fresh stream, on the device."""
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.B for r in rows):
+            raise ValueError(f"reset({rows}): rows are 0 .. {self.B - 1}")
+        if not rows:
+            return
+        idx = ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device)
+        for t, v in ((self._state, 0.0), (self._carry[self._cur], 0.0), (self._e, 0.0), (self._G, 0.0), (self._g, 1.0), (self.peak, 0.0)):
+            t.index_fill_(0, idx, v)
+        self._j_start.index_fill_(0, idx, -(-self.samples // self.S))
+
+
+class LevelledSession:
+    """A StreamingCodec, a StreamingConverter or a ResampledSession of one whose input goes through an AutoGain first:
+
+        codec = LevelledSession(StreamingCodec(model, timbre), target_db=-23.0)
+        out = codec.prime(wave[:, :, :4800]); out = codec.push(wave[:, :, t:t + 480]); out = codec.finish()
+
+    Same surface and the same dicts as the wrapped session (whose other attributes read through).  The AutoGain runs at the
+    rate the session takes its audio at, eagerly, around the session's captured graphs: at most three C calls per push.  The
+    session sees `lookahead` zeros and then the levelled input, cut off where the pushed audio ends; `latency_in` is that delay
+    in seconds, on top of the wrapped session's own.  **parameters: AutoGain's (target_db, window, max_boost_db, max_cut_db,
+    ceiling_db, lookahead, ring), whose defaults were not tuned by listening.  The applied gain does not travel with the codes."""
+
+    def __init__(self, session, **parameters):
+        if not hasattr(session, "prime_samples") or not session.prime_samples:
+            raise ValueError("LevelledSession: this session takes codes, not audio")
+        self.session = session
+        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
+        inner = session if hasattr(session, "B") else session.session           # a ResampledSession keeps them on the session it wraps
+        self.agc = AutoGain(inner.B, self.rate, device=inner.device, **parameters)
+        self.lookahead = self.agc.lookahead
+        self.latency_in = self.agc.latency + getattr(session, "latency_in", 0.0)
+
+    def __getattr__(self, name):
+        if name == "session":
+            raise AttributeError(name)
+        return getattr(self.session, name)
+
+    def prime(self, first):
+        return self.session.prime(self.agc.push(first))
+
+    def push(self, hop):
+        return self.session.push(self.agc.push(hop))
+
+    def finish(self):
+        return self.session.finish()
+
+    def set_target(self, timbre):
+        return self.session.set_target(timbre)
 
 
 class ResampledSession:

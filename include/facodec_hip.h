@@ -1250,6 +1250,92 @@ typedef struct fac_sid_apply_desc {
 } fac_sid_apply_desc;
 int fac_sid_apply(const fac_sid_apply_desc* d, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Level control (csrc/agc.hip): a causal automatic gain control on the sub-block energies of fac_kweight_energy, a
+ * look-ahead peak limiter behind it, and a true-peak meter.  This comment is the normative definition.  Finite windows, no
+ * recurrence: a gain depends on the W energies up to its sub-block, an output sample on 2 LA + 1 input samples and two gains.
+ * Unless said otherwise every operation below is one IEEE fp64 operation with one round-to-nearest; nothing is fused.
+ *
+ * fac_agc_gains: S = fs / 10 samples per sub-block; e (B, R) fp64 holds the energy of sub-block j at column j % R (a plain
+ * (B, n) array is R >= n, j0 = 0).  The gains of the n_new sub-blocks j = j0 .. j0 + n_new - 1, each known once its sub-block
+ * is complete.  With js = j_start[b] (0 when j_start is NULL), the first sub-block of the row's current stream:
+ *   lo = max(js, j - W + 1);   the gating blocks inside the window are k = lo .. j - 3, block k = sub-blocks k .. k + 3
+ *   z_k = (((e_k + e_{k+1}) + e_{k+2}) + e_{k+3}) / (4 S);    l_k = -0.691 + 10 log10(z_k), -inf for z_k <= 0
+ *   pass 1, k ascending, both sums from 0.0:  l_k > -70:  A += z_k, nA += 1.     nA = 0: L_j = -70.
+ *   Gr = -0.691 + 10 log10(A / nA) - 10
+ *   pass 2, k ascending, from 0.0:  l_k > -70 and l_k > Gr:  Z += z_k, nZ += 1
+ *   L_j = max(-70, -0.691 + 10 log10(Z / nZ));   L_j = -70 when nZ = 0, when the window holds fewer than 4 sub-blocks (j - lo < 3)
+ *   G_j = 0 for L_j <= -70, else min(max(target_db - L_j, -max_cut_db), max_boost_db);      g_j = pow(10, G_j / 20)
+ * log10 and pow are the device math library's (correct to an ulp or two, not single roundings); everything else is.
+ * lens (B) int32 or NULL: row b holds lens[b] samples, sub-block j is complete when (j + 1) S <= lens[b].  A sub-block that is
+ * not complete, or lies before js, produces no gain: G = 0, g = 1 are stored.  G, g (either may be NULL, not both) fp64 (B, R) of
+ * pitch g_bs, column j % R.  One workgroup of 64 threads per (row, 64 sub-blocks), the tile's energies and its W - 1 older
+ * neighbours in LDS, one thread per gain.
+ * Refused before any launch: a NULL descriptor or e; G and g both NULL; B outside 1 .. 65535; n_new < 1; W outside
+ * 4 .. FAC_AGC_MAX_WINDOW; S < 1; j0 < 0; max_boost_db or max_cut_db negative or not finite, target_db not finite;
+ * R < min(j0 + n_new, W + n_new - 1); e_bs or g_bs below R with B > 1.
+ *
+ * fac_agc_apply: per row the signal is [carry | block]: the block's sample i has the absolute index n = n0 + i, lies in
+ * sub-block j = n / S at position u = n % S, and exists for i < k_b = lens ? clamp(lens[b], 0, k) : k.
+ *   a(n) = g_{j-2} + (g_{j-1} - g_{j-2}) * ((double)(u + 1) / (double)S)      g_i = 1 for i < js (js >= 0): only gains of completed
+ *   v[n] = (double)x[n] * a(n)                                               sub-blocks are used, and the gain is continuous
+ *   v[n] = 0 for samples that do not exist (behind k_b) and before the stream's start; nothing at or behind lens[b] is read
+ * g (B, R) fp64 of pitch g_bs, g_i at column i % R.  The limiter, C = ceiling (linear, fp64, from the host), LA = look-ahead:
+ *   c[n] = |v[n]| > C ? C / |v[n]| : 1
+ *   p[k] = min c[k - LA .. k]                                                (exact in any order)
+ *   s[m] = min( (p[m-LA+1] + p[m-LA+2] + .. + p[m]) / (double)LA, c[m-LA] )   the sum left to right, starting from p[m-LA+1]
+ *   y[m] = (float)( v[m-LA] * s[m] )                                         one fp64 product, one rounding to fp32
+ * Every p in the mean contains c[m-LA], so |y[m]| <= C up to the roundings of the quotient, the mean and the product.  Where no
+ * |v| > C lies in m - 2 LA + 1 .. m, s[m] is exactly 1 and y[m] = (float)v[m-LA].  The output runs LA samples behind the input:
+ * the call writes y[b * y_bs + i] = y[n0 + i], i < n_out, k <= n_out <= k + LA (n_out = k for a block of a stream, k + LA where
+ * the signal ends: row b then holds k_b + LA samples and zeros behind; k = 0, n_out = LA is the flush of a stream, x may be
+ * NULL).
+ *   carry_in (B, 2 LA) fp64, dense: v[n0 - 2 LA .. n0 - 1]; NULL: zeros (the start of a signal)
+ *   carry_out (B, 2 LA), NULL or a buffer OTHER than carry_in: v[n0 + k - 2 LA .. n0 + k - 1], written by one extra workgroup per
+ *   row of the same launch; the host alternates two buffers, so no word is read and written in one launch.
+ * One workgroup of 256 threads per (row, 1024 outputs): v and c of the tile and its 2 LA older neighbours and p in LDS; a tile
+ * none of whose c is below 1 skips the limiter (the same bits).
+ * Refused before any launch: a NULL descriptor, g or y; x NULL with k > 0; B outside 1 .. 65535; k outside 0 .. 2^30; n_out
+ * outside max(k, 1) .. k + LA; S outside 1 .. 2^30; R outside 1 .. 2^28; LA outside 1 .. FAC_AGC_MAX_LOOKAHEAD; ceiling not in (0, inf); n0 < 0; carry_out ==
+ * carry_in; lens with a carry buffer; x_bs < k, y_bs < n_out or g_bs < R with B > 1; R below the gains the block reaches
+ * (R >= min(jl, jl - jf + 2), jf and jl the sub-blocks of the block's first and last sample: g of jf - 2 .. jl - 1 in different
+ * columns; that the ring still holds them is the business of whoever writes it).
+ *
+ * fac_true_peak: peak[b] = max |y| over the outputs of fac_resample for the same descriptor (offline form: hist, hist_out and y
+ * NULL, n_hist = 0, q0 = 0, m_lo = 0, n_out = ceil(T n / o)), without writing y: every output is the same chain of fp32 fmas
+ * in ascending tap order, so the result equals the maximum over fac_resample's output bit for bit.  The maximum itself is
+ * exact in any order.  ws: fac_true_peak_ws_bytes(B, n_out) bytes of device scratch (one partial maximum per row and tile).
+ * ---------------------------------------------------------------------------------------- */
+enum { FAC_AGC_MAX_WINDOW = 1024, FAC_AGC_MAX_LOOKAHEAD = 1024 };
+typedef struct fac_agc_gains_desc {
+  const double* e;          /* (B, R), pitch e_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  const int64_t* j_start;   /* (B) or NULL */
+  double* G;                /* written: (B, R) dB, pitch g_bs; or NULL */
+  double* g;                /* written: (B, R) linear, pitch g_bs; or NULL */
+  int64_t e_bs, g_bs, j0;
+  double target_db, max_boost_db, max_cut_db;
+  int32_t B, n_new, R, W, S, reserved;
+} fac_agc_gains_desc;
+int fac_agc_gains(const fac_agc_gains_desc* d, fac_stream_t stream);
+
+typedef struct fac_agc_apply_desc {
+  const double* carry_in;   /* (B, 2 LA) or NULL */
+  double* carry_out;        /* (B, 2 LA) or NULL, never carry_in */
+  const float* x;           /* (B, k), pitch x_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  const int64_t* j_start;   /* (B) or NULL */
+  const double* g;          /* (B, R), pitch g_bs */
+  float* y;                 /* written: (B, n_out), pitch y_bs */
+  int64_t x_bs, g_bs, y_bs, n0;
+  double ceiling;
+  int32_t B, k, n_out, S, LA, R;
+} fac_agc_apply_desc;
+int fac_agc_apply(const fac_agc_apply_desc* d, fac_stream_t stream);
+
+int64_t fac_true_peak_ws_bytes(int B, int n_out);
+int fac_true_peak(const fac_resample_desc* d, float* peak, void* ws, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
