@@ -122,6 +122,34 @@ class AgcApplyDesc(C.Structure):
     ]
 
 
+NS_N, NS_H, NS_BINS, NS_CARRY, NS_MAX_M, NS_MAX_W = 512, 256, 257, 1023, 64, 256      # FAC_NS_*
+
+
+class NsPowerDesc(C.Structure):
+    _fields_ = [
+        ("carry_in", _p), ("carry_out", _p), ("x", _p), ("lens", _p), ("starts", _p), ("P", _p), ("X", _p),
+        ("x_bs", _i64), ("p_bs", _i64), ("n0", _i64), ("f0", _i64),
+        ("B", C.c_int32), ("k", C.c_int32), ("n_new", C.c_int32), ("R", C.c_int32),
+    ]
+
+
+class NsGainsDesc(C.Structure):
+    _fields_ = [
+        ("P", _p), ("starts", _p), ("G", _p),
+        ("p_bs", _i64), ("g_bs", _i64), ("f0", _i64),
+        ("over", C.c_double), ("g_min", C.c_double),
+        ("B", C.c_int32), ("n_new", C.c_int32), ("R", C.c_int32), ("M", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class NsSynthDesc(C.Structure):
+    _fields_ = [
+        ("carry_in", _p), ("x", _p), ("lens", _p), ("starts", _p), ("G", _p), ("X", _p), ("y", _p),
+        ("x_bs", _i64), ("g_bs", _i64), ("y_bs", _i64), ("n0", _i64), ("m0", _i64),
+        ("B", C.c_int32), ("k", C.c_int32), ("n_out", C.c_int32), ("R", C.c_int32),
+    ]
+
+
 class SidApplyDesc(C.Structure):
     _fields_ = [
         ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3), ("n_q", C.c_int32 * 3), ("B", C.c_int32),
@@ -309,6 +337,9 @@ SIGNATURES = {
     "fac_sid_apply": (_i, [C.POINTER(SidApplyDesc), _p]),
     "fac_agc_gains": (_i, [C.POINTER(AgcGainsDesc), _p]),
     "fac_agc_apply": (_i, [C.POINTER(AgcApplyDesc), _p]),
+    "fac_ns_power": (_i, [C.POINTER(NsPowerDesc), _p]),
+    "fac_ns_gains": (_i, [C.POINTER(NsGainsDesc), _p]),
+    "fac_ns_synth": (_i, [C.POINTER(NsSynthDesc), _p]),
     "fac_true_peak_ws_bytes": (_i64, [_i, _i]),
     "fac_true_peak": (_i, [C.POINTER(ResampleDesc), _p, _p, _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),

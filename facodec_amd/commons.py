@@ -814,6 +814,33 @@ def level_clips(waves, sample_rate=MODEL_RATE, max_batch_samples=MAX_BATCH_SAMPL
     return out
 
 
+@torch.no_grad()
+def denoise_clips(waves, max_batch_samples=MAX_BATCH_SAMPLES, **parameters):
+    """Spectral noise suppression (ops.denoise) of clips of different lengths -> per clip, in the caller's order,
+    ops.Denoised(y (T_i,) float32, G (ceil(T_i / 256) + 1, 257) float64), on the device.  The clips (T_i,) or (1, T_i), float32
+    on the GPU at any sample rate, go through plan_groups' zero-padded groups with their lengths: one ops.denoise call (three
+    C calls) per group, nothing is read back; a clip comes out as the single-clip call gives it, bit for bit, whatever it is
+    grouped with.  **parameters: ops.denoise's M, W, over, max_atten_db -- whose defaults were not tuned by listening."""
+    from . import ops
+    ops.ns_params(**parameters)                                     # ValueError: the parameters
+    waves = list(waves)
+    if not waves:
+        return []
+    _need_gpu(waves, "clips")
+    for w in waves:
+        if not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(w.shape)}")
+    lengths = [int(w.shape[-1]) for w in waves]
+    out = [None] * len(waves)
+    for group in plan_groups(lengths, max_batch_samples):
+        batch = torch.nn.utils.rnn.pad_sequence([waves[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), batch.device)
+        r = ops.denoise(batch, lens=lens, **parameters)
+        for j, i in enumerate(group):
+            out[i] = ops.Denoised(r.y[j, :lengths[i]], r.G[j, :ops.ns_frames(lengths[i])])
+    return out
+
+
 def active_segments(flags, frame, length):
     """flags: one clip's 0 / 1 frame flags (host sequence) -> [(start_sample, end_sample)] of its runs of active frames, the last
     end clipped to the clip's length.  Host only."""

@@ -2004,6 +2004,184 @@ def true_peak(x, rate=24000, lens=None, quality="best"):
     return peak
 
 
+# --------------------------------------------------------------------------------- noise suppression
+NsParams = namedtuple("NsParams", "M W over g_min")
+Denoised = namedtuple("Denoised", "y G")
+NS_N, NS_H, NS_BINS, NS_CARRY, NS_DELAY = _lib.NS_N, _lib.NS_H, _lib.NS_BINS, _lib.NS_CARRY, 2 * _lib.NS_H
+
+
+def ns_params(M=8, W=96, over=4.0, max_atten_db=15.0):
+    """-> NsParams(M, W, over, g_min) of fac_ns_gains: the power spectra are averaged over M frames, the noise floor is the
+    minimum of that average over W frames (frames of 512 samples at a hop of 256), a bin passes in proportion to what its
+    average holds above `over` times the floor, and never falls below g_min = 10 ** (-max_atten_db / 20) (a Python float: the
+    kernel and a restatement of it take the same bits).  The defaults -- 8 frames, 96 frames (1.02 s at 24 kHz), 4.0, 15 dB --
+    were not tuned by listening."""
+    if int(M) != M or not 1 <= int(M) <= _lib.NS_MAX_M:
+        raise ValueError(f"denoise: M = {M} outside 1 .. {_lib.NS_MAX_M} frames")
+    if int(W) != W or not 1 <= int(W) <= _lib.NS_MAX_W:
+        raise ValueError(f"denoise: W = {W} outside 1 .. {_lib.NS_MAX_W} frames")
+    over, max_atten_db = float(over), float(max_atten_db)
+    if not 0.0 < over < math.inf:
+        raise ValueError(f"denoise: over = {over} (finite, above 0)")
+    if not 0.0 <= max_atten_db < math.inf:
+        raise ValueError(f"denoise: max_atten_db = {max_atten_db} (finite, not negative)")
+    g_min = 10.0 ** (-max_atten_db / 20.0)
+    if not g_min > 0.0:
+        raise ValueError(f"denoise: max_atten_db = {max_atten_db} leaves no gain floor above 0")
+    return NsParams(int(M), int(W), over, g_min)
+
+
+def ns_frames(n):
+    """Frames of a signal of n samples: ceil(n / 256) + 1, 0 for an empty one."""
+    return -(-int(n) // NS_H) + 1 if n > 0 else 0
+
+
+def _ns_ring(t, B, R, what, dtype=torch.float64, last=()):
+    shape = (B, R, NS_BINS) + last
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != len(shape) or t.shape[0] != B or t.shape[1] < R \
+            or tuple(t.shape[2:]) != shape[2:] or not t[0].is_contiguous():
+        raise ValueError(f"{what} must be {dtype} {shape} on the GPU with dense rows, got {getattr(t, 'dtype', type(t))} "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+    return t
+
+
+def _ns_carry(t, B, what):
+    if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (B, NS_CARRY) or not t.is_contiguous()):
+        raise ValueError(f"{what} must be contiguous float32 ({B}, {NS_CARRY}) on the GPU")
+    return t
+
+
+def _ns_pitch(t, B):
+    """Row pitch of a (B, R, 257[, 2]) ring in elements of 8 (or, for spectra, 16) bytes."""
+    per = 2 if t.dim() == 4 else 1
+    return (t.stride(0) if B > 1 else t.shape[1] * NS_BINS * per) // per
+
+
+def ns_power(x, P, n0=0, f0=0, n_new=None, R=None, lens=None, starts=None, carry_in=None, carry_out=None, X=None, k=None):
+    """fac_ns_power: the power spectra of frames f0 .. f0 + n_new - 1 of [carry | x] (x (B, k) float32, sample i at the absolute
+    index n0 + i) into the ring P (B, >= R, 257) float64, frame f at slot f % R; X (B, >= R, 257, 2) float64 also takes the
+    spectra.  n_new defaults to the frames of an offline signal of k samples.  carry_in / carry_out (B, 1023) float32: two
+    different buffers of a stream; lens (B,) int32 only without them; starts (B,) int64: the rows' first samples."""
+    if not isinstance(P, torch.Tensor) or not P.is_cuda:
+        raise _lib.FacodecHipError(f"ns_power: P must live on the GPU (got {getattr(P, 'device', type(P))}); there is no CPU path")
+    if x is not None:
+        x = _rows(x, "ns_power")
+    B = P.shape[0]
+    k = (x.shape[1] if x is not None else 0) if k is None else int(k)
+    R = P.shape[1] if R is None else int(R)
+    n_new = ns_frames(k) if n_new is None else int(n_new)
+    P = _ns_ring(P, B, R, "ns_power: P")
+    if X is not None:
+        X = _ns_ring(X, B, R, "ns_power: X", last=(2,))
+        if B > 1 and _ns_pitch(X, B) != _ns_pitch(P, B):
+            raise ValueError("ns_power: X and P must have the same row pitch")
+    if B == 0 or (n_new == 0 and carry_out is None):
+        return P
+    d = _lib.NsPowerDesc()
+    d.carry_in = _ptr(_ns_carry(carry_in, B, "ns_power: carry_in"))
+    d.carry_out = _ptr(_ns_carry(carry_out, B, "ns_power: carry_out"))
+    d.x = x.data_ptr() if x is not None and k > 0 else None
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.starts = _ptr(_i64_rows(starts, B, "ns_power: starts"))
+    d.P, d.X = P.data_ptr(), _ptr(X)
+    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
+    d.p_bs, d.n0, d.f0 = _ns_pitch(P, B), int(n0), int(f0)
+    d.B, d.k, d.n_new, d.R = B, k, n_new, R
+    _lib.check(_lib.load().fac_ns_power(C.byref(d), _stream()), "fac_ns_power")
+    return P
+
+
+def ns_gains(P, p, f0=0, n_new=None, R=None, starts=None, G=None):
+    """fac_ns_gains over the ring P (B, >= R, 257) float64 with p = ns_params(...): the gains of frames f0 .. f0 + n_new - 1 -> G
+    (B, R, 257) float64, frame f at slot f % R (allocated when not given)."""
+    if not isinstance(P, torch.Tensor) or not P.is_cuda:
+        raise _lib.FacodecHipError(f"ns_gains: P must live on the GPU (got {getattr(P, 'device', type(P))}); there is no CPU path")
+    B = P.shape[0]
+    R = P.shape[1] if R is None else int(R)
+    n_new = R - int(f0) if n_new is None else int(n_new)
+    P = _ns_ring(P, B, R, "ns_gains: P")
+    if G is None:
+        G = torch.ones(B, R, NS_BINS, device=P.device, dtype=torch.float64)
+    G = _ns_ring(G, B, R, "ns_gains: G")
+    if B == 0 or n_new == 0:
+        return G
+    d = _lib.NsGainsDesc()
+    d.P, d.G, d.starts = P.data_ptr(), G.data_ptr(), _ptr(_i64_rows(starts, B, "ns_gains: starts"))
+    d.p_bs, d.g_bs, d.f0 = _ns_pitch(P, B), _ns_pitch(G, B), int(f0)
+    d.over, d.g_min = p.over, p.g_min
+    d.B, d.n_new, d.R, d.M, d.W = B, n_new, R, p.M, p.W
+    _lib.check(_lib.load().fac_ns_gains(C.byref(d), _stream()), "fac_ns_gains")
+    return G
+
+
+def ns_synth(x, G, n0=0, m0=0, n_out=None, R=None, lens=None, starts=None, carry_in=None, X=None, k=None, out=None):
+    """fac_ns_synth: y[m0 .. m0 + n_out) (B, n_out) float32 of [carry | x] masked with the gains G (B, >= R, 257) float64 (frame
+    f at slot f % R): both frames over every output segment are transformed (or, with X, read from that ring), masked,
+    transformed back, windowed and added.  n_out defaults to k (with n0 = m0 = 0: the offline call)."""
+    if not isinstance(G, torch.Tensor) or not G.is_cuda:
+        raise _lib.FacodecHipError(f"ns_synth: G must live on the GPU (got {getattr(G, 'device', type(G))}); there is no CPU path")
+    if x is not None:
+        x = _rows(x, "ns_synth")
+    B = G.shape[0]
+    k = (x.shape[1] if x is not None else 0) if k is None else int(k)
+    R = G.shape[1] if R is None else int(R)
+    n_out = k if n_out is None else int(n_out)
+    G = _ns_ring(G, B, R, "ns_synth: G")
+    if X is not None:
+        X = _ns_ring(X, B, R, "ns_synth: X", last=(2,))
+        if B > 1 and _ns_pitch(X, B) != _ns_pitch(G, B):
+            raise ValueError("ns_synth: X and G must have the same row pitch")
+    if out is None:
+        out = torch.empty(B, n_out, device=G.device, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_out or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"ns_synth: out must be float32 ({B}, >= {n_out}) on the GPU with dense rows")
+    if B == 0 or n_out == 0:
+        return out[:, :n_out]
+    d = _lib.NsSynthDesc()
+    d.carry_in = _ptr(_ns_carry(carry_in, B, "ns_synth: carry_in"))
+    d.x = x.data_ptr() if x is not None and k > 0 else None
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.starts = _ptr(_i64_rows(starts, B, "ns_synth: starts"))
+    d.G, d.X, d.y = G.data_ptr(), _ptr(X), out.data_ptr()
+    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
+    d.g_bs, d.y_bs, d.n0, d.m0 = _ns_pitch(G, B), (out.stride(0) if B > 1 else out.shape[1]), int(n0), int(m0)
+    d.B, d.k, d.n_out, d.R = B, k, n_out, R
+    _lib.check(_lib.load().fac_ns_synth(C.byref(d), _stream()), "fac_ns_synth")
+    return out[:, :n_out]
+
+
+def denoise(x, lens=None, starts=None, M=8, W=96, over=4.0, max_atten_db=15.0, keep_spectra=False):
+    """Spectral noise suppression of x (B, T) or (B, 1, T) float32 on the GPU -> Denoised(y, G): y of x's shape,
+    float32, aligned with x; G (B, F, 257) float64, F = ceil(T / 256) + 1, the gain of every frame (512 samples, sine window,
+    hop 256) and bin.  A bin's gain is xi / (1 + xi), xi = S / (over * Nf) - 1 clipped at 0, S the mean power of the last M
+    frames, Nf the minimum of S over the last W frames, never below -max_atten_db; 1 while the window holds digital silence.
+    lens (B,) int32: row b is x[b, :lens[b]], what lies behind it is not read and comes out 0.  starts (B,) int32: row b's
+    stream begins at sample starts[b]; earlier samples count as zero, frames below starts[b] // 256 are in no window, outputs
+    before starts[b] are 0.  Three C calls (fac_ns_power, fac_ns_gains, fac_ns_synth), no host read; what streaming.
+    NoiseSuppressor gives for the same signal, 512 samples earlier.  keep_spectra: synthesis reads the spectra fac_ns_power
+    wrote (16 bytes per frame and bin of scratch) where it otherwise transforms every frame again; the same bits.  A stream
+    that starts in speech has that speech for its floor until the window has seen a pause.  The arithmetic is pinned in
+    include/facodec_hip.h; the defaults were not tuned by listening."""
+    p = ns_params(M, W, over, max_atten_db)
+    x2 = _rows(x, "denoise")
+    B, T = x2.shape
+    F = ns_frames(T)
+    dev = x2.device
+    G = torch.ones(B, F, NS_BINS, device=dev, dtype=torch.float64)
+    if B == 0 or T == 0:
+        return Denoised(torch.zeros_like(x), G)
+    if starts is not None:
+        if not isinstance(starts, torch.Tensor) or not starts.is_cuda or tuple(starts.shape) != (B,) or starts.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"denoise: starts must be int32 ({B},) on the GPU")
+        starts = starts.to(torch.int64).contiguous()
+    P = torch.empty(B, F, NS_BINS, device=dev, dtype=torch.float64)
+    X = torch.empty(B, F, NS_BINS, 2, device=dev, dtype=torch.float64) if keep_spectra else None
+    ns_power(x2, P, lens=lens, starts=starts, X=X)
+    ns_gains(P, p, 0, F, starts=starts, G=G)
+    y = ns_synth(x2, G, lens=lens, starts=starts, X=X)
+    return Denoised(y.view(x.shape), G)
+
+
 # --------------------------------------------------------------------------------- objective scores (DESIGN.md 27)
 STOI_RATE = 10000
 StoiGeometry = namedtuple("StoiGeometry", "n_frames ws_bytes_per_row energy_frames scan_block band_frames score_segments")

@@ -1356,6 +1356,158 @@ class LevelledSession:
         return self.session.set_target(timbre)
 
 
+class NoiseSuppressor:
+    """Spectral noise suppression over B parallel streams, one block at a time:
+
+        ns = NoiseSuppressor(B)                              # M = 8, W = 96, over = 4.0, max_atten_db = 15.0
+        y = ns.push(block)                                   # (B, 1, k) or (B, k) float32 on the GPU, any k >= 1 -> the same shape
+        tail = ns.finish()                                   # the last 512 samples
+
+    The pushes and finish(), concatenated, are 512 zeros and then ops.denoise(whole signal).y, bit for bit, for any chunking
+    (`latency` seconds at `rate`; the definition is in samples, any rate is accepted).  push is three C calls -- fac_ns_power
+    for the frames the block completes, which also moves the last 1023 input samples from one carry buffer into the other;
+    fac_ns_gains for those frames, when there are any; fac_ns_synth for the block's outputs -- reads nothing back and allocates
+    nothing but its output.  Power spectra and gains live in device rings of `ring` frames; a push that completes more than
+    ring - max(M + W - 2, 2) frames is run as several.  The synthesis transforms the frames over its outputs again instead of
+    keeping half-finished output between pushes: the state is the input carry, the two rings and the rows' starts.  It runs
+    eagerly, outside the sessions' captured graphs.
+
+    reset(rows) restarts the given rows on the device: their carry and rings are cleared and their stream begins at `samples`;
+    the 512 samples of the old stream that were not played yet come out as zeros, and the rows then give row b of
+    ops.denoise(concat(zeros(samples), new), starts=samples), 512 samples late, bit for bit.  The other rows are not touched.
+    A stream that starts in speech has that speech for its noise floor until the window has seen a pause.  The defaults were
+    not tuned by listening."""
+
+    def __init__(self, B, rate=MODEL_RATE, M=8, W=96, over=4.0, max_atten_db=15.0, ring=128, device="cuda"):
+        self.p = ops.ns_params(M, W, over, max_atten_db)
+        self.B, self.rate, self.R, self.device = int(B), int(rate), int(ring), torch.device(device)
+        if self.B < 1:
+            raise ValueError(f"NoiseSuppressor: B = {B}")
+        self._reach = max(self.p.M + self.p.W - 2, 2)                # older frames a push still reads in the rings
+        if self.R < self._reach + 2:
+            raise ValueError(f"NoiseSuppressor: ring = {ring} below the {self._reach} older frames a push reaches plus the two frames of its own")
+        self.delay, self.latency = ops.NS_DELAY, ops.NS_DELAY / self.rate
+        self.samples = 0
+        f64 = dict(device=self.device, dtype=torch.float64)
+        self._P = torch.zeros(self.B, self.R, ops.NS_BINS, **f64)
+        self._G = torch.ones(self.B, self.R, ops.NS_BINS, **f64)
+        self._start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
+        self._carry = [torch.zeros(self.B, ops.NS_CARRY, device=self.device, dtype=torch.float32) for _ in range(2)]
+        self._cur = 0
+        self._done = False
+
+    @property
+    def frames(self):
+        """Frames whose gains are decided (on the host)."""
+        return self.samples // ops.NS_H
+
+    def _run(self, x):
+        k = x.shape[1]
+        f0 = self.frames
+        n_new = (self.samples + k) // ops.NS_H - f0
+        src, dst = self._carry[self._cur], self._carry[1 - self._cur]
+        ops.ns_power(x, self._P, n0=self.samples, f0=f0, n_new=n_new, R=self.R, starts=self._start, carry_in=src, carry_out=dst)
+        if n_new:
+            ops.ns_gains(self._P, self.p, f0, n_new, R=self.R, starts=self._start, G=self._G)
+        y = ops.ns_synth(x, self._G, n0=self.samples, m0=self.samples - self.delay, n_out=k, R=self.R, starts=self._start, carry_in=src)
+        self._cur ^= 1
+        self.samples += k
+        return y
+
+    def push(self, block):
+        if self._done:
+            raise RuntimeError("push() after finish()")
+        x = ops._rows(block, "NoiseSuppressor.push")
+        if x.shape[0] != self.B or x.shape[1] < 1:
+            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
+        parts, t, k = [], 0, x.shape[1]
+        while t < k:
+            room = (self.R - self._reach) * ops.NS_H - self.samples % ops.NS_H     # completes at most ring - reach frames
+            n = min(k - t, room)
+            parts.append(self._run(x[:, t:t + n]))
+            t += n
+        y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return y.view(block.shape)
+
+    def finish(self):
+        """(B, 512) float32: the samples still held back; the stream takes no more audio."""
+        if self._done:
+            raise RuntimeError("finish() twice")
+        self._done = True
+        f0 = self.frames
+        n_new = ops.ns_frames(self.samples) - f0                     # the one or two frames that reach past the end
+        src = self._carry[self._cur]
+        if n_new:
+            ops.ns_power(None, self._P, n0=self.samples, f0=f0, n_new=n_new, R=self.R, starts=self._start, carry_in=src, k=0)
+            ops.ns_gains(self._P, self.p, f0, n_new, R=self.R, starts=self._start, G=self._G)
+        self._final = f0 + n_new
+        return ops.ns_synth(None, self._G, n0=self.samples, m0=self.samples - self.delay, n_out=self.delay, R=self.R, starts=self._start,
+                            carry_in=src, k=0)
+
+    def gains(self, n):
+        """-> G (B, n, 257) float64: the gains of the last n decided frames (a copy out of the ring; for tests and meters)."""
+        have = self._final if self._done else self.frames
+        if not 1 <= n <= min(have, self.R):
+            raise ValueError(f"gains({n}): {min(have, self.R)} decided frames are in the ring")
+        idx = torch.arange(have - n, have, device=self.device) % self.R
+        return self._G[:, idx]
+
+    def reset(self, rows):
+        """Puts the given rows (indices on the host) back into the state of a fresh stream that begins at `samples`, on the device."""
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.B for r in rows):
+            raise ValueError(f"reset({rows}): rows are 0 .. {self.B - 1}")
+        if not rows:
+            return
+        idx = ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device)
+        for t, v in ((self._carry[self._cur], 0.0), (self._P, 0.0), (self._G, 1.0)):
+            t.index_fill_(0, idx, v)
+        self._start.index_fill_(0, idx, self.samples)
+
+
+class DenoisedSession:
+    """A StreamingCodec, a StreamingConverter, a ResampledSession or a LevelledSession of one whose input goes through a
+    NoiseSuppressor first:
+
+        codec = DenoisedSession(StreamingCodec(model, timbre), max_atten_db=15.0)
+        out = codec.prime(wave[:, :, :4800]); out = codec.push(wave[:, :, t:t + 480]); out = codec.finish()
+
+    Same surface and the same dicts as the wrapped session (whose other attributes read through).  The suppressor runs at the
+    rate the session takes its audio at, eagerly, around the session's captured graphs: three C calls per push.  The session
+    sees 512 zeros and then the suppressed input, cut off where the pushed audio ends; `latency_in` is that delay in seconds, on
+    top of the wrapped session's own.  It nests with LevelledSession either way round: the outer stage runs first.
+    **parameters: NoiseSuppressor's (M, W, over, max_atten_db, ring), whose defaults were not tuned by listening."""
+
+    def __init__(self, session, **parameters):
+        if not hasattr(session, "prime_samples") or not session.prime_samples:
+            raise ValueError("DenoisedSession: this session takes codes, not audio")
+        self.session = session
+        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
+        inner = session
+        while not hasattr(inner, "B"):                               # a ResampledSession keeps them on the session it wraps
+            inner = inner.session
+        self.B, self.device = inner.B, inner.device
+        self.ns = NoiseSuppressor(self.B, self.rate, device=self.device, **parameters)
+        self.latency_in = self.ns.latency + getattr(session, "latency_in", 0.0)
+
+    def __getattr__(self, name):
+        if name == "session":
+            raise AttributeError(name)
+        return getattr(self.session, name)
+
+    def prime(self, first):
+        return self.session.prime(self.ns.push(first))
+
+    def push(self, hop):
+        return self.session.push(self.ns.push(hop))
+
+    def finish(self):
+        return self.session.finish()
+
+    def set_target(self, timbre):
+        return self.session.set_target(timbre)
+
+
 class ResampledSession:
     """A StreamingCodec / StreamingConverter / StreamingDecoder that takes its audio at `in_rate` and gives it at `out_rate`:
 

@@ -1336,6 +1336,104 @@ int fac_agc_apply(const fac_agc_apply_desc* d, fac_stream_t stream);
 int64_t fac_true_peak_ws_bytes(int B, int n_out);
 int fac_true_peak(const fac_resample_desc* d, float* peak, void* ws, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Noise suppression (csrc/denoise.hip): a spectral suppressor of stationary background noise.  This comment is the
+ * normative definition.  Finite windows, no recurrence in time: a gain depends on the M + W - 1 power spectra up to its frame,
+ * an output sample on two frames, so every frame is computable in parallel and any chunking of a stream gives the bits of the
+ * offline call.  Unless said otherwise every operation below is one IEEE fp64 operation with one round-to-nearest; nothing is
+ * fused.
+ *
+ * Framing.  N = 512, H = 256, w[n] = sinpi(n / 512) (the device library's sinpi of the fp64 quotient), analysis and synthesis
+ * window alike; w[n]^2 + w[n + H]^2 = 1.  Per row b the signal is the virtual concatenation [carry | block]: the block's sample i
+ * has the absolute index n0 + i and exists for i < k_b = lens ? clamp(lens[b], 0, k) : k; carry_in (B, FAC_NS_CARRY) fp32, dense,
+ * holds the samples n0 - FAC_NS_CARRY .. n0 - 1 (NULL: zeros).  A sample before start_b = starts ? max(starts[b], 0) : 0, at or
+ * behind n0 + k_b, or before the carry is 0 and is not read.  Frame f >= 0 covers the samples (f - 1) H .. (f + 1) H - 1;
+ * fs_b = start_b / H is the first frame of the row's current stream.
+ *
+ * Transform.  z[n] = (w[n] * (double)sample, 0), n < 512.  Forward: for half = 256, 128, .. 1, for every i < 256 with
+ * pos = i % half, lo = 2 (i - pos) + pos, hi = lo + half, t = tw[pos * (256 / half)], tw[j] = (c, -s) of sincospi(j / 256):
+ *   (u, v) = (z[lo], z[hi]);  z[lo] = u + v;  d = u - v;  z[hi] = (d.x t.x - d.y t.y,  d.x t.y + d.y t.x)
+ * -- the radix-2 decimation in frequency of stoi_bands_kernel, butterfly for butterfly.  X[k] = z[rev9(k)] (the 9-bit reversal).
+ * Inverse: for half = 1, 2, .. 256, same i, pos, lo, hi, t:
+ *   q = (v.x t.x + v.y t.y,  v.y t.x - v.x t.y);  z[lo] = u + q;  z[hi] = u - q;      then every z[n] times 1 / 512 (exact).
+ *
+ * fac_ns_power: P_f[k] = X.x^2 + X.y^2, k = 0 .. 256, for the n_new frames f = f0 .. f0 + n_new - 1, written frame-major
+ * (FAC_NS_BINS contiguous doubles per frame) into the ring P (B, R, 257) of row pitch p_bs doubles, frame f at slot f % R (a
+ * plain (B, F, 257) array is R >= F, f0 = 0).  X, NULL or a ring of the same geometry in double2 units: the spectra themselves,
+ * for fac_ns_synth.  carry_out (B, FAC_NS_CARRY), NULL or a buffer OTHER than carry_in: the samples n0 + k - FAC_NS_CARRY ..
+ * n0 + k - 1, written by one extra workgroup per row of the same launch; n_new = 0 with carry_out only moves the carry.  After n
+ * samples of a stream the frames below n / H are complete.  One wave per frame, 4 x 4 frames per 256-thread workgroup, 40 KB LDS.
+ * Refused before any launch: a NULL descriptor or P; x NULL with k > 0; B outside 1 .. 65535; k outside 0 .. 2^30; n_new < 0, or
+ * 0 without carry_out; n0 or f0 negative; carry_out == carry_in; lens with a carry buffer; x_bs < k or p_bs < 257 R with B > 1;
+ * R outside max(n_new, 1) .. 2^22; with carry_in, a frame f0 that starts before the carry.
+ *
+ * fac_ns_gains: for the n_new frames f = f0 .. f0 + n_new - 1 and every bin k, from the ring P:
+ *   S_f[k]  = (P_lo[k] + .. + P_f[k]) / (double)(f - lo + 1),  lo = max(fs_b, f - M + 1), the sum left to right from P_lo
+ *   Nf_f[k] = min S_g[k] over g = max(fs_b, f - W + 1) .. f                        (exact in any order)
+ *   Nf_f[k] == 0:  G_f[k] = 1                                    (digital silence in the window: nothing can be estimated)
+ *   else  xi = max(S_f[k] / (over * Nf_f[k]) - 1, 0);   G_f[k] = max(xi / (1 + xi), g_min)
+ * g_min = 10^(-max_atten_db / 20) is the host's, handed over as fp64.  A frame f < fs_b gets G = 1.  G (B, R, 257) fp64 of row
+ * pitch g_bs, frame f at slot f % R.  One 256-thread workgroup per (row, 64 frames, 16 bins): P of the tile and its M + W - 2
+ * older neighbours in LDS, then S of the tile and its W - 1 older neighbours, then the minimum and the gain, one thread per
+ * (bin, four consecutive frames), which reads the S their windows share once; (125 + M + 2 W) * 128 bytes of dynamic LDS
+ * (41.6 KB at M = 8, W = 96).
+ * Refused before any launch: a NULL descriptor, P or G; B outside 1 .. 65535; n_new < 1; M outside 1 .. FAC_NS_MAX_M; W outside
+ * 1 .. FAC_NS_MAX_W; over not in (0, inf); g_min not in (0, 1]; f0 < 0; R < min(f0 + n_new, M + W - 2 + n_new) or above 2^22;
+ * p_bs or g_bs below 257 R with B > 1.
+ *
+ * fac_ns_synth: v_f = w * Re(inverse(Y_f)) with Y_f[k] = (G_f[k] X_f[k].x, G_f[k] X_f[k].y) for k = 0 .. 256 and
+ * Y_f[512 - k] = conj(Y_f[k]) for k = 1 .. 255; v_f = 0 for f < fs_b.  X_f is transformed again from the samples (the same
+ * bits as fac_ns_power's) or, with X != NULL, read from that ring (row pitch g_bs double2; no sample is read then).
+ *   y[m] = (float)(v_f[m - (f - 1) H] + v_{f+1}[m - f H]),  f = m / H: the older frame first, one fp64 sum, one rounding to fp32
+ *   y[m] = 0 for m < start_b (and so for m < 0) and for m >= n0 + k_b
+ * The call writes y[b * y_bs + i] = y[m0 + i], i < n_out: store only.  Offline n0 = m0 = 0, n_out = k.  In a stream the caller
+ * asks only for samples whose two frames are complete (m0 + n_out <= (floor((n0 + k) / H) - 1) H), or the signal ends with
+ * this block; the constant delay of a block-in, block-out stream is D = 2 H = 512 samples: m0 = n0 - 512, n_out = k, and the
+ * flush is k = 0, n_out = 512.  FAC_NS_CARRY = 1023 is what the oldest such output reaches back.  One workgroup per (row,
+ * 15 segments) transforms their 16 frames, one wave per frame, and keeps the last half frame of a round in LDS for the next:
+ * 42 KB LDS.
+ * Refused before any launch: a NULL descriptor, G or y; x NULL with k > 0 and no X; B outside 1 .. 65535; k outside 0 .. 2^30;
+ * n_out outside 1 .. 2^30; n0 < 0; lens with a carry buffer; x_bs < k, y_bs < n_out or g_bs < 257 R with B > 1; outputs that
+ * reach in front of the carry (or, with n0 > 0 and no carry or X, in front of the block); R below the frames the outputs reach
+ * (floor(m0 / H) .. floor((m0 + n_out - 1) / H) + 1 in different slots) or above 2^22.
+ * ---------------------------------------------------------------------------------------- */
+enum { FAC_NS_N = 512, FAC_NS_H = 256, FAC_NS_BINS = 257, FAC_NS_CARRY = 1023, FAC_NS_MAX_M = 64, FAC_NS_MAX_W = 256 };
+typedef struct fac_ns_power_desc {
+  const float* carry_in;    /* (B, FAC_NS_CARRY) or NULL */
+  float* carry_out;         /* (B, FAC_NS_CARRY) or NULL, never carry_in */
+  const float* x;           /* (B, k), pitch x_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  const int64_t* starts;    /* (B) or NULL */
+  double* P;                /* written: (B, R, 257), row pitch p_bs */
+  double* X;                /* written: (B, R, 257, 2), row pitch p_bs double2; or NULL */
+  int64_t x_bs, p_bs, n0, f0;
+  int32_t B, k, n_new, R;
+} fac_ns_power_desc;
+int fac_ns_power(const fac_ns_power_desc* d, fac_stream_t stream);
+
+typedef struct fac_ns_gains_desc {
+  const double* P;          /* (B, R, 257), row pitch p_bs */
+  const int64_t* starts;    /* (B) or NULL */
+  double* G;                /* written: (B, R, 257), row pitch g_bs */
+  int64_t p_bs, g_bs, f0;
+  double over, g_min;
+  int32_t B, n_new, R, M, W, reserved;
+} fac_ns_gains_desc;
+int fac_ns_gains(const fac_ns_gains_desc* d, fac_stream_t stream);
+
+typedef struct fac_ns_synth_desc {
+  const float* carry_in;    /* (B, FAC_NS_CARRY) or NULL */
+  const float* x;           /* (B, k), pitch x_bs */
+  const int32_t* lens;      /* (B) or NULL */
+  const int64_t* starts;    /* (B) or NULL */
+  const double* G;          /* (B, R, 257), row pitch g_bs */
+  const double* X;          /* (B, R, 257, 2), row pitch g_bs double2; or NULL */
+  float* y;                 /* written: (B, n_out), pitch y_bs */
+  int64_t x_bs, g_bs, y_bs, n0, m0;
+  int32_t B, k, n_out, R;
+} fac_ns_synth_desc;
+int fac_ns_synth(const fac_ns_synth_desc* d, fac_stream_t stream);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
