@@ -150,6 +150,21 @@ class NsSynthDesc(C.Structure):
     ]
 
 
+AEC_N, AEC_H, AEC_BINS, AEC_MAX_P, AEC_LDS_P, AEC_MAX_DELAY, AEC_MIC_CARRY, AEC_FAR_CARRY = 512, 256, 257, 32, 8, 16384, 255, 511     # FAC_AEC_*
+
+
+class AecDesc(C.Structure):
+    _fields_ = [
+        ("mic_carry_in", _p), ("mic_carry_out", _p), ("far_carry_in", _p), ("far_carry_out", _p), ("mic", _p), ("far", _p),
+        ("lens", _p), ("starts", _p), ("adapt", _p), ("W", _p), ("X", _p), ("e_ring", _p), ("y", _p), ("stats", _p),
+        ("mic_bs", _i64), ("far_bs", _i64), ("y_bs", _i64), ("w_bs", _i64), ("xr_bs", _i64), ("s_bs", _i64),
+        ("n0", _i64), ("m0", _i64), ("blk0", _i64),
+        ("mu", C.c_double), ("c", C.c_double), ("delta", C.c_double),
+        ("B", C.c_int32), ("k", C.c_int32), ("n_out", C.c_int32), ("n_blk", C.c_int32), ("P", C.c_int32), ("delay", C.c_int32),
+        ("far_cn", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class SidApplyDesc(C.Structure):
     _fields_ = [
         ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3), ("n_q", C.c_int32 * 3), ("B", C.c_int32),
@@ -340,6 +355,8 @@ SIGNATURES = {
     "fac_ns_power": (_i, [C.POINTER(NsPowerDesc), _p]),
     "fac_ns_gains": (_i, [C.POINTER(NsGainsDesc), _p]),
     "fac_ns_synth": (_i, [C.POINTER(NsSynthDesc), _p]),
+    "fac_aec_run": (_i, [C.POINTER(AecDesc), _p]),
+    "fac_aec_state_sizes": (_i, [_i, _i, C.POINTER(_i64)]),
     "fac_true_peak_ws_bytes": (_i64, [_i, _i]),
     "fac_true_peak": (_i, [C.POINTER(ResampleDesc), _p, _p, _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),

@@ -841,6 +841,39 @@ def denoise_clips(waves, max_batch_samples=MAX_BATCH_SAMPLES, **parameters):
     return out
 
 
+def echo_cancel_clips(mics, fars, max_batch_samples=MAX_BATCH_SAMPLES, **parameters):
+    """Echo cancellation (ops.echo_cancel) of clips of different lengths -> per clip, in the caller's order,
+    ops.EchoCancelled(e (T_i,) float32, W (P, 257, 2) float64, stats (ceil(T_i / 256), 3) float64), on the device.  mics[i] and
+    fars[i], (T_i,) or (1, T_i), float32 on the GPU, are one call's microphone and far-end signals, of one length.  They go
+    through plan_groups' zero-padded groups with their lengths: one ops.echo_cancel call (one C call) per group, nothing is
+    read back; a clip comes out as the single-clip call gives it, bit for bit, whatever it is grouped with.  **parameters:
+    ops.echo_cancel's P, mu, beta, delta, delay -- whose defaults were not tuned by listening."""
+    from . import ops
+    ops.aec_params(**parameters)                                    # ValueError: the parameters
+    mics, fars = list(mics), list(fars)
+    if len(mics) != len(fars):
+        raise ValueError(f"{len(mics)} microphone clips and {len(fars)} far-end clips")
+    if not mics:
+        return []
+    _need_gpu(mics, "clips")
+    _need_gpu(fars, "clips")
+    for m, f in zip(mics, fars):
+        if not (m.dim() == 1 or (m.dim() == 2 and m.shape[0] == 1)) or not (f.dim() == 1 or (f.dim() == 2 and f.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(m.shape)} and {tuple(f.shape)}")
+        if m.shape[-1] != f.shape[-1]:
+            raise ValueError(f"a microphone clip of {m.shape[-1]} samples with a far-end clip of {f.shape[-1]}")
+    lengths = [int(m.shape[-1]) for m in mics]
+    out = [None] * len(mics)
+    for group in plan_groups(lengths, max_batch_samples):
+        mic = torch.nn.utils.rnn.pad_sequence([mics[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        far = torch.nn.utils.rnn.pad_sequence([fars[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), mic.device)
+        r = ops.echo_cancel(mic, far, lens=lens, **parameters)
+        for j, i in enumerate(group):
+            out[i] = ops.EchoCancelled(r.e[j, :lengths[i]], r.W[j], r.stats[j, :ops.aec_blocks(lengths[i])])
+    return out
+
+
 def active_segments(flags, frame, length):
     """flags: one clip's 0 / 1 frame flags (host sequence) -> [(start_sample, end_sample)] of its runs of active frames, the last
     end clipped to the clip's length.  Host only."""

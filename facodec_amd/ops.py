@@ -2182,6 +2182,151 @@ def denoise(x, lens=None, starts=None, M=8, W=96, over=4.0, max_atten_db=15.0, k
     return Denoised(y.view(x.shape), G)
 
 
+# --------------------------------------------------------------------------------- echo cancellation
+AecParams = namedtuple("AecParams", "P mu beta delta delay c")
+EchoCancelled = namedtuple("EchoCancelled", "e W stats")
+AEC_H, AEC_BINS, AEC_DELAY = _lib.AEC_H, _lib.AEC_BINS, _lib.AEC_H
+
+
+def aec_params(P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0):
+    """-> AecParams(P, mu, beta, delta, delay, c) of fac_aec_run: P partitions of 256 taps; the step is mu over the far-end
+    power in the filter's span plus c = beta * P times the error power plus delta (c a Python float: the kernel and a
+    restatement of it take the same bits); the far end is used `delay` samples late.  The error term is what keeps the filter
+    from diverging under double talk.  The defaults -- 8, 0.5, 1.0, 1e-6, 0 -- were not tuned by listening."""
+    if int(P) != P or not 1 <= int(P) <= _lib.AEC_MAX_P:
+        raise ValueError(f"echo_cancel: P = {P} outside 1 .. {_lib.AEC_MAX_P} partitions")
+    mu, beta, delta = float(mu), float(beta), float(delta)
+    if not 0.0 <= mu <= 1.0:
+        raise ValueError(f"echo_cancel: mu = {mu} outside [0, 1]")
+    if not 0.0 <= beta < math.inf:
+        raise ValueError(f"echo_cancel: beta = {beta} (finite, not negative)")
+    if not 0.0 <= delta < math.inf:
+        raise ValueError(f"echo_cancel: delta = {delta} (finite, not negative)")
+    if int(delay) != delay or not 0 <= int(delay) <= _lib.AEC_MAX_DELAY:
+        raise ValueError(f"echo_cancel: delay = {delay} outside 0 .. {_lib.AEC_MAX_DELAY} samples")
+    return AecParams(int(P), mu, beta, delta, int(delay), beta * int(P))
+
+
+def aec_blocks(n):
+    """Blocks of a signal of n samples: ceil(n / 256)."""
+    return -(-int(n) // AEC_H)
+
+
+def aec_state_sizes(P, delay=0):
+    """fac_aec_state_sizes: per-row (doubles of W, doubles of the X ring, floats of the mic carry, of the far carry, of the e ring)."""
+    sizes = (C.c_int64 * 5)()
+    _lib.check(_lib.load().fac_aec_state_sizes(int(P), int(delay), sizes), "fac_aec_state_sizes")
+    return tuple(int(v) for v in sizes)
+
+
+def _aec_state(t, B, P, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (B, P, AEC_BINS, 2) or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous float64 ({B}, {P}, {AEC_BINS}, 2) on the GPU")
+    return t
+
+
+def _aec_f32(t, B, n, what):
+    if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (B, n) or not t.is_contiguous()):
+        raise ValueError(f"{what} must be contiguous float32 ({B}, {n}) on the GPU")
+    return t
+
+
+def aec_run(mic, far, p, W, X, n0=0, m0=0, n_out=None, blk0=0, n_blk=None, lens=None, starts=None, adapt=None, mic_carry=(None, None),
+            far_carry=(None, None), e_ring=None, stats=None, k=None):
+    """fac_aec_run with p = aec_params(...): the blocks blk0 .. blk0 + n_blk - 1 of [carry | mic], [carry | far] (both (B, k)
+    float32, sample i at the absolute index n0 + i) on the state W, X (B, P, 257, 2) float64, updated in place -> e[m0 .. m0 +
+    n_out) (B, n_out) float32.  mic_carry / far_carry: (in, out) pairs of two different buffers (B, 255) / (B, 511 + delay);
+    e_ring (B, 256) float32; stats (B, n_blk, 3) float64; adapt (B,) int32; lens (B,) int32 only offline; starts (B,) int64."""
+    if not isinstance(W, torch.Tensor) or not W.is_cuda:
+        raise _lib.FacodecHipError(f"aec_run: W must live on the GPU (got {getattr(W, 'device', type(W))}); there is no CPU path")
+    B = W.shape[0]
+    if mic is not None:
+        mic, far = _rows(mic, "aec_run"), _rows(far, "aec_run")
+        if mic.shape != far.shape:
+            raise ValueError(f"aec_run: mic {tuple(mic.shape)} and far {tuple(far.shape)} differ")
+    k = (mic.shape[1] if mic is not None else 0) if k is None else int(k)
+    n_out = k if n_out is None else int(n_out)
+    n_blk = aec_blocks(k) if n_blk is None else int(n_blk)
+    W, X = _aec_state(W, B, p.P, "aec_run: W"), _aec_state(X, B, p.P, "aec_run: X")
+    far_cn = _lib.AEC_FAR_CARRY + p.delay
+    y = torch.empty(B, n_out, device=W.device, dtype=torch.float32)
+    if B == 0 or n_out == 0:
+        return y
+    if stats is not None and (not stats.is_cuda or stats.dtype != torch.float64 or tuple(stats.shape) != (B, n_blk, 3) or not stats.is_contiguous()):
+        raise ValueError(f"aec_run: stats must be contiguous float64 ({B}, {n_blk}, 3) on the GPU")
+    if adapt is not None and (not isinstance(adapt, torch.Tensor) or not adapt.is_cuda or adapt.dtype != torch.int32 or tuple(adapt.shape) != (B,)
+                              or not adapt.is_contiguous()):
+        raise ValueError(f"aec_run: adapt must be contiguous int32 ({B},) on the GPU")
+    d = _lib.AecDesc()
+    d.mic_carry_in, d.mic_carry_out = (_ptr(_aec_f32(t, B, _lib.AEC_MIC_CARRY, "aec_run: mic carry")) for t in mic_carry)
+    d.far_carry_in, d.far_carry_out = (_ptr(_aec_f32(t, B, far_cn, "aec_run: far carry")) for t in far_carry)
+    d.mic = mic.data_ptr() if mic is not None and k > 0 else None
+    d.far = far.data_ptr() if far is not None and k > 0 else None
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.starts = _ptr(_i64_rows(starts, B, "aec_run: starts"))
+    d.adapt = _ptr(adapt)
+    d.W, d.X, d.e_ring, d.y, d.stats = W.data_ptr(), X.data_ptr(), _ptr(_aec_f32(e_ring, B, AEC_H, "aec_run: e_ring")), y.data_ptr(), _ptr(stats)
+    d.mic_bs = (mic.stride(0) if B > 1 else max(k, 1)) if mic is not None else max(k, 1)
+    d.far_bs = (far.stride(0) if B > 1 else max(k, 1)) if far is not None else max(k, 1)
+    d.y_bs, d.w_bs, d.xr_bs, d.s_bs = n_out, p.P * AEC_BINS * 2, p.P * AEC_BINS * 2, 3 * n_blk
+    d.n0, d.m0, d.blk0 = int(n0), int(m0), int(blk0)
+    d.mu, d.c, d.delta = p.mu, p.c, p.delta
+    d.B, d.k, d.n_out, d.n_blk, d.P, d.delay, d.far_cn = B, k, n_out, n_blk, p.P, p.delay, far_cn
+    _lib.check(_lib.load().fac_aec_run(C.byref(d), _stream()), "fac_aec_run")
+    return y
+
+
+def _aec_adapt(adapt, B, device):
+    """None, a bool, or B of them -> None or (B,) int32 on the device."""
+    if adapt is None:
+        return None
+    if isinstance(adapt, torch.Tensor):
+        if tuple(adapt.shape) != (B,):
+            raise ValueError(f"echo_cancel: adapt must be ({B},), got {tuple(adapt.shape)}")
+        return h2d(adapt, device).to(torch.int32).contiguous()
+    flags = [bool(adapt)] * B if isinstance(adapt, (bool, int)) else [bool(a) for a in adapt]
+    if len(flags) != B:
+        raise ValueError(f"echo_cancel: adapt has {len(flags)} entries for {B} rows")
+    return h2d(torch.tensor(flags, dtype=torch.int32), device)
+
+
+def echo_cancel(mic, far, lens=None, starts=None, P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0, adapt=None):
+    """Acoustic echo cancellation of mic against the far-end reference far, both (B, T) or (B, 1, T) float32 on the GPU
+     -> EchoCancelled(e, W, stats): e of mic's shape, float32, aligned with it: the microphone less the estimate
+    of the echo; W (B, P, 257, 2) float64, the filter after the row's last block (partition p holds taps 256 p .. 256 p + 255
+    as the first half of a 512-point spectrum); stats (B, M, 3) float64, M = ceil(T / 256): per block the sums of mic^2, of the
+    estimate^2 and of e^2.  A partitioned-block frequency-domain adaptive filter on blocks of 256 samples with P partitions
+    (P * 256 taps: 85 ms at 24 kHz for P = 8), overlap-save, a fully constrained gradient, the step mu / (far-end power in
+    the span + beta * P * error power + delta) per bin; the far end is used `delay` samples late, so the filter's span begins
+    there.  adapt: None, a bool or one per row; a row that does not adapt only filters.  lens (B,) int32: row b is its first
+    lens[b] samples, nothing behind them is read and e comes out 0 there.  starts (B,) int: row b's stream begins at sample
+    starts[b]; earlier samples of both signals count as zero, the filter starts from zero at block starts[b] // 256, outputs
+    before starts[b] are 0.  One C call (fac_aec_run), one workgroup per row that walks the blocks in order, no host read;
+    what streaming.EchoCanceller gives for the same signals, 256 samples earlier.  There is no delay estimator, no
+    residual-echo suppressor and no double-talk detector beyond the error term of the step.  The arithmetic is pinned in
+    include/facodec_hip.h; the defaults were not tuned by listening."""
+    p = aec_params(P, mu, beta, delta, delay)
+    m2, f2 = _rows(mic, "echo_cancel"), _rows(far, "echo_cancel")
+    if m2.shape != f2.shape:
+        raise ValueError(f"echo_cancel: mic {tuple(m2.shape)} and far {tuple(f2.shape)} differ")
+    B, T = m2.shape
+    dev = m2.device
+    M = aec_blocks(T)
+    W = torch.zeros(B, p.P, AEC_BINS, 2, device=dev, dtype=torch.float64)
+    stats = torch.zeros(B, M, 3, device=dev, dtype=torch.float64)
+    if B == 0 or T == 0:
+        return EchoCancelled(torch.zeros_like(mic), W, stats)
+    if starts is not None:
+        if not isinstance(starts, torch.Tensor) or tuple(starts.shape) != (B,) or starts.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"echo_cancel: starts must be an int32 or int64 tensor ({B},)")
+        if not starts.is_cuda and bool((starts < 0).any()):
+            raise ValueError("echo_cancel: starts must not be negative")
+        starts = h2d(starts, dev).to(torch.int64).contiguous()
+    X = torch.zeros(B, p.P, AEC_BINS, 2, device=dev, dtype=torch.float64)
+    e = aec_run(m2, f2, p, W, X, lens=lens, starts=starts, adapt=_aec_adapt(adapt, B, dev), stats=stats)
+    return EchoCancelled(e.view(mic.shape), W, stats)
+
+
 # --------------------------------------------------------------------------------- objective scores (DESIGN.md 27)
 STOI_RATE = 10000
 StoiGeometry = namedtuple("StoiGeometry", "n_frames ws_bytes_per_row energy_frames scan_block band_frames score_segments")

@@ -1508,6 +1508,153 @@ class DenoisedSession:
         return self.session.set_target(timbre)
 
 
+class EchoCanceller:
+    """Acoustic echo cancellation over B parallel streams, one block at a time:
+
+        aec = EchoCanceller(B)                               # P = 8, mu = 0.5, beta = 1.0, delta = 1e-6, delay = 0
+        e = aec.push(mic, far)                               # two (B, 1, k) or (B, k) float32 on the GPU, any k >= 1 -> mic's shape
+        tail = aec.finish()                                  # the last 256 samples
+
+    far is what goes to the loudspeaker (the `wave` of a StreamingDecoder or StreamingReceiver in the same process: a device
+    tensor already), mic what comes back from the microphone, sample for sample alongside it; `delay` samples of known
+    playout-to-capture delay move the filter's P * 256 taps to where the echo is.  The pushes and finish(), concatenated, are
+    256 zeros and then ops.echo_cancel(whole mic, whole far).e, bit for bit, for any chunking (`latency` seconds at `rate`;
+    the definition is in samples, any rate is accepted).  The filter is recursive in time; the chunking cannot show because
+    the blocks lie on an absolute grid of 256 samples and a block is computed once, when a push completes it, by the kernel of
+    the offline call.  push is one C call -- fac_aec_run, which computes the blocks the push completes, hands out the e of
+    earlier blocks that were not due yet, keeps those that are not due now, and moves the pending microphone samples and the
+    last 511 + delay far-end samples from one carry buffer into the other -- reads nothing back and allocates nothing but its
+    output.  The state is all on the device: the two carries, the spectra of the last P far-end blocks, the weights, a ring
+    of 256 e samples, the rows' starts and adapt flags.  It runs eagerly, outside the sessions' captured graphs.
+
+    set_adapt(rows, on) freezes or releases the given rows' filters from the next block on; a frozen row still filters.
+    reset(rows) restarts the given rows on the device: their stream begins at `samples`, the filter starts from zero at the
+    block that holds that sample, the 256 samples of the old stream that were not played yet come out as zeros, and the rows
+    then give row b of ops.echo_cancel(concat(old, new), concat(old, new), starts=samples), 256 samples late, bit for bit.
+    The other rows are not touched.  There is no delay estimator, no clock-drift compensation and no residual-echo
+    suppressor; the defaults were not tuned by listening."""
+
+    def __init__(self, B, rate=MODEL_RATE, P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0, adapt=True, device="cuda"):
+        self.p = ops.aec_params(P, mu, beta, delta, delay)
+        self.B, self.rate, self.device = int(B), int(rate), torch.device(device)
+        if self.B < 1:
+            raise ValueError(f"EchoCanceller: B = {B}")
+        self.delay, self.latency = ops.AEC_DELAY, ops.AEC_DELAY / self.rate
+        self.far_delay = self.p.delay
+        self.samples = 0
+        n_w, n_x, n_mic, n_far, n_e = ops.aec_state_sizes(self.p.P, self.p.delay)
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self._W = torch.zeros(self.B, self.p.P, ops.AEC_BINS, 2, device=self.device, dtype=torch.float64)
+        self._X = torch.zeros_like(self._W)
+        assert self._W[0].numel() == n_w == n_x
+        self._mic = [torch.zeros(self.B, n_mic, **f32) for _ in range(2)]
+        self._far = [torch.zeros(self.B, n_far, **f32) for _ in range(2)]
+        self._ring = torch.zeros(self.B, n_e, **f32)
+        self._start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
+        self._adapt = torch.full((self.B,), 1 if adapt else 0, device=self.device, dtype=torch.int32)
+        self._cur = 0
+        self._done = False
+
+    @property
+    def blocks(self):
+        """Blocks that are complete (on the host)."""
+        return self.samples // ops.AEC_H
+
+    def _run(self, mic, far, k, n_blk, n_out, carry_out):
+        c = self._cur
+        return ops.aec_run(mic, far, self.p, self._W, self._X, n0=self.samples, m0=self.samples - self.delay, n_out=n_out, blk0=self.blocks,
+                           n_blk=n_blk, starts=self._start, adapt=self._adapt, mic_carry=(self._mic[c], self._mic[1 - c] if carry_out else None),
+                           far_carry=(self._far[c], self._far[1 - c] if carry_out else None), e_ring=self._ring, k=k)
+
+    def push(self, mic, far):
+        if self._done:
+            raise RuntimeError("push() after finish()")
+        m, f = ops._rows(mic, "EchoCanceller.push"), ops._rows(far, "EchoCanceller.push")
+        if m.shape[0] != self.B or m.shape[1] < 1 or m.shape != f.shape:
+            raise ValueError(f"push() takes two (B = {self.B}, 1, k) or (B, k) of one length k >= 1, got {tuple(mic.shape)} and {tuple(far.shape)}")
+        k = m.shape[1]
+        y = self._run(m, f, k, (self.samples + k) // ops.AEC_H - self.blocks, k, True)
+        self._cur ^= 1
+        self.samples += k
+        return y.view(mic.shape)
+
+    def finish(self):
+        """(B, 256) float32: the samples still held back, the open block padded with zeros; the stream takes no more audio."""
+        if self._done:
+            raise RuntimeError("finish() twice")
+        self._done = True
+        return self._run(None, None, 0, 1 if self.samples % ops.AEC_H else 0, self.delay, False)
+
+    def weights(self):
+        """-> W (B, P, 257, 2) float64: the filters after the last complete block (a copy; for tests and meters)."""
+        return self._W.clone()
+
+    def _rows_idx(self, rows, what):
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.B for r in rows):
+            raise ValueError(f"{what}({rows}): rows are 0 .. {self.B - 1}")
+        return ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device) if rows else None
+
+    def set_adapt(self, rows, on):
+        """The given rows (indices on the host) adapt, or only filter, from the next block on."""
+        idx = self._rows_idx(rows, "set_adapt")
+        if idx is not None:
+            self._adapt.index_fill_(0, idx, 1 if on else 0)
+
+    def reset(self, rows):
+        """Restarts the given rows (indices on the host) as a stream that begins at `samples`, on the device."""
+        idx = self._rows_idx(rows, "reset")
+        if idx is not None:
+            self._start.index_fill_(0, idx, self.samples)
+
+
+class EchoCancelledSession:
+    """A StreamingCodec, a StreamingConverter, a ResampledSession, a LevelledSession or a DenoisedSession of one whose input
+    goes through an EchoCanceller first:
+
+        codec = EchoCancelledSession(DenoisedSession(StreamingCodec(model, timbre)), P=8, delay=0)
+        out = codec.prime(mic[:, :, :4800], far[:, :, :4800]); out = codec.push(mic[:, :, t:t + 480], far[:, :, t:t + 480])
+        out = codec.finish()
+
+    The surface and the dicts of the wrapped session (whose other attributes read through), except that prime and push take
+    the far end next to the microphone, as a device tensor of the same shape: typically the `wave` a StreamingDecoder or a
+    StreamingReceiver in the same process has just produced.  This is the outermost stage: the canceller models a linear path,
+    so it must see the microphone before any gain control or suppressor has changed it, and the other wrappers' push takes one
+    argument.  The canceller runs at the rate the session takes its audio at, eagerly, around the session's captured graphs:
+    one C call per push.  The session sees 256 zeros and then the cancelled input, cut off where the pushed audio ends;
+    `latency_in` is that delay, 256 / rate seconds, on top of the wrapped session's own.  **parameters: EchoCanceller's (P, mu,
+    beta, delta, delay, adapt), whose defaults were not tuned by listening."""
+
+    def __init__(self, session, **parameters):
+        if not hasattr(session, "prime_samples") or not session.prime_samples:
+            raise ValueError("EchoCancelledSession: this session takes codes, not audio")
+        self.session = session
+        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
+        inner = session
+        while not hasattr(inner, "B"):                               # a ResampledSession keeps them on the session it wraps
+            inner = inner.session
+        self.B, self.device = inner.B, inner.device
+        self.aec = EchoCanceller(self.B, self.rate, device=self.device, **parameters)
+        self.latency_in = self.aec.latency + getattr(session, "latency_in", 0.0)
+
+    def __getattr__(self, name):
+        if name == "session":
+            raise AttributeError(name)
+        return getattr(self.session, name)
+
+    def prime(self, first, far):
+        return self.session.prime(self.aec.push(first, far))
+
+    def push(self, hop, far):
+        return self.session.push(self.aec.push(hop, far))
+
+    def finish(self):
+        return self.session.finish()
+
+    def set_target(self, timbre):
+        return self.session.set_target(timbre)
+
+
 class ResampledSession:
     """A StreamingCodec / StreamingConverter / StreamingDecoder that takes its audio at `in_rate` and gives it at `out_rate`:
 

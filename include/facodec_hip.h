@@ -1434,6 +1434,89 @@ typedef struct fac_ns_synth_desc {
 } fac_ns_synth_desc;
 int fac_ns_synth(const fac_ns_synth_desc* d, fac_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Echo cancellation (csrc/aec.hip): a partitioned-block frequency-domain adaptive filter -- overlap-save, a fully
+ * constrained gradient, a step normalised by the far-end power in the filter's span plus the error power.  This comment is the
+ * normative definition.  The state is recursive in time: block m needs the weights block m - 1 left.  Any chunking of a stream
+ * still gives the bits of the offline call, because the block grid is absolute (from sample 0 of the session), a block is
+ * computed once, when its last sample is there, and the blocks of a row are computed in ascending order by one workgroup.
+ * Unless said otherwise every operation below is one IEEE fp64 operation with one round-to-nearest; nothing is fused.
+ *
+ * Geometry.  N = 512, H = 256, bins k = 0 .. 256, P partitions (1 .. FAC_AEC_MAX_P; P H taps).  Row b has a microphone signal d
+ * and a far-end signal x, both fp32, each the virtual concatenation [carry | block]: the block's sample i has the absolute index
+ * n0 + i and exists for i < k_b = lens ? clamp(lens[b], 0, k) : k; mic_carry_in (B, FAC_AEC_MIC_CARRY) holds the samples
+ * n0 - 255 .. n0 - 1, far_carry_in (B, far_cn), far_cn >= FAC_AEC_FAR_CARRY + delay, the samples n0 - far_cn .. n0 - 1 (NULL:
+ * zeros).  A sample of either signal before start_b = starts ? max(starts[b], 0) : 0, at or behind n0 + k_b, or before the carry
+ * is 0 and is not read.  The far end is used delayed: u[n] = x[n - delay], 0 <= delay <= FAC_AEC_MAX_DELAY.  Block m covers the
+ * samples m H .. m H + H - 1; ms_b = start_b / H.  At block ms_b every W_p = 0 and X_j = 0 for j < ms_b; a block m < ms_b
+ * computes nothing.  DFT512 and IDFT512 are the transform of the noise suppressor above, butterfly for butterfly, the inverse
+ * with its factor 1 / 512; the imaginary input of every forward transform here is 0.
+ *
+ * Per block m >= ms_b, in this order:
+ *   1. X_m = DFT512(a), a[n] = u[(m - 1) H + n], n < 512, no window; kept in the ring X (B, P, 257, 2) at slot m % P.
+ *   2. Yh[k] = sum over p = 0 .. P - 1 of W_p[k] X_{m-p}[k], from (0, 0), p ascending, a product being
+ *      (w.x x.x - w.y x.y,  w.x x.y + w.y x.x): four products, a difference, a sum; then the two additions into Yh.
+ *   3. Yf[k] = Yh[k], k <= 256, with the imaginary parts of bins 0 and 256 set to 0; Yf[512 - k] = conj(Yh[k]), k = 1 .. 255;
+ *      yh[n] = Re(IDFT512(Yf))[H + n], n < H.
+ *   4. e[n] = (double)d[m H + n] - yh[n] for m H + n < n0 + k_b, 0 behind it.  The output is (float)e[n]; outputs before start_b
+ *      and at or behind n0 + k_b are 0.
+ *   5. E = DFT512([0^H | e]), from the fp64 e.
+ *   6. S[k] = sum over p ascending of (X.x^2 + X.y^2)(X_{m-p}[k]), from 0;  den = (S[k] + c (E.x^2 + E.y^2)) + delta;
+ *      step[k] = den == 0 ? 0 : mu / den.  c = beta P is the host's, handed over as fp64.
+ *   7. Only if adapt[b] != 0 (adapt NULL: every row adapts): for every p, G_p[k] = step[k] * (conj(X_{m-p}[k]) E[k]), the product
+ *      (x.x e.x + x.y e.y,  x.x e.y - x.y e.x) first, then each part times step[k]; the full spectrum as in 3;
+ *      g = Re(IDFT512(.)), g[n] = 0 for n >= H;  W_p[k] += DFT512(g)[k], k = 0 .. 256.
+ *   8. stats_m = (sum d^2, sum yh^2, sum e^2) over the block's samples n with m H + n < n0 + k_b (others count 0), each sum by
+ *      the tree v[j] += v[j + s], j < s, for s = 128, 64, .. 1, over the 256 fp64 squares; the sum is v[0].
+ *
+ * fac_aec_run computes, per row, the blocks max(blk0, ms_b) .. min(blk0 + n_blk, ceil((n0 + k_b) / H)) - 1 and writes
+ * y[b * y_bs + i] = (float)e[m0 + i], i < n_out: of a block of this call directly; of a block before blk0 from e_ring
+ * (B, FAC_AEC_H) fp32, sample n at slot n % 256; 0 before start_b, behind the row's last block, below sample 0, and without a
+ * ring.  An e of this call at or behind m0 + n_out is written into the ring for a later call (dropped without one).  stats,
+ * NULL or (B, n_blk, 3) fp64 of row pitch s_bs: block m at index m - blk0, zeros for a block the row does not compute.
+ * mic_carry_out / far_carry_out, NULL or buffers OTHER than the inputs: the last 255 / far_cn samples up to n0 + k - 1, written
+ * by a second workgroup per row.  W (B, P, 257, 2) and X (B, P, 257, 2) fp64, row pitches w_bs and xr_bs doubles, are read
+ * (unless the call contains block ms_b) and written in place; only row b's workgroup touches row b's state.  Offline: n0 = m0 =
+ * blk0 = 0, n_out = k, n_blk = ceil(k / H), no carries, no ring.  A stream keeps the grid with a delay of D = H = 256 samples:
+ * after n samples the blocks below n / H are complete, so a push of k samples at n0 is blk0 = n0 / H, n_blk = (n0 + k) / H - blk0,
+ * m0 = n0 - 256, n_out = k; the flush is k = 0, n_blk = 1 if n0 % H else 0, m0 = n0 - 256, n_out = 256.
+ * One 512-thread workgroup per row walks the blocks; steps 1 and 3 to 5 are one wave's transforms, 2 and 6 one thread per bin,
+ * 7 one wave per partition in ceil(P / 8) rounds.  P <= FAC_AEC_LDS_P keeps W and the X ring in LDS for the call (84160 +
+ * 8224 P bytes of dynamic LDS), a larger P works on them in global memory; the arithmetic is the same.
+ * Refused before any launch: a NULL descriptor, W, X or y; mic or far NULL with k > 0; B outside 1 .. 65535; P outside 1 ..
+ * FAC_AEC_MAX_P; mu not in [0, 1]; c or delta negative or not finite; delay outside 0 .. FAC_AEC_MAX_DELAY; k outside 0 .. 2^30;
+ * n_out outside 1 .. 2^30; n_blk, n0 or blk0 negative; lens with a carry or a ring; a carry_out that is its carry_in; W and X
+ * the same buffer; far_cn < 511 + delay with a far carry; w_bs or xr_bs below 514 P, mic_bs or far_bs below k, y_bs below n_out,
+ * s_bs below 3 n_blk, with B > 1; a block blk0 that starts in front of the carries; with a ring, outputs that reach more than
+ * 256 samples in front of block blk0, or more than 256 computed samples that are not due.
+ *
+ * fac_aec_state_sizes: the per-row sizes of a stream's state for (P, delay) into sizes[0 .. 4]: doubles of W, doubles of X,
+ * floats of the mic carry, floats of the far carry, floats of the e ring.
+ * ---------------------------------------------------------------------------------------- */
+enum { FAC_AEC_N = 512, FAC_AEC_H = 256, FAC_AEC_BINS = 257, FAC_AEC_MAX_P = 32, FAC_AEC_LDS_P = 8, FAC_AEC_MAX_DELAY = 16384,
+       FAC_AEC_MIC_CARRY = 255, FAC_AEC_FAR_CARRY = 511 };
+typedef struct fac_aec_desc {
+  const float* mic_carry_in;  /* (B, 255) or NULL */
+  float* mic_carry_out;       /* (B, 255) or NULL, never mic_carry_in */
+  const float* far_carry_in;  /* (B, far_cn) or NULL */
+  float* far_carry_out;       /* (B, far_cn) or NULL, never far_carry_in */
+  const float* mic;           /* (B, k), pitch mic_bs */
+  const float* far;           /* (B, k), pitch far_bs */
+  const int32_t* lens;        /* (B) or NULL */
+  const int64_t* starts;      /* (B) or NULL */
+  const int32_t* adapt;       /* (B) or NULL: every row adapts */
+  double* W;                  /* read and written: (B, P, 257, 2), row pitch w_bs doubles */
+  double* X;                  /* read and written: (B, P, 257, 2), row pitch xr_bs doubles, block j at slot j % P */
+  float* e_ring;              /* read and written: (B, 256), or NULL */
+  float* y;                   /* written: (B, n_out), pitch y_bs */
+  double* stats;              /* written: (B, n_blk, 3), row pitch s_bs doubles, or NULL */
+  int64_t mic_bs, far_bs, y_bs, w_bs, xr_bs, s_bs, n0, m0, blk0;
+  double mu, c, delta;
+  int32_t B, k, n_out, n_blk, P, delay, far_cn, reserved;
+} fac_aec_desc;
+int fac_aec_run(const fac_aec_desc* d, fac_stream_t stream);
+int fac_aec_state_sizes(int P, int delay, int64_t* sizes);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
