@@ -13,6 +13,7 @@
 // P <= FAC_AEC_LDS_P keeps them in LDS (aec_kernel<true>), a larger P works on the global buffers, which stay in L2.
 #include "common.h"
 #include "fft512_f64.h"
+#include "stream_src.h"
 #include <math.h>
 
 namespace fac {
@@ -22,21 +23,6 @@ constexpr int AEC_N = FAC_AEC_N, AEC_H = FAC_AEC_H, AEC_BINS = FAC_AEC_BINS;
 constexpr int AEC_BINS_PAD = 264;
 static_assert(AEC_N == FFT512_N && AEC_N == 2 * AEC_H && AEC_BINS == AEC_H + 1, "echo canceller geometry");
 static_assert(FAC_AEC_MIC_CARRY == AEC_H - 1 && FAC_AEC_FAR_CARRY == AEC_N - 1 && FAC_AEC_LDS_P == AEC_WAVES, "echo canceller geometry");
-
-// Sample n (absolute) of one row of [carry | block]: 0 before the row's start and at or behind its end.
-struct AecSrc {
-  const float* carry;       // the row's cn samples in front of the block, or nullptr
-  const float* x;           // the row's block
-  int cn;
-  long long n0, start, end;
-};
-__device__ __forceinline__ float aec_sample(const AecSrc& s, long long n) {
-  if (n < s.start || n >= s.end) return 0.f;
-  long long r = n - s.n0;
-  if (r >= 0) return s.x[r];
-  r += s.cn;
-  return s.carry && r >= 0 ? s.carry[r] : 0.f;
-}
 
 struct AecArgs {
   fac_aec_desc d;
@@ -52,31 +38,13 @@ __global__ __launch_bounds__(AEC_T) void aec_kernel(AecArgs a) {
   const fac_aec_desc& d = a.d;
   const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int P = d.P;
-  int kb = d.k;
-  if (d.lens) {
-    const int len = d.lens[b];
-    kb = len < 0 ? 0 : (len < d.k ? len : d.k);
-  }
-  const long long start = d.starts ? (d.starts[b] > 0 ? d.starts[b] : 0) : 0;
-  const long long end = d.n0 + kb;
-  AecSrc mic, far;
-  mic.carry = d.mic_carry_in ? d.mic_carry_in + (long long)b * FAC_AEC_MIC_CARRY : nullptr;
-  mic.x = d.mic ? d.mic + (long long)b * d.mic_bs : nullptr;
-  mic.cn = FAC_AEC_MIC_CARRY;
-  far.carry = d.far_carry_in ? d.far_carry_in + (long long)b * d.far_cn : nullptr;
-  far.x = d.far ? d.far + (long long)b * d.far_bs : nullptr;
-  far.cn = d.far_cn;
-  mic.n0 = far.n0 = d.n0, mic.start = far.start = start, mic.end = far.end = end;
+  const StreamSrc mic = stream_src(d.mic_carry_in, FAC_AEC_MIC_CARRY, d.mic, d.mic_bs, d.lens, d.starts, d.n0, d.k, b);
+  const StreamSrc far = stream_src_like(mic, d.far_carry_in, d.far_cn, d.far, d.far_bs, b);
+  const long long start = mic.start, end = mic.end;
 
   if (blockIdx.x == 1) {                                 // the row's next carries
-    if (d.mic_carry_out) {
-      float* out = d.mic_carry_out + (long long)b * FAC_AEC_MIC_CARRY;
-      for (int t = tid; t < FAC_AEC_MIC_CARRY; t += AEC_T) out[t] = aec_sample(mic, d.n0 + d.k - FAC_AEC_MIC_CARRY + t);
-    }
-    if (d.far_carry_out) {
-      float* out = d.far_carry_out + (long long)b * d.far_cn;
-      for (int t = tid; t < d.far_cn; t += AEC_T) out[t] = aec_sample(far, d.n0 + d.k - d.far_cn + t);
-    }
+    if (d.mic_carry_out) stream_carry_out(mic, d.mic_carry_out, d.k, b, tid, AEC_T);
+    if (d.far_carry_out) stream_carry_out(far, d.far_carry_out, d.k, b, tid, AEC_T);
     return;
   }
 
@@ -137,7 +105,7 @@ __global__ __launch_bounds__(AEC_T) void aec_kernel(AecArgs a) {
 #pragma unroll
       for (int r = 0; r < AEC_N / 64; ++r) {
         const int n = lane + 64 * r;
-        z0[n] = make_double2((double)aec_sample(far, base + n), 0.0);
+        z0[n] = make_double2((double)far.sample(base + n), 0.0);
       }
       fft512_forward(z0, tw, lane);
       for (int k = lane; k < AEC_BINS; k += 64) X[mm * AEC_BINS + k] = z0[fft512_rev(k)];
@@ -145,7 +113,7 @@ __global__ __launch_bounds__(AEC_T) void aec_kernel(AecArgs a) {
 #pragma unroll
       for (int r = 0; r < AEC_H / 64; ++r) {
         const int n = lane + 64 * r;
-        dm[n] = (double)aec_sample(mic, m * AEC_H + n);
+        dm[n] = (double)mic.sample(m * AEC_H + n);
       }
     }
     __syncthreads();

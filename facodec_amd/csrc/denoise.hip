@@ -5,13 +5,14 @@
 // contracts: the header comment of include/facodec_hip.h.  All fp64 on the vector pipe, no matrix pipe, no atomics, every word
 // has one writer; the build runs with -ffp-contract=off.
 //
-// The transform is the scheme of stoi_bands_kernel (csrc/metrics.hip), copied: one wave per frame, four frames per 256-thread
-// workgroup, a 512-entry double2 buffer per wave, in-place radix-2 decimation in frequency (bin k ends at the bit-reversed
-// index), twiddles from a 256-entry table the workgroup computes once with sincospi.  The inverse runs the same flow graph
-// backwards (decimation in time from bit-reversed input, conjugated twiddles), so no reordering pass is needed in between.  A
-// wave's buffer is private to it; the barriers between the stages order that wave's own LDS traffic and every loop that holds
-// one has a workgroup-uniform trip count.
+// The transform is fft512_f64.h's: one wave per frame, four frames per 256-thread workgroup, a 512-entry double2 buffer per
+// wave, transformed in place (bin k ends at the bit-reversed index; the inverse starts from that order).  A wave's buffer is
+// private to it while it transforms, so the stages are ordered inside the wave and a wave without a frame skips the transform;
+// workgroup barriers stand only where waves exchange data: behind the tables, and around the synthesis kernel's overlap-add.
+// The input is a StreamSrc (stream_src.h) over [carry | block] with a carry of NS_CARRY samples.
 #include "common.h"
+#include "fft512_f64.h"
+#include "stream_src.h"
 #include <math.h>
 
 namespace fac {
@@ -24,83 +25,23 @@ constexpr int NS_GF = 64, NS_GK = 16, NS_GQ = 4;   // the gain kernel's tile: fr
 static_assert(NS_GF == (NS_T / NS_GK) * NS_GQ, "one thread per (bin, four frames) of the tile");
 static_assert(NS_N == 2 * NS_H && NS_BINS == NS_H + 1 && NS_CARRY == 2 * NS_N - 1, "noise suppressor geometry");
 
-// Sample n (absolute) of row b of [carry | block]: 0 before the row's start and at or behind its end.
-struct NsSrc {
-  const float* carry;       // the row's NS_CARRY samples in front of the block, or nullptr
-  const float* x;           // the row's block
-  long long n0, start, end;
-};
-__device__ __forceinline__ float ns_sample(const NsSrc& s, long long n) {
-  if (n < s.start || n >= s.end) return 0.f;
-  long long r = n - s.n0;
-  if (r >= 0) return s.x[r];
-  r += NS_CARRY;
-  return s.carry && r >= 0 ? s.carry[r] : 0.f;
-}
-__device__ __forceinline__ NsSrc ns_src(const float* carry_in, const float* x, long long x_bs, const int32_t* lens, const int64_t* starts,
-                                        long long n0, int k, int b) {
-  NsSrc s;
-  s.carry = carry_in ? carry_in + (long long)b * NS_CARRY : nullptr;
-  s.x = x ? x + (long long)b * x_bs : nullptr;
-  int kb = k;
-  if (lens) {
-    const int len = lens[b];
-    kb = len < 0 ? 0 : (len < k ? len : k);
-  }
-  s.n0 = n0, s.end = n0 + kb;
-  s.start = starts ? (starts[b] > 0 ? starts[b] : 0) : 0;
-  return s;
-}
+static_assert(NS_N == FFT512_N && NS_T == FFT512_N / 2, "one thread per twiddle and per two window entries");
 
-__device__ __forceinline__ void ns_tables(double2* tw, double* win, int tid) {
-  double s, c;
-  sincospi((double)tid / (double)(NS_N / 2), &s, &c);
-  tw[tid] = make_double2(c, -s);                    // exp(-2 pi i tid / 512)
+// win[n] = sin(pi n / 512)
+__device__ __forceinline__ void ns_window(double* win, int tid) {
   win[tid] = sinpi((double)tid / (double)NS_N);
   win[tid + NS_T] = sinpi((double)(tid + NS_T) / (double)NS_N);
 }
 
 // z[n] = (w[n] * sample((f - 1) H + n), 0)
-__device__ __forceinline__ void ns_load(double2* z, const double* win, const NsSrc& src, long long f, int lane) {
+__device__ __forceinline__ void ns_load(double2* z, const double* win, const StreamSrc& src, long long f, int lane) {
   const long long base = (f - 1) * NS_H;
 #pragma unroll
   for (int r = 0; r < NS_N / 64; ++r) {
     const int n = lane + 64 * r;
-    z[n] = make_double2(win[n] * (double)ns_sample(src, base + n), 0.0);
+    z[n] = make_double2(win[n] * (double)src.sample(base + n), 0.0);
   }
 }
-
-// one stage of the forward transform: the butterflies of stoi_bands_kernel
-__device__ __forceinline__ void ns_dif(double2* z, const double2* tw, int lane, int half) {
-  const int step = (NS_N / 2) / half;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = lane + 64 * r;
-    const int pos = i & (half - 1);
-    const int lo = ((i - pos) << 1) + pos, hi = lo + half;
-    const double2 u = z[lo], v = z[hi], t = tw[pos * step];
-    const double dx = u.x - v.x, dy = u.y - v.y;
-    z[lo] = make_double2(u.x + v.x, u.y + v.y);
-    z[hi] = make_double2(dx * t.x - dy * t.y, dx * t.y + dy * t.x);
-  }
-}
-
-// one stage of the inverse: q = v * conj(t), (u, v) <- (u + q, u - q)
-__device__ __forceinline__ void ns_dit(double2* z, const double2* tw, int lane, int half) {
-  const int step = (NS_N / 2) / half;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = lane + 64 * r;
-    const int pos = i & (half - 1);
-    const int lo = ((i - pos) << 1) + pos, hi = lo + half;
-    const double2 u = z[lo], v = z[hi], t = tw[pos * step];
-    const double qx = v.x * t.x + v.y * t.y, qy = v.y * t.x - v.x * t.y;
-    z[lo] = make_double2(u.x + qx, u.y + qy);
-    z[hi] = make_double2(u.x - qx, u.y - qy);
-  }
-}
-
-__device__ __forceinline__ int ns_rev(int k) { return (int)(__brev((unsigned)k) >> 23); }   // 9-bit reversal
 
 // ---- power
 
@@ -117,36 +58,29 @@ __global__ __launch_bounds__(NS_T) void ns_power_kernel(NsPowerArgs a) {
   __shared__ double win[NS_N];
   const fac_ns_power_desc& d = a.d;
   const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const NsSrc src = ns_src(d.carry_in, d.x, d.x_bs, d.lens, d.starts, d.n0, d.k, b);
+  const StreamSrc src = stream_src(d.carry_in, NS_CARRY, d.x, d.x_bs, d.lens, d.starts, d.n0, d.k, b);
   if ((int)blockIdx.x == a.n_tiles) {
-    float* out = d.carry_out + (long long)b * NS_CARRY;
-    for (int t = tid; t < NS_CARRY; t += NS_T) out[t] = ns_sample(src, d.n0 + d.k - NS_CARRY + t);
+    stream_carry_out(src, d.carry_out, d.k, b, tid, NS_T);
     return;
   }
-  ns_tables(tw, win, tid);
-  __syncthreads();
+  fft512_table(tw, tid);
+  ns_window(win, tid);
+  __syncthreads();                                     // the tables: written by all four waves, read by each
   const int i0 = blockIdx.x * NS_PF;
   const int n_t = d.n_new - i0 < NS_PF ? d.n_new - i0 : NS_PF;
   double2* z = buf[wave];
-  for (int it = 0; it * 4 < n_t; ++it) {
-    const int i = i0 + it * 4 + wave;
-    const bool valid = it * 4 + wave < n_t;            // wave-uniform
-    const long long f = d.f0 + i;
-    if (valid) ns_load(z, win, src, f, lane);
-    __syncthreads();
-    for (int half = NS_N / 2; half >= 1; half >>= 1) {
-      if (valid) ns_dif(z, tw, lane, half);
-      __syncthreads();
+  // no wave reads another's buffer: no workgroup barrier in this loop, and its trip count is the wave's own
+  for (int i = wave; i < n_t; i += 4) {
+    const long long f = d.f0 + i0 + i;
+    ns_load(z, win, src, f, lane);
+    fft512_forward(z, tw, lane);
+    const long long at = (long long)b * d.p_bs + (f % d.R) * NS_BINS;
+    for (int k = lane; k < NS_BINS; k += 64) {
+      const double2 v = z[fft512_rev(k)];
+      d.P[at + k] = v.x * v.x + v.y * v.y;
+      if (d.X) reinterpret_cast<double2*>(d.X)[at + k] = v;
     }
-    if (valid) {
-      const long long at = (long long)b * d.p_bs + (f % d.R) * NS_BINS;
-      for (int k = lane; k < NS_BINS; k += 64) {
-        const double2 v = z[ns_rev(k)];
-        d.P[at + k] = v.x * v.x + v.y * v.y;
-        if (d.X) reinterpret_cast<double2*>(d.X)[at + k] = v;
-      }
-    }
-    __syncthreads();
+    fft512_wave_sync();                                // the lanes have read the spectrum before the next frame overwrites it
   }
 }
 
@@ -262,42 +196,35 @@ __global__ __launch_bounds__(NS_T) void ns_synth_kernel(NsSynthArgs a) {
   __shared__ double prev[NS_H];
   const fac_ns_synth_desc& d = a.d;
   const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const NsSrc src = ns_src(d.carry_in, d.x, d.x_bs, d.lens, d.starts, d.n0, d.k, b);
+  const StreamSrc src = stream_src(d.carry_in, NS_CARRY, d.x, d.x_bs, d.lens, d.starts, d.n0, d.k, b);
   const long long fs = src.start / NS_H;
   const long long s0 = a.s_first + (long long)blockIdx.x * (NS_SF - 1);
   const long long s_end = s0 + NS_SF - 2 < a.s_last ? s0 + NS_SF - 2 : a.s_last;
   const int n_f = (int)(s_end - s0) + 2;             // frames s0 .. s_end + 1
-  ns_tables(tw, win, tid);
-  __syncthreads();
+  fft512_table(tw, tid);
+  ns_window(win, tid);
+  __syncthreads();                                     // the tables: written by all four waves, read by each
   double2* z = buf[wave];
   float* yrow = d.y + (long long)b * d.y_bs;
-  for (int it = 0; it * 4 < n_f; ++it) {
+  for (int it = 0; it * 4 < n_f; ++it) {               // two workgroup barriers per round: the trip count is the workgroup's
     const bool valid = it * 4 + wave < n_f;            // wave-uniform
     const long long f = s0 + it * 4 + wave;
     const bool live = valid && f >= fs;                // f >= fs >= 0: a frame of the row's current stream
     const long long gat = (long long)b * d.g_bs + (live ? f % d.R : 0) * NS_BINS;
-    if (live && !d.X) ns_load(z, win, src, f, lane);
-    __syncthreads();
-    if (!d.X) {
-      for (int half = NS_N / 2; half >= 1; half >>= 1) {
-        if (live) ns_dif(z, tw, lane, half);
-        __syncthreads();
+    if (live) {                                        // the wave alone in its buffer
+      if (!d.X) {
+        ns_load(z, win, src, f, lane);
+        fft512_forward(z, tw, lane);
       }
-    }
-    if (live) {
       // Y[k] = G[k] X[k], k = 0 .. 256; Y[512 - k] = conj(Y[k]), k = 1 .. 255
       for (int k = lane; k < NS_BINS; k += 64) {
-        const double2 v = d.X ? reinterpret_cast<const double2*>(d.X)[gat + k] : z[ns_rev(k)];
+        const double2 v = d.X ? reinterpret_cast<const double2*>(d.X)[gat + k] : z[fft512_rev(k)];
         const double g = d.G[gat + k];
         const double2 y = make_double2(g * v.x, g * v.y);
-        z[ns_rev(k)] = y;
-        if (k >= 1 && k < NS_H) z[ns_rev(NS_N - k)] = make_double2(y.x, -y.y);
+        z[fft512_rev(k)] = y;
+        if (k >= 1 && k < NS_H) z[fft512_rev(NS_N - k)] = make_double2(y.x, -y.y);
       }
-    }
-    __syncthreads();
-    for (int half = 1; half <= NS_N / 2; half <<= 1) {
-      if (live) ns_dit(z, tw, lane, half);
-      __syncthreads();
+      fft512_inverse(z, tw, lane);
     }
     if (valid) {
 #pragma unroll
@@ -306,7 +233,7 @@ __global__ __launch_bounds__(NS_T) void ns_synth_kernel(NsSynthArgs a) {
         z[n].x = live ? win[n] * (z[n].x * (1.0 / NS_N)) : 0.0;
       }
     }
-    __syncthreads();
+    __syncthreads();                                   // every wave's v_f, and prev[] of the round before, for the overlap-add
     if (valid && it * 4 + wave > 0) {                  // segment f - 1 >= s0
       const long long mb = (f - 1) * NS_H;
 #pragma unroll
@@ -320,10 +247,12 @@ __global__ __launch_bounds__(NS_T) void ns_synth_kernel(NsSynthArgs a) {
         }
       }
     }
+    // the overlap-add has read prev[] and the neighbours' buffers: wave 3 may overwrite prev[], the next round the buffers
     __syncthreads();
     if (wave == 3) {
 #pragma unroll
       for (int r = 0; r < NS_H / 64; ++r) prev[lane + 64 * r] = z[NS_H + lane + 64 * r].x;
+      fft512_wave_sync();                              // read by its lanes before the next round's spectrum goes into z
     }
   }
 }

@@ -1,8 +1,9 @@
-// The 512-point fp64 transform of DESIGN.md 33.1 as device functions: the radix-2 decimation in frequency of stoi_bands_kernel
-// (csrc/metrics.hip) and ns_power_kernel (csrc/denoise.hip), butterfly for butterfly, and the same flow graph run backwards.
-// One wave transforms one 512-entry double2 buffer in LDS in place; bin k of the forward transform ends at the bit-reversed
-// index fft512_rev(k), and the inverse starts from that order, so no reordering pass lies between the two.  The twiddles come
-// from a 256-entry table the workgroup computes once with sincospi.  metrics.hip and denoise.hip keep their own copies.
+// The 512-point fp64 transform of DESIGN.md 33.1 as device functions, the one copy every kernel that transforms uses:
+// stoi_bands_kernel (csrc/metrics.hip), ns_power_kernel and ns_synth_kernel (csrc/denoise.hip), aec_kernel (csrc/aec.hip).  A
+// radix-2 decimation in frequency, and the same flow graph run backwards (decimation in time from bit-reversed input,
+// conjugated twiddles).  One wave transforms one 512-entry double2 buffer in LDS in place; bin k of the forward transform ends
+// at the bit-reversed index fft512_rev(k), and the inverse starts from that order, so no reordering pass lies between the two.
+// The twiddles come from a 256-entry table the workgroup computes once with sincospi and publishes with a workgroup barrier.
 //
 // A buffer belongs to one wave, so the stages of a whole transform are ordered by fft512_wave_sync(), not by a workgroup
 // barrier: the 64 lanes run in lockstep, LDS operations of one wave retire in order, and the fence keeps the compiler from

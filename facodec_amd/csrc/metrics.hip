@@ -16,10 +16,10 @@
 //   stoi_select_kernel  one workgroup per row: maximum of E, then blocks of 256 frames: keep flag, inclusive scan in LDS, carried
 //                       offset; writes the kept frame indices in order (-1 behind them) and n_frames / n_kept.
 //   stoi_bands_kernel   one wave per (kept frame, signal): the frame of the compacted signal is rebuilt from the kept frame and
-//                       its kept neighbours, windowed again and transformed in LDS by an in-place radix-2 decimation-in-frequency
-//                       FFT of 512 complex points (9 stages of 256 butterflies, 4 per lane; twiddles from a 256-entry table the
-//                       workgroup computes once with sincospi); bin k then sits at the bit-reversed index.  The 212 powers of
-//                       bins 7 .. 218 go to LDS and 15 lanes add their band in ascending bin order.  32 frames per workgroup:
+//                       its kept neighbours, windowed again and transformed in LDS by the wave's own 512-point transform of
+//                       fft512_f64.h (twiddles from a 256-entry table the workgroup computes once with sincospi); bin k then
+//                       sits at the bit-reversed index.  The 212 powers of bins 7 .. 218 go to LDS and 15 lanes add their
+//                       band in ascending bin order, both ordered inside the wave.  32 frames per workgroup:
 //                       4 waves x 16 rounds, wave w of round i takes transform 4 i + w = (frame 2 i + w / 2, signal w & 1).
 //                       x and y are transformed separately (not packed as real and imaginary part of one transform): a zero
 //                       reference must give exact zeros, which the packed form's 1e-16 leakage from y would not.
@@ -28,9 +28,11 @@
 //                       normalisation, written to LDS), lanes 0 .. 29 then one column each, lane 0 adds both in ascending order.
 //   stoi_finish_kernel  per row, the segment sums in a fixed order -> stoi, estoi, n_segments.
 // Nothing depends on scheduling and nothing is accumulated with atomics: two runs, and a row alone or in a batch, give the same
-// bits.  All LDS of the band and score kernels is private to one wave except the read-only tables and tile, so the barriers
-// between their stages order one wave's own LDS traffic; every loop with a barrier has a workgroup-uniform trip count.
+// bits.  All LDS of the band and score kernels is private to one wave except the read-only tables and tile: the band kernel
+// has one workgroup barrier, behind its tables, and orders a wave's own LDS traffic inside the wave; the score kernel's barriers
+// between its stages do the same job, and every loop with a barrier has a workgroup-uniform trip count.
 #include "common.h"
+#include "fft512_f64.h"
 #include <math.h>
 
 namespace fac {
@@ -50,6 +52,7 @@ constexpr int ST_BIN0 = 7, ST_BIN1 = 219;      // bins the bands cover
 constexpr double ST_EPS = 2.220446049250313e-16;
 constexpr double ST_DYN = 40.0;
 constexpr double SD_EPS = 1e-8;
+static_assert(ST_NFFT == FFT512_N && MT_T == FFT512_N / 2 && MT_T == ST_FRAME, "one thread per twiddle and per window entry");
 static_assert(ST_FE % 4 == 0 && ST_FB % 2 == 0 && ST_SS % 4 == 0, "four waves share a workgroup's frames / segments evenly");
 
 __constant__ int st_lo[ST_BANDS] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174};
@@ -236,71 +239,49 @@ __global__ __launch_bounds__(MT_T) void stoi_bands_kernel(StArgs a) {
   const int K = a.n_kept[b];
   const int j0 = blockIdx.x * ST_FB;
   if (j0 >= K) return;                              // the whole workgroup, before any barrier
-  {
-    double s, c;
-    sincospi((double)tid / (double)(ST_NFFT / 2), &s, &c);
-    tw[tid] = make_double2(c, -s);                  // exp(-2 pi i tid / 512)
-    win[tid] = st_window(tid);
-  }
-  __syncthreads();
+  fft512_table(tw, tid);
+  win[tid] = st_window(tid);
+  __syncthreads();                                  // the tables: written by all four waves, read by each
   const int32_t* __restrict__ kept = a.kept_idx + (long long)b * a.M_max;
   double2* z = buf[wave];
 
+  // buf[wave] and pw[wave] are the wave's own and nothing else is written: no workgroup barrier in this loop, the wave orders
+  // its own LDS traffic and leaves when its frames run out
   for (int it = 0; it < ST_FB / 2; ++it) {
     const int q = it * 4 + wave;
     const int jj = j0 + (q >> 1), sig = q & 1;
-    const bool valid = jj < K;                      // wave-uniform
-    if (valid) {
-      const float* __restrict__ src = sig ? a.y + b * a.y_bs : a.x + b * a.x_bs;
-      const long long k = kept[jj];
-      const long long kp = jj > 0 ? kept[jj - 1] : -1, kn = jj + 1 < K ? kept[jj + 1] : -1;
+    if (jj >= K) break;                             // wave-uniform, and jj only grows
+    const float* __restrict__ src = sig ? a.y + b * a.y_bs : a.x + b * a.x_bs;
+    const long long k = kept[jj];
+    const long long kp = jj > 0 ? kept[jj - 1] : -1, kn = jj + 1 < K ? kept[jj + 1] : -1;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = lane + 64 * r;
-        double c = win[n] * (double)src[k * ST_HOP + n];
-        if (n < ST_HOP) {
-          if (kp >= 0) c = win[n + ST_HOP] * (double)src[kp * ST_HOP + n + ST_HOP] + c;
-        } else {
-          if (kn >= 0) c = c + win[n - ST_HOP] * (double)src[kn * ST_HOP + n - ST_HOP];
-        }
-        z[n] = make_double2(win[n] * c, 0.0);
-        z[n + ST_FRAME] = make_double2(0.0, 0.0);
+    for (int r = 0; r < 4; ++r) {
+      const int n = lane + 64 * r;
+      double c = win[n] * (double)src[k * ST_HOP + n];
+      if (n < ST_HOP) {
+        if (kp >= 0) c = win[n + ST_HOP] * (double)src[kp * ST_HOP + n + ST_HOP] + c;
+      } else {
+        if (kn >= 0) c = c + win[n - ST_HOP] * (double)src[kn * ST_HOP + n - ST_HOP];
+      }
+      z[n] = make_double2(win[n] * c, 0.0);
+      z[n + ST_FRAME] = make_double2(0.0, 0.0);
+    }
+    fft512_forward(z, tw, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int kbin = ST_BIN0 + lane + 64 * r;
+      if (kbin < ST_BIN1) {
+        const double2 v = z[fft512_rev(kbin)];
+        pw[wave][kbin - ST_BIN0] = v.x * v.x + v.y * v.y;
       }
     }
-    __syncthreads();
-    for (int half = ST_NFFT / 2; half >= 1; half >>= 1) {
-      if (valid) {
-        const int step = (ST_NFFT / 2) / half;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = lane + 64 * r;
-          const int pos = i & (half - 1);
-          const int lo = ((i - pos) << 1) + pos, hi = lo + half;
-          const double2 u = z[lo], v = z[hi], t = tw[pos * step];
-          const double dx = u.x - v.x, dy = u.y - v.y;
-          z[lo] = make_double2(u.x + v.x, u.y + v.y);
-          z[hi] = make_double2(dx * t.x - dy * t.y, dx * t.y + dy * t.x);
-        }
-      }
-      __syncthreads();
-    }
-    if (valid) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kbin = ST_BIN0 + lane + 64 * r;
-        if (kbin < ST_BIN1) {
-          const double2 v = z[__brev((unsigned)kbin) >> 23];       // 9-bit reversal
-          pw[wave][kbin - ST_BIN0] = v.x * v.x + v.y * v.y;
-        }
-      }
-    }
-    __syncthreads();
-    if (valid && lane < ST_BANDS) {
+    fft512_wave_sync();                             // the powers, for the lanes that add the bands
+    if (lane < ST_BANDS) {
       double s = 0.0;
       for (int kbin = st_lo[lane]; kbin < st_hi[lane]; ++kbin) s += pw[wave][kbin - ST_BIN0];
       a.Tb[(((long long)b * 2 + sig) * ST_BANDS + lane) * a.M_max + jj] = sqrt(s);
     }
-    __syncthreads();
+    fft512_wave_sync();                             // read before the next round overwrites pw[wave] and the buffer
   }
 }
 

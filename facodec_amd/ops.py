@@ -64,6 +64,36 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _on_gpu(t, what):
+    """The refusal every entry shares: a missing kernel path is an error, not a detour over the CPU."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.FacodecHipError(f"{what} must live on the GPU (got {getattr(t, 'device', type(t))}); there is no CPU path")
+    return t
+
+
+def _row_pitch(t, B, k):
+    """The row pitch of t (B, ...) for a descriptor, in elements: its stride, or k where a single row's stride says nothing
+    (and for no tensor at all)."""
+    return t.stride(0) if t is not None and B > 1 else k
+
+
+def _arg(t, what, dtype, shape, at_least=False, optional=False):
+    """A tensor argument of a descriptor builder: `dtype`, on the GPU, and either exactly `shape` and contiguous or, with
+    at_least, shape = (B, n): (B, >= n) with dense columns at any row pitch.  None passes where it is optional.  ValueError names
+    the argument by `what`."""
+    if t is None and optional:
+        return None
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype:
+        if not at_least:
+            if t.shape == shape and t.is_contiguous():
+                return t
+        elif t.dim() == 2 and t.shape[0] == shape[0] and t.shape[1] >= shape[1] and (t.shape[1] <= 1 or t.stride(1) == 1):
+            return t
+    name = str(dtype).replace("torch.", "")
+    want = f"{name} ({shape[0]}, >= {shape[1]}) on the GPU with dense rows" if at_least else f"contiguous {name} {tuple(shape)} on the GPU"
+    raise ValueError(f"{what} must be {want}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
 def _dev(t, what="tensor"):
     if t is None:
         return None
@@ -1709,8 +1739,8 @@ def _rows(x, what):
     """(B, T) or (B, 1, T) float32 on the device -> the (B, T) view with dense samples."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
         raise ValueError(f"{what} takes (B, T) or (B, 1, T), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
-    if not x.is_cuda:
-        raise _lib.FacodecHipError(f"{what}: x must live on the GPU (got {x.device}); there is no CPU path")
+    if not x.is_cuda:                                               # checked in line: every push comes through here
+        _on_gpu(x, f"{what}: x")
     if x.dtype != torch.float32:
         raise _lib.FacodecHipError(f"{what}: x must be float32 (got {x.dtype})")
     x2 = x.reshape(x.shape[0], x.shape[-1]) if x.dim() == 3 else x
@@ -1740,17 +1770,15 @@ def loudness_energies(x, rate=24000, lens=None, state=None, offset=0, out=None, 
         if offset:
             raise ValueError("loudness_energies: offset > 0 adds to out[:, 0]; pass out=")
         out = torch.empty(B, n_sub, device=dev, dtype=torch.float64)
-    elif out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_sub or (out.shape[1] > 1 and out.stride(1) != 1) \
-            or not out.is_cuda:
-        raise ValueError(f"loudness_energies: out must be float64 ({B}, >= {n_sub}) on the GPU with dense rows, got {out.dtype} {tuple(out.shape)}")
+    else:
+        _arg(out, "loudness_energies: out", torch.float64, (B, n_sub), at_least=True)
     acc = peak is not None
     if peak is None:
         peak = torch.empty(B, device=dev, dtype=torch.float32)
     if state is not None and state_out is None:
         state_out = torch.empty(B, 4, device=dev, dtype=torch.float64)
-    for t, name in ((state, "state"), (state_out, "state_out")):
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (B, 4) or not t.is_contiguous() or not t.is_cuda):
-            raise ValueError(f"loudness_energies: {name} must be contiguous float64 ({B}, 4) on the GPU")
+    _arg(state, "loudness_energies: state", torch.float64, (B, 4), optional=True)
+    _arg(state_out, "loudness_energies: state_out", torch.float64, (B, 4), optional=True)
     if B == 0:
         return LoudnessEnergies(out[:, :n_sub], peak, state_out)
     lib = _lib.load()
@@ -1772,7 +1800,7 @@ def loudness_energies(x, rate=24000, lens=None, state=None, offset=0, out=None, 
     d.state_in = state.data_ptr() if state is not None else None
     d.state_out = state_out.data_ptr() if state_out is not None else None
     d.peak, d.ws = peak.data_ptr(), ws.data_ptr()
-    d.x_bs, d.e_bs = (x.stride(0) if B > 1 else T), (out.stride(0) if B > 1 else out.shape[1])
+    d.x_bs, d.e_bs = _row_pitch(x, B, T), _row_pitch(out, B, out.shape[1])
     d.B, d.T, d.S, d.offset, d.peak_accumulate = B, T, S, offset, 1 if acc else 0
     d.coef[:] = coef.tolist()
     for k in range(7):
@@ -1787,8 +1815,7 @@ def loudness_gate(e, n_samples, rate=24000, lens=None, last_n=0, peaks=None):
     ungated (4: momentary, 30: short-term).  Never below -70."""
     S = _kweight_tables(rate)[0]
     B = e.shape[0]
-    if not e.is_cuda:
-        raise _lib.FacodecHipError(f"loudness_gate: e must live on the GPU (got {e.device}); there is no CPU path")
+    _on_gpu(e, "loudness_gate: e")
     if e.dtype != torch.float64 or e.dim() != 2 or (e.shape[1] > 1 and e.stride(1) != 1) or e.shape[1] < -(-int(n_samples) // S):
         raise ValueError(f"loudness_gate: e must be float64 (B, >= {-(-int(n_samples) // S)}) with dense rows, got {e.dtype} {tuple(e.shape)}")
     L = torch.empty(B, device=e.device, dtype=torch.float64)
@@ -1800,7 +1827,7 @@ def loudness_gate(e, n_samples, rate=24000, lens=None, last_n=0, peaks=None):
         return L if peaks is None else (L, pk)
     # a row without sub-blocks is never read; keep the pointer valid all the same
     e_ptr = e if e.numel() else torch.zeros(1, device=e.device, dtype=torch.float64)
-    _lib.check(_lib.load().fac_loudness_gate(_ptr(e_ptr), e.stride(0) if B > 1 else e.shape[1], _ptr(_lens(lens, B) if lens is not None else None),
+    _lib.check(_lib.load().fac_loudness_gate(_ptr(e_ptr), _row_pitch(e, B, e.shape[1]), _ptr(_lens(lens, B) if lens is not None else None),
                                              int(n_samples), S, int(last_n), _ptr(peaks), peaks.shape[1] if peaks is not None else 0,
                                              _ptr(L), _ptr(pk), B, _stream()), "fac_loudness_gate")
     return L if peaks is None else (L, pk)
@@ -1824,9 +1851,9 @@ def loudness_gain(x, L, peak=None, target_db=-16.0, target_rows=None, lens=None,
     y = torch.empty_like(x2) if out is None else _rows(out, "loudness_gain")
     g = torch.empty(B, device=x2.device, dtype=torch.float32)
     if B and T:
-        _lib.check(_lib.load().fac_loudness_gain(_ptr(x2), x2.stride(0) if B > 1 else T, _ptr(_lens(lens, B) if lens is not None else None),
+        _lib.check(_lib.load().fac_loudness_gain(_ptr(x2), _row_pitch(x2, B, T), _ptr(_lens(lens, B) if lens is not None else None),
                                                  _ptr(L), _ptr(peak), _ptr(target_rows), float(target_db), 1 if guard else 0,
-                                                 _ptr(y), y.stride(0) if B > 1 else T, _ptr(g), B, T, _stream()), "fac_loudness_gain")
+                                                 _ptr(y), _row_pitch(y, B, T), _ptr(g), B, T, _stream()), "fac_loudness_gain")
     elif B:
         g.fill_(1.0)
     return y.view(x.shape) if out is None else out, g
@@ -1868,48 +1895,29 @@ def agc_params(rate=24000, target_db=-23.0, window=30, max_boost_db=30.0, max_cu
     return AgcParams(S, W, target_db, max_boost_db, max_cut_db, ceiling, LA)
 
 
-def _f64_rows(t, B, n, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < n \
-            or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what} must be float64 ({B}, >= {n}) on the GPU with dense rows, got {getattr(t, 'dtype', type(t))} "
-                         f"{tuple(getattr(t, 'shape', ()))}")
-    return t
-
-
-def _i64_rows(t, B, what):
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or tuple(t.shape) != (B,) or not t.is_contiguous():
-        raise ValueError(f"{what} must be contiguous int64 ({B},) on the GPU")
-    return t
-
-
 def agc_gains(e, p, j0=0, n_new=None, R=None, lens=None, j_start=None, G=None, g=None):
     """fac_agc_gains over the sub-block energies e (B, >= R) float64 (sub-block j at column j % R; a plain array is R = its
     width, j0 = 0) with p = agc_params(...): the gains of sub-blocks j0 .. j0 + n_new - 1 -> (G dB, g linear), float64 (B, R)
     written at columns j % R (allocated when not given).  lens (B,) int32: the rows' lengths in samples, sub-blocks that are
     not complete get G = 0, g = 1.  j_start (B,) int64: the first sub-block of every row's current stream."""
-    if not isinstance(e, torch.Tensor) or not e.is_cuda:
-        raise _lib.FacodecHipError(f"agc_gains: e must live on the GPU (got {getattr(e, 'device', type(e))}); there is no CPU path")
-    B = e.shape[0]
+    B = _on_gpu(e, "agc_gains: e").shape[0]
     R = e.shape[1] if R is None else int(R)
     n_new = R - int(j0) if n_new is None else int(n_new)
-    e = _f64_rows(e, B, R, "agc_gains: e")
+    _arg(e, "agc_gains: e", torch.float64, (B, R), at_least=True)
     if G is None:
         G = torch.zeros(B, R, device=e.device, dtype=torch.float64)
     if g is None:
         g = torch.ones(B, R, device=e.device, dtype=torch.float64)
-    G, g = _f64_rows(G, B, R, "agc_gains: G"), _f64_rows(g, B, R, "agc_gains: g")
+    _arg(G, "agc_gains: G", torch.float64, (B, R), at_least=True), _arg(g, "agc_gains: g", torch.float64, (B, R), at_least=True)
     if G.stride(0) != g.stride(0) and B > 1:
         raise ValueError("agc_gains: G and g must have the same row pitch")
     if B == 0 or n_new == 0:
         return G, g
     d = _lib.AgcGainsDesc()
     d.e, d.lens = e.data_ptr(), (_lens(lens, B).data_ptr() if lens is not None else None)
-    j_start = _i64_rows(j_start, B, "agc_gains: j_start")
-    d.j_start = j_start.data_ptr() if j_start is not None else None
+    d.j_start = _ptr(_arg(j_start, "agc_gains: j_start", torch.int64, (B,), optional=True))
     d.G, d.g = G.data_ptr(), g.data_ptr()
-    d.e_bs, d.g_bs, d.j0 = (e.stride(0) if B > 1 else e.shape[1]), (g.stride(0) if B > 1 else g.shape[1]), int(j0)
+    d.e_bs, d.g_bs, d.j0 = _row_pitch(e, B, e.shape[1]), _row_pitch(g, B, g.shape[1]), int(j0)
     d.target_db, d.max_boost_db, d.max_cut_db = p.target_db, p.max_boost_db, p.max_cut_db
     d.B, d.n_new, d.R, d.W, d.S = B, n_new, R, p.W, p.S
     _lib.check(_lib.load().fac_agc_gains(C.byref(d), _stream()), "fac_agc_gains")
@@ -1922,34 +1930,28 @@ def agc_apply(x, g, p, n0=0, R=None, lens=None, j_start=None, carry_in=None, car
     with this block) and k without; y runs LA samples behind x.  n0: the absolute index of x[:, 0].  carry_in / carry_out
     (B, 2 LA) float64, two different buffers of a stream; lens (B,) int32 only without them.  k = 0 with flush is the flush of
     a stream alone (x may be None).  out: a preallocated (B, >= n_out) float32 buffer with dense rows."""
-    if not isinstance(g, torch.Tensor) or not g.is_cuda:
-        raise _lib.FacodecHipError(f"agc_apply: g must live on the GPU (got {getattr(g, 'device', type(g))}); there is no CPU path")
+    B = _on_gpu(g, "agc_apply: g").shape[0]
     if x is not None:
         x = _rows(x, "agc_apply")
-    B = g.shape[0]
     k = (x.shape[1] if x is not None else 0) if k is None else int(k)
     R = g.shape[1] if R is None else int(R)
-    g = _f64_rows(g, B, R, "agc_apply: g")
+    _arg(g, "agc_apply: g", torch.float64, (B, R), at_least=True)
     n_out = k + p.LA if flush else k
     if out is None:
         out = torch.empty(B, n_out, device=g.device, dtype=torch.float32)
-    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_out or (out.shape[1] > 1 and out.stride(1) != 1):
-        raise ValueError(f"agc_apply: out must be float32 ({B}, >= {n_out}) on the GPU with dense rows")
+    else:
+        _arg(out, "agc_apply: out", torch.float32, (B, n_out), at_least=True)
     if B == 0 or n_out == 0:
         return out[:, :n_out]
-    for t, name in ((carry_in, "carry_in"), (carry_out, "carry_out")):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (B, 2 * p.LA) or not t.is_contiguous()):
-            raise ValueError(f"agc_apply: {name} must be contiguous float64 ({B}, {2 * p.LA}) on the GPU")
     d = _lib.AgcApplyDesc()
-    d.carry_in = carry_in.data_ptr() if carry_in is not None else None
-    d.carry_out = carry_out.data_ptr() if carry_out is not None else None
+    d.carry_in = _ptr(_arg(carry_in, "agc_apply: carry_in", torch.float64, (B, 2 * p.LA), optional=True))
+    d.carry_out = _ptr(_arg(carry_out, "agc_apply: carry_out", torch.float64, (B, 2 * p.LA), optional=True))
     d.x = x.data_ptr() if x is not None and k > 0 else None
     d.lens = _lens(lens, B).data_ptr() if lens is not None else None
-    j_start = _i64_rows(j_start, B, "agc_apply: j_start")
-    d.j_start = j_start.data_ptr() if j_start is not None else None
+    d.j_start = _ptr(_arg(j_start, "agc_apply: j_start", torch.int64, (B,), optional=True))
     d.g, d.y = g.data_ptr(), out.data_ptr()
-    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
-    d.g_bs, d.y_bs, d.n0 = (g.stride(0) if B > 1 else g.shape[1]), (out.stride(0) if B > 1 else out.shape[1]), int(n0)
+    d.x_bs = _row_pitch(x, B, max(k, 1))
+    d.g_bs, d.y_bs, d.n0 = _row_pitch(g, B, g.shape[1]), _row_pitch(out, B, out.shape[1]), int(n0)
     d.ceiling = p.ceiling
     d.B, d.k, d.n_out, d.S, d.LA, d.R = B, k, n_out, p.S, p.LA, R
     _lib.check(_lib.load().fac_agc_apply(C.byref(d), _stream()), "fac_agc_apply")
@@ -2045,12 +2047,6 @@ def _ns_ring(t, B, R, what, dtype=torch.float64, last=()):
     return t
 
 
-def _ns_carry(t, B, what):
-    if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (B, NS_CARRY) or not t.is_contiguous()):
-        raise ValueError(f"{what} must be contiguous float32 ({B}, {NS_CARRY}) on the GPU")
-    return t
-
-
 def _ns_pitch(t, B):
     """Row pitch of a (B, R, 257[, 2]) ring in elements of 8 (or, for spectra, 16) bytes."""
     per = 2 if t.dim() == 4 else 1
@@ -2062,11 +2058,9 @@ def ns_power(x, P, n0=0, f0=0, n_new=None, R=None, lens=None, starts=None, carry
     index n0 + i) into the ring P (B, >= R, 257) float64, frame f at slot f % R; X (B, >= R, 257, 2) float64 also takes the
     spectra.  n_new defaults to the frames of an offline signal of k samples.  carry_in / carry_out (B, 1023) float32: two
     different buffers of a stream; lens (B,) int32 only without them; starts (B,) int64: the rows' first samples."""
-    if not isinstance(P, torch.Tensor) or not P.is_cuda:
-        raise _lib.FacodecHipError(f"ns_power: P must live on the GPU (got {getattr(P, 'device', type(P))}); there is no CPU path")
+    B = _on_gpu(P, "ns_power: P").shape[0]
     if x is not None:
         x = _rows(x, "ns_power")
-    B = P.shape[0]
     k = (x.shape[1] if x is not None else 0) if k is None else int(k)
     R = P.shape[1] if R is None else int(R)
     n_new = ns_frames(k) if n_new is None else int(n_new)
@@ -2078,13 +2072,13 @@ def ns_power(x, P, n0=0, f0=0, n_new=None, R=None, lens=None, starts=None, carry
     if B == 0 or (n_new == 0 and carry_out is None):
         return P
     d = _lib.NsPowerDesc()
-    d.carry_in = _ptr(_ns_carry(carry_in, B, "ns_power: carry_in"))
-    d.carry_out = _ptr(_ns_carry(carry_out, B, "ns_power: carry_out"))
+    d.carry_in = _ptr(_arg(carry_in, "ns_power: carry_in", torch.float32, (B, NS_CARRY), optional=True))
+    d.carry_out = _ptr(_arg(carry_out, "ns_power: carry_out", torch.float32, (B, NS_CARRY), optional=True))
     d.x = x.data_ptr() if x is not None and k > 0 else None
     d.lens = _lens(lens, B).data_ptr() if lens is not None else None
-    d.starts = _ptr(_i64_rows(starts, B, "ns_power: starts"))
+    d.starts = _ptr(_arg(starts, "ns_power: starts", torch.int64, (B,), optional=True))
     d.P, d.X = P.data_ptr(), _ptr(X)
-    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
+    d.x_bs = _row_pitch(x, B, max(k, 1))
     d.p_bs, d.n0, d.f0 = _ns_pitch(P, B), int(n0), int(f0)
     d.B, d.k, d.n_new, d.R = B, k, n_new, R
     _lib.check(_lib.load().fac_ns_power(C.byref(d), _stream()), "fac_ns_power")
@@ -2094,9 +2088,7 @@ def ns_power(x, P, n0=0, f0=0, n_new=None, R=None, lens=None, starts=None, carry
 def ns_gains(P, p, f0=0, n_new=None, R=None, starts=None, G=None):
     """fac_ns_gains over the ring P (B, >= R, 257) float64 with p = ns_params(...): the gains of frames f0 .. f0 + n_new - 1 -> G
     (B, R, 257) float64, frame f at slot f % R (allocated when not given)."""
-    if not isinstance(P, torch.Tensor) or not P.is_cuda:
-        raise _lib.FacodecHipError(f"ns_gains: P must live on the GPU (got {getattr(P, 'device', type(P))}); there is no CPU path")
-    B = P.shape[0]
+    B = _on_gpu(P, "ns_gains: P").shape[0]
     R = P.shape[1] if R is None else int(R)
     n_new = R - int(f0) if n_new is None else int(n_new)
     P = _ns_ring(P, B, R, "ns_gains: P")
@@ -2106,7 +2098,7 @@ def ns_gains(P, p, f0=0, n_new=None, R=None, starts=None, G=None):
     if B == 0 or n_new == 0:
         return G
     d = _lib.NsGainsDesc()
-    d.P, d.G, d.starts = P.data_ptr(), G.data_ptr(), _ptr(_i64_rows(starts, B, "ns_gains: starts"))
+    d.P, d.G, d.starts = P.data_ptr(), G.data_ptr(), _ptr(_arg(starts, "ns_gains: starts", torch.int64, (B,), optional=True))
     d.p_bs, d.g_bs, d.f0 = _ns_pitch(P, B), _ns_pitch(G, B), int(f0)
     d.over, d.g_min = p.over, p.g_min
     d.B, d.n_new, d.R, d.M, d.W = B, n_new, R, p.M, p.W
@@ -2118,11 +2110,9 @@ def ns_synth(x, G, n0=0, m0=0, n_out=None, R=None, lens=None, starts=None, carry
     """fac_ns_synth: y[m0 .. m0 + n_out) (B, n_out) float32 of [carry | x] masked with the gains G (B, >= R, 257) float64 (frame
     f at slot f % R): both frames over every output segment are transformed (or, with X, read from that ring), masked,
     transformed back, windowed and added.  n_out defaults to k (with n0 = m0 = 0: the offline call)."""
-    if not isinstance(G, torch.Tensor) or not G.is_cuda:
-        raise _lib.FacodecHipError(f"ns_synth: G must live on the GPU (got {getattr(G, 'device', type(G))}); there is no CPU path")
+    B = _on_gpu(G, "ns_synth: G").shape[0]
     if x is not None:
         x = _rows(x, "ns_synth")
-    B = G.shape[0]
     k = (x.shape[1] if x is not None else 0) if k is None else int(k)
     R = G.shape[1] if R is None else int(R)
     n_out = k if n_out is None else int(n_out)
@@ -2133,18 +2123,18 @@ def ns_synth(x, G, n0=0, m0=0, n_out=None, R=None, lens=None, starts=None, carry
             raise ValueError("ns_synth: X and G must have the same row pitch")
     if out is None:
         out = torch.empty(B, n_out, device=G.device, dtype=torch.float32)
-    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_out or (out.shape[1] > 1 and out.stride(1) != 1):
-        raise ValueError(f"ns_synth: out must be float32 ({B}, >= {n_out}) on the GPU with dense rows")
+    else:
+        _arg(out, "ns_synth: out", torch.float32, (B, n_out), at_least=True)
     if B == 0 or n_out == 0:
         return out[:, :n_out]
     d = _lib.NsSynthDesc()
-    d.carry_in = _ptr(_ns_carry(carry_in, B, "ns_synth: carry_in"))
+    d.carry_in = _ptr(_arg(carry_in, "ns_synth: carry_in", torch.float32, (B, NS_CARRY), optional=True))
     d.x = x.data_ptr() if x is not None and k > 0 else None
     d.lens = _lens(lens, B).data_ptr() if lens is not None else None
-    d.starts = _ptr(_i64_rows(starts, B, "ns_synth: starts"))
+    d.starts = _ptr(_arg(starts, "ns_synth: starts", torch.int64, (B,), optional=True))
     d.G, d.X, d.y = G.data_ptr(), _ptr(X), out.data_ptr()
-    d.x_bs = (x.stride(0) if B > 1 else max(k, 1)) if x is not None else max(k, 1)
-    d.g_bs, d.y_bs, d.n0, d.m0 = _ns_pitch(G, B), (out.stride(0) if B > 1 else out.shape[1]), int(n0), int(m0)
+    d.x_bs = _row_pitch(x, B, max(k, 1))
+    d.g_bs, d.y_bs, d.n0, d.m0 = _ns_pitch(G, B), _row_pitch(out, B, out.shape[1]), int(n0), int(m0)
     d.B, d.k, d.n_out, d.R = B, k, n_out, R
     _lib.check(_lib.load().fac_ns_synth(C.byref(d), _stream()), "fac_ns_synth")
     return out[:, :n_out]
@@ -2219,27 +2209,13 @@ def aec_state_sizes(P, delay=0):
     return tuple(int(v) for v in sizes)
 
 
-def _aec_state(t, B, P, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (B, P, AEC_BINS, 2) or not t.is_contiguous():
-        raise ValueError(f"{what} must be contiguous float64 ({B}, {P}, {AEC_BINS}, 2) on the GPU")
-    return t
-
-
-def _aec_f32(t, B, n, what):
-    if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (B, n) or not t.is_contiguous()):
-        raise ValueError(f"{what} must be contiguous float32 ({B}, {n}) on the GPU")
-    return t
-
-
 def aec_run(mic, far, p, W, X, n0=0, m0=0, n_out=None, blk0=0, n_blk=None, lens=None, starts=None, adapt=None, mic_carry=(None, None),
             far_carry=(None, None), e_ring=None, stats=None, k=None):
     """fac_aec_run with p = aec_params(...): the blocks blk0 .. blk0 + n_blk - 1 of [carry | mic], [carry | far] (both (B, k)
     float32, sample i at the absolute index n0 + i) on the state W, X (B, P, 257, 2) float64, updated in place -> e[m0 .. m0 +
     n_out) (B, n_out) float32.  mic_carry / far_carry: (in, out) pairs of two different buffers (B, 255) / (B, 511 + delay);
     e_ring (B, 256) float32; stats (B, n_blk, 3) float64; adapt (B,) int32; lens (B,) int32 only offline; starts (B,) int64."""
-    if not isinstance(W, torch.Tensor) or not W.is_cuda:
-        raise _lib.FacodecHipError(f"aec_run: W must live on the GPU (got {getattr(W, 'device', type(W))}); there is no CPU path")
-    B = W.shape[0]
+    B = _on_gpu(W, "aec_run: W").shape[0]
     if mic is not None:
         mic, far = _rows(mic, "aec_run"), _rows(far, "aec_run")
         if mic.shape != far.shape:
@@ -2247,27 +2223,23 @@ def aec_run(mic, far, p, W, X, n0=0, m0=0, n_out=None, blk0=0, n_blk=None, lens=
     k = (mic.shape[1] if mic is not None else 0) if k is None else int(k)
     n_out = k if n_out is None else int(n_out)
     n_blk = aec_blocks(k) if n_blk is None else int(n_blk)
-    W, X = _aec_state(W, B, p.P, "aec_run: W"), _aec_state(X, B, p.P, "aec_run: X")
+    _arg(W, "aec_run: W", torch.float64, (B, p.P, AEC_BINS, 2)), _arg(X, "aec_run: X", torch.float64, (B, p.P, AEC_BINS, 2))
     far_cn = _lib.AEC_FAR_CARRY + p.delay
     y = torch.empty(B, n_out, device=W.device, dtype=torch.float32)
     if B == 0 or n_out == 0:
         return y
-    if stats is not None and (not stats.is_cuda or stats.dtype != torch.float64 or tuple(stats.shape) != (B, n_blk, 3) or not stats.is_contiguous()):
-        raise ValueError(f"aec_run: stats must be contiguous float64 ({B}, {n_blk}, 3) on the GPU")
-    if adapt is not None and (not isinstance(adapt, torch.Tensor) or not adapt.is_cuda or adapt.dtype != torch.int32 or tuple(adapt.shape) != (B,)
-                              or not adapt.is_contiguous()):
-        raise ValueError(f"aec_run: adapt must be contiguous int32 ({B},) on the GPU")
+    _arg(stats, "aec_run: stats", torch.float64, (B, n_blk, 3), optional=True)
+    _arg(adapt, "aec_run: adapt", torch.int32, (B,), optional=True)
     d = _lib.AecDesc()
-    d.mic_carry_in, d.mic_carry_out = (_ptr(_aec_f32(t, B, _lib.AEC_MIC_CARRY, "aec_run: mic carry")) for t in mic_carry)
-    d.far_carry_in, d.far_carry_out = (_ptr(_aec_f32(t, B, far_cn, "aec_run: far carry")) for t in far_carry)
+    d.mic_carry_in, d.mic_carry_out = (_ptr(_arg(t, "aec_run: mic carry", torch.float32, (B, _lib.AEC_MIC_CARRY), optional=True)) for t in mic_carry)
+    d.far_carry_in, d.far_carry_out = (_ptr(_arg(t, "aec_run: far carry", torch.float32, (B, far_cn), optional=True)) for t in far_carry)
     d.mic = mic.data_ptr() if mic is not None and k > 0 else None
     d.far = far.data_ptr() if far is not None and k > 0 else None
     d.lens = _lens(lens, B).data_ptr() if lens is not None else None
-    d.starts = _ptr(_i64_rows(starts, B, "aec_run: starts"))
+    d.starts = _ptr(_arg(starts, "aec_run: starts", torch.int64, (B,), optional=True))
     d.adapt = _ptr(adapt)
-    d.W, d.X, d.e_ring, d.y, d.stats = W.data_ptr(), X.data_ptr(), _ptr(_aec_f32(e_ring, B, AEC_H, "aec_run: e_ring")), y.data_ptr(), _ptr(stats)
-    d.mic_bs = (mic.stride(0) if B > 1 else max(k, 1)) if mic is not None else max(k, 1)
-    d.far_bs = (far.stride(0) if B > 1 else max(k, 1)) if far is not None else max(k, 1)
+    d.W, d.X, d.e_ring, d.y, d.stats = W.data_ptr(), X.data_ptr(), _ptr(_arg(e_ring, "aec_run: e_ring", torch.float32, (B, AEC_H), optional=True)), y.data_ptr(), _ptr(stats)
+    d.mic_bs, d.far_bs = _row_pitch(mic, B, max(k, 1)), _row_pitch(far, B, max(k, 1))
     d.y_bs, d.w_bs, d.xr_bs, d.s_bs = n_out, p.P * AEC_BINS * 2, p.P * AEC_BINS * 2, 3 * n_blk
     d.n0, d.m0, d.blk0 = int(n0), int(m0), int(blk0)
     d.mu, d.c, d.delta = p.mu, p.c, p.delta

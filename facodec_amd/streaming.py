@@ -1116,7 +1116,53 @@ class LoudnessMeter:
         return self._gate(0)
 
 
-class VoiceActivity:
+class _Stage:
+    """What the streaming stages in front of a session share (VoiceActivity, AutoGain, NoiseSuppressor, EchoCanceller, each over
+    B rows on one device, with rings of R entries where it has any): the guards of push and finish, the check of a pushed
+    block, row indices on the device, the last entries of a ring, and a long push run as several."""
+    _done = False
+
+    def __init_subclass__(cls):
+        cls._what = cls.__name__ + ".push"                  # how push's refusals name their caller
+
+    def _close(self):
+        if self._done:
+            raise RuntimeError("finish() twice")
+        self._done = True
+
+    def _block(self, block):
+        """push()'s argument, (B, 1, k) or (B, k) float32 on the GPU with k >= 1 -> its (B, k) view."""
+        if self._done:
+            raise RuntimeError("push() after finish()")
+        x = ops._rows(block, self._what)
+        if x.shape[0] != self.B or x.shape[1] < 1:
+            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
+        return x
+
+    def _rows_idx(self, rows, what):
+        """Row indices on the host -> an int64 tensor on the device, None for no rows."""
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.B for r in rows):
+            raise ValueError(f"{what}({rows}): rows are 0 .. {self.B - 1}")
+        return ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device) if rows else None
+
+    def _ring_tail(self, ring, have, n):
+        """Entries have - n .. have - 1 of a ring (B, R, ...) that holds entry j at slot j % R: a copy."""
+        return ring[:, torch.arange(have - n, have, device=self.device) % self.R]
+
+    def _push_pieces(self, block):
+        """push() of a stage whose rings bound what one run may take: self._run on consecutive pieces of the block, each of at
+        most self._room() samples (asked again before every piece) -> the pieces' outputs, concatenated, in the block's shape."""
+        x = self._block(block)
+        parts, t, k = [], 0, x.shape[1]
+        while t < k:
+            n = min(k - t, self._room())
+            parts.append(self._run(x[:, t:t + n]))
+            t += n
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)).view(block.shape)
+
+
+class VoiceActivity(_Stage):
     """Voice activity detection over B parallel streams, one block at a time:
 
         vad = VoiceActivity(B)                               # frames of 300 samples: the codec's frames
@@ -1144,7 +1190,6 @@ class VoiceActivity:
         self._carry_n = self._cur = 0
         self._e = torch.zeros(self.B, self.R, device=self.device, dtype=torch.float64)
         self._flags = torch.zeros(self.B, self.R, device=self.device, dtype=torch.uint8)
-        self._done = False
 
     def _run(self, x, final):
         k = x.shape[-1]
@@ -1162,12 +1207,7 @@ class VoiceActivity:
             self.frames += n_new
 
     def push(self, block):
-        if self._done:
-            raise RuntimeError("push() after finish()")
-        x = ops._rows(block, "VoiceActivity.push")
-        if x.shape[0] != self.B or x.shape[1] < 1:
-            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
-        self._run(x, False)
+        self._run(self._block(block), False)
 
     def finish(self):
         """Decides the partial last frame, if there is one; the session takes no more audio."""
@@ -1200,11 +1240,10 @@ class VoiceActivity:
         """(B, n) float64: the energies of the last n decided frames (a copy out of the ring; for tests and meters)."""
         if not 1 <= n <= min(self.frames, self.R):
             raise ValueError(f"energies({n}): {min(self.frames, self.R)} frames are in the ring")
-        idx = torch.arange(self.frames - n, self.frames, device=self.device) % self.R
-        return self._e[:, idx]
+        return self._ring_tail(self._e, self.frames, n)
 
 
-class AutoGain:
+class AutoGain(_Stage):
     """Causal level control over B parallel streams, one block at a time:
 
         agc = AutoGain(B)                                    # rate 24000, -23 LUFS over 3 s, ceiling -1 dBFS, 120 samples ahead
@@ -1247,7 +1286,6 @@ class AutoGain:
         self._cur = 0
         self.peak = torch.zeros(self.B, device=self.device, dtype=torch.float32)
         self._ws = None
-        self._done = False
 
     @property
     def decided(self):
@@ -1271,27 +1309,15 @@ class AutoGain:
         self.samples += k
         return y
 
-    def push(self, block):
-        if self._done:
-            raise RuntimeError("push() after finish()")
-        x = ops._rows(block, "AutoGain.push")
-        if x.shape[0] != self.B or x.shape[1] < 1:
-            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
-        parts, t, k = [], 0, x.shape[1]
-        while t < k:
-            j0, offset = divmod(self.samples, self.S)
-            room = min(self.R - j0 % self.R, self.R - self.p.W - 2) * self.S - offset      # up to the ring's end, and within its reach
-            n = min(k - t, room)
-            parts.append(self._run(x[:, t:t + n]))
-            t += n
-        y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-        return y.view(block.shape)
+    def _room(self):
+        j0, offset = divmod(self.samples, self.S)
+        return min(self.R - j0 % self.R, self.R - self.p.W - 2) * self.S - offset          # up to the ring's end, and within its reach
+
+    push = _Stage._push_pieces
 
     def finish(self):
         """(B, lookahead) float32: the samples the limiter was still holding back; the stream takes no more audio."""
-        if self._done:
-            raise RuntimeError("finish() twice")
-        self._done = True
+        self._close()
         return ops.agc_apply(None, self._g, self.p, n0=self.samples, R=self.R, j_start=self._j_start, carry_in=self._carry[self._cur],
                              flush=True, k=0)
 
@@ -1300,23 +1326,56 @@ class AutoGain:
         and meters)."""
         if not 1 <= n <= min(self.decided, self.R):
             raise ValueError(f"gains({n}): {min(self.decided, self.R)} decided gains are in the ring")
-        idx = torch.arange(self.decided - n, self.decided, device=self.device) % self.R
-        return self._G[:, idx], self._g[:, idx]
+        return self._ring_tail(self._G, self.decided, n), self._ring_tail(self._g, self.decided, n)
 
     def reset(self, rows):
         """Puts the given rows (indices on the host) back into the state of a fresh stream, on the device."""
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.B for r in rows):
-            raise ValueError(f"reset({rows}): rows are 0 .. {self.B - 1}")
-        if not rows:
+        idx = self._rows_idx(rows, "reset")
+        if idx is None:
             return
-        idx = ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device)
         for t, v in ((self._state, 0.0), (self._carry[self._cur], 0.0), (self._e, 0.0), (self._G, 0.0), (self._g, 1.0), (self.peak, 0.0)):
             t.index_fill_(0, idx, v)
         self._j_start.index_fill_(0, idx, -(-self.samples // self.S))
 
 
-class LevelledSession:
+class _FrontEndSession:
+    """A session that takes audio, with one front-end stage in front of it: what LevelledSession, DenoisedSession and
+    EchoCancelledSession share.  `stage` is the stage's class, built with the session's B, the rate it takes its audio at and
+    its device, and kept under the attribute `name`; prime and push hand the session what the stage's push makes of their
+    arguments, every other attribute of the session reads through."""
+
+    def __init__(self, session, stage, name, **parameters):
+        if not hasattr(session, "prime_samples") or not session.prime_samples:
+            raise ValueError(f"{type(self).__name__}: this session takes codes, not audio")
+        self.session = session
+        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
+        inner = session
+        while not hasattr(inner, "B"):                               # a ResampledSession keeps them on the session it wraps
+            inner = inner.session
+        self.B, self.device = inner.B, inner.device
+        self._stage = stage(self.B, self.rate, device=self.device, **parameters)
+        setattr(self, name, self._stage)
+        self.latency_in = self._stage.latency + getattr(session, "latency_in", 0.0)
+
+    def __getattr__(self, name):
+        if name == "session":
+            raise AttributeError(name)
+        return getattr(self.session, name)
+
+    def prime(self, *audio):
+        return self.session.prime(self._stage.push(*audio))
+
+    def push(self, *audio):
+        return self.session.push(self._stage.push(*audio))
+
+    def finish(self):
+        return self.session.finish()
+
+    def set_target(self, timbre):
+        return self.session.set_target(timbre)
+
+
+class LevelledSession(_FrontEndSession):
     """A StreamingCodec, a StreamingConverter or a ResampledSession of one whose input goes through an AutoGain first:
 
         codec = LevelledSession(StreamingCodec(model, timbre), target_db=-23.0)
@@ -1329,34 +1388,11 @@ class LevelledSession:
     ceiling_db, lookahead, ring), whose defaults were not tuned by listening.  The applied gain does not travel with the codes."""
 
     def __init__(self, session, **parameters):
-        if not hasattr(session, "prime_samples") or not session.prime_samples:
-            raise ValueError("LevelledSession: this session takes codes, not audio")
-        self.session = session
-        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
-        inner = session if hasattr(session, "B") else session.session           # a ResampledSession keeps them on the session it wraps
-        self.agc = AutoGain(inner.B, self.rate, device=inner.device, **parameters)
+        super().__init__(session, AutoGain, "agc", **parameters)
         self.lookahead = self.agc.lookahead
-        self.latency_in = self.agc.latency + getattr(session, "latency_in", 0.0)
-
-    def __getattr__(self, name):
-        if name == "session":
-            raise AttributeError(name)
-        return getattr(self.session, name)
-
-    def prime(self, first):
-        return self.session.prime(self.agc.push(first))
-
-    def push(self, hop):
-        return self.session.push(self.agc.push(hop))
-
-    def finish(self):
-        return self.session.finish()
-
-    def set_target(self, timbre):
-        return self.session.set_target(timbre)
 
 
-class NoiseSuppressor:
+class NoiseSuppressor(_Stage):
     """Spectral noise suppression over B parallel streams, one block at a time:
 
         ns = NoiseSuppressor(B)                              # M = 8, W = 96, over = 4.0, max_atten_db = 15.0
@@ -1394,7 +1430,6 @@ class NoiseSuppressor:
         self._start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
         self._carry = [torch.zeros(self.B, ops.NS_CARRY, device=self.device, dtype=torch.float32) for _ in range(2)]
         self._cur = 0
-        self._done = False
 
     @property
     def frames(self):
@@ -1414,26 +1449,14 @@ class NoiseSuppressor:
         self.samples += k
         return y
 
-    def push(self, block):
-        if self._done:
-            raise RuntimeError("push() after finish()")
-        x = ops._rows(block, "NoiseSuppressor.push")
-        if x.shape[0] != self.B or x.shape[1] < 1:
-            raise ValueError(f"push() takes (B = {self.B}, 1, k) or (B, k) with k >= 1, got {tuple(block.shape)}")
-        parts, t, k = [], 0, x.shape[1]
-        while t < k:
-            room = (self.R - self._reach) * ops.NS_H - self.samples % ops.NS_H     # completes at most ring - reach frames
-            n = min(k - t, room)
-            parts.append(self._run(x[:, t:t + n]))
-            t += n
-        y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-        return y.view(block.shape)
+    def _room(self):
+        return (self.R - self._reach) * ops.NS_H - self.samples % ops.NS_H         # completes at most ring - reach frames
+
+    push = _Stage._push_pieces
 
     def finish(self):
         """(B, 512) float32: the samples still held back; the stream takes no more audio."""
-        if self._done:
-            raise RuntimeError("finish() twice")
-        self._done = True
+        self._close()
         f0 = self.frames
         n_new = ops.ns_frames(self.samples) - f0                     # the one or two frames that reach past the end
         src = self._carry[self._cur]
@@ -1449,23 +1472,19 @@ class NoiseSuppressor:
         have = self._final if self._done else self.frames
         if not 1 <= n <= min(have, self.R):
             raise ValueError(f"gains({n}): {min(have, self.R)} decided frames are in the ring")
-        idx = torch.arange(have - n, have, device=self.device) % self.R
-        return self._G[:, idx]
+        return self._ring_tail(self._G, have, n)
 
     def reset(self, rows):
         """Puts the given rows (indices on the host) back into the state of a fresh stream that begins at `samples`, on the device."""
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.B for r in rows):
-            raise ValueError(f"reset({rows}): rows are 0 .. {self.B - 1}")
-        if not rows:
+        idx = self._rows_idx(rows, "reset")
+        if idx is None:
             return
-        idx = ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device)
         for t, v in ((self._carry[self._cur], 0.0), (self._P, 0.0), (self._G, 1.0)):
             t.index_fill_(0, idx, v)
         self._start.index_fill_(0, idx, self.samples)
 
 
-class DenoisedSession:
+class DenoisedSession(_FrontEndSession):
     """A StreamingCodec, a StreamingConverter, a ResampledSession or a LevelledSession of one whose input goes through a
     NoiseSuppressor first:
 
@@ -1479,36 +1498,10 @@ class DenoisedSession:
     **parameters: NoiseSuppressor's (M, W, over, max_atten_db, ring), whose defaults were not tuned by listening."""
 
     def __init__(self, session, **parameters):
-        if not hasattr(session, "prime_samples") or not session.prime_samples:
-            raise ValueError("DenoisedSession: this session takes codes, not audio")
-        self.session = session
-        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
-        inner = session
-        while not hasattr(inner, "B"):                               # a ResampledSession keeps them on the session it wraps
-            inner = inner.session
-        self.B, self.device = inner.B, inner.device
-        self.ns = NoiseSuppressor(self.B, self.rate, device=self.device, **parameters)
-        self.latency_in = self.ns.latency + getattr(session, "latency_in", 0.0)
-
-    def __getattr__(self, name):
-        if name == "session":
-            raise AttributeError(name)
-        return getattr(self.session, name)
-
-    def prime(self, first):
-        return self.session.prime(self.ns.push(first))
-
-    def push(self, hop):
-        return self.session.push(self.ns.push(hop))
-
-    def finish(self):
-        return self.session.finish()
-
-    def set_target(self, timbre):
-        return self.session.set_target(timbre)
+        super().__init__(session, NoiseSuppressor, "ns", **parameters)
 
 
-class EchoCanceller:
+class EchoCanceller(_Stage):
     """Acoustic echo cancellation over B parallel streams, one block at a time:
 
         aec = EchoCanceller(B)                               # P = 8, mu = 0.5, beta = 1.0, delta = 1e-6, delay = 0
@@ -1553,7 +1546,6 @@ class EchoCanceller:
         self._start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
         self._adapt = torch.full((self.B,), 1 if adapt else 0, device=self.device, dtype=torch.int32)
         self._cur = 0
-        self._done = False
 
     @property
     def blocks(self):
@@ -1567,10 +1559,8 @@ class EchoCanceller:
                            far_carry=(self._far[c], self._far[1 - c] if carry_out else None), e_ring=self._ring, k=k)
 
     def push(self, mic, far):
-        if self._done:
-            raise RuntimeError("push() after finish()")
-        m, f = ops._rows(mic, "EchoCanceller.push"), ops._rows(far, "EchoCanceller.push")
-        if m.shape[0] != self.B or m.shape[1] < 1 or m.shape != f.shape:
+        m, f = self._block(mic), ops._rows(far, self._what)
+        if m.shape != f.shape:
             raise ValueError(f"push() takes two (B = {self.B}, 1, k) or (B, k) of one length k >= 1, got {tuple(mic.shape)} and {tuple(far.shape)}")
         k = m.shape[1]
         y = self._run(m, f, k, (self.samples + k) // ops.AEC_H - self.blocks, k, True)
@@ -1580,20 +1570,12 @@ class EchoCanceller:
 
     def finish(self):
         """(B, 256) float32: the samples still held back, the open block padded with zeros; the stream takes no more audio."""
-        if self._done:
-            raise RuntimeError("finish() twice")
-        self._done = True
+        self._close()
         return self._run(None, None, 0, 1 if self.samples % ops.AEC_H else 0, self.delay, False)
 
     def weights(self):
         """-> W (B, P, 257, 2) float64: the filters after the last complete block (a copy; for tests and meters)."""
         return self._W.clone()
-
-    def _rows_idx(self, rows, what):
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.B for r in rows):
-            raise ValueError(f"{what}({rows}): rows are 0 .. {self.B - 1}")
-        return ops.h2d(torch.tensor(rows, dtype=torch.int64), self.device) if rows else None
 
     def set_adapt(self, rows, on):
         """The given rows (indices on the host) adapt, or only filter, from the next block on."""
@@ -1608,7 +1590,7 @@ class EchoCanceller:
             self._start.index_fill_(0, idx, self.samples)
 
 
-class EchoCancelledSession:
+class EchoCancelledSession(_FrontEndSession):
     """A StreamingCodec, a StreamingConverter, a ResampledSession, a LevelledSession or a DenoisedSession of one whose input
     goes through an EchoCanceller first:
 
@@ -1626,33 +1608,7 @@ class EchoCancelledSession:
     beta, delta, delay, adapt), whose defaults were not tuned by listening."""
 
     def __init__(self, session, **parameters):
-        if not hasattr(session, "prime_samples") or not session.prime_samples:
-            raise ValueError("EchoCancelledSession: this session takes codes, not audio")
-        self.session = session
-        self.rate = int(getattr(session, "in_rate", MODEL_RATE))
-        inner = session
-        while not hasattr(inner, "B"):                               # a ResampledSession keeps them on the session it wraps
-            inner = inner.session
-        self.B, self.device = inner.B, inner.device
-        self.aec = EchoCanceller(self.B, self.rate, device=self.device, **parameters)
-        self.latency_in = self.aec.latency + getattr(session, "latency_in", 0.0)
-
-    def __getattr__(self, name):
-        if name == "session":
-            raise AttributeError(name)
-        return getattr(self.session, name)
-
-    def prime(self, first, far):
-        return self.session.prime(self.aec.push(first, far))
-
-    def push(self, hop, far):
-        return self.session.push(self.aec.push(hop, far))
-
-    def finish(self):
-        return self.session.finish()
-
-    def set_target(self, timbre):
-        return self.session.set_target(timbre)
+        super().__init__(session, EchoCanceller, "aec", **parameters)
 
 
 class ResampledSession:

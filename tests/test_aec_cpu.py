@@ -419,6 +419,82 @@ def test_parameter_checks_of_the_python_surface():
         aec.push(torch.zeros(3, 480), torch.zeros(3, 480))
 
 
+def test_front_end_wrappers_keep_their_surface():
+    """LevelledSession, DenoisedSession and EchoCancelledSession: (session, **parameters), the refusal of a session that takes
+    codes, the attributes, and prime / push / finish / set_target, on a stand-in session and without a GPU."""
+    import inspect
+    import torch
+    from facodec_amd import streaming
+
+    class Inner:
+        prime_samples, B, device, hop_samples = 4800, 2, torch.device("cpu"), 480
+
+        def __init__(self):
+            self.calls = []
+
+        def prime(self, first):
+            raise AssertionError("the stage runs first, and it has no CPU path")
+
+        push = prime
+
+        def finish(self):
+            self.calls.append("finish")
+            return "finished"
+
+        def set_target(self, timbre):
+            self.calls.append(("set_target", timbre))
+            return "set"
+
+    class Outer:                                     # keeps B and device on the session it wraps, as ResampledSession does
+        prime_samples, in_rate, latency_in = 9600, 48000, 0.25
+
+        def __init__(self, session):
+            self.session = session
+            self.prime = self.push = session.prime
+
+        def finish(self):
+            return self.session.finish()
+
+        def set_target(self, timbre):
+            return self.session.set_target(timbre)
+
+    class TakesCodes:
+        prime_samples = None
+
+    cases = ((streaming.LevelledSession, "agc", streaming.AutoGain, dict(target_db=-20.0), 1),
+             (streaming.DenoisedSession, "ns", streaming.NoiseSuppressor, dict(M=4), 1),
+             (streaming.EchoCancelledSession, "aec", streaming.EchoCanceller, dict(P=2, delay=7), 2))
+    for cls, name, stage, parameters, n_audio in cases:
+        sig = inspect.signature(cls)
+        assert list(sig.parameters) == ["session", "parameters"] and sig.parameters["parameters"].kind is inspect.Parameter.VAR_KEYWORD
+        for bad in (object(), TakesCodes()):
+            with pytest.raises(ValueError) as err:
+                cls(bad)
+            assert str(err.value) == f"{cls.__name__}: this session takes codes, not audio"
+        assert cls.__doc__ and stage.__name__ in cls.__doc__
+        for wrapped, rate, base in ((Inner(), 24000, 0.0), (Outer(Inner()), 48000, 0.25)):
+            s = cls(wrapped, **parameters)
+            st = getattr(s, name)
+            assert isinstance(st, stage) and (st.B, st.rate, st.device) == (2, rate, torch.device("cpu"))
+            assert s.session is wrapped and s.rate == rate and (s.B, s.device) == (2, torch.device("cpu"))
+            assert s.latency_in == st.latency + base
+            assert s.prime_samples == wrapped.prime_samples                  # what the wrapper does not have reads through
+            with pytest.raises(AttributeError):
+                s.no_such_attribute
+            assert s.finish() == "finished" and s.set_target("t") == "set"
+            inner = wrapped if isinstance(wrapped, Inner) else wrapped.session
+            assert inner.calls == ["finish", ("set_target", "t")]
+            for call in (s.prime, s.push):                                   # through the stage's push first: it refuses the CPU
+                with pytest.raises(_lib.FacodecHipError, match="no CPU path"):
+                    call(*[torch.zeros(2, 1, 480)] * n_audio)
+        if name == "agc":
+            assert s.lookahead == s.agc.lookahead == 120
+        if name == "aec":
+            assert (s.aec.p.P, s.aec.far_delay) == (2, 7)
+    defined = [c for c in (streaming.LevelledSession, streaming.DenoisedSession, streaming.EchoCancelledSession) if "__getattr__" in vars(c)]
+    assert defined == []                                                     # the pass-through is written once, in their base
+
+
 def test_desc_layout_matches_the_header(tmp_path):
     import os
     import shutil

@@ -24,8 +24,9 @@ T = 30000
 LENS = (30000, 2561, 256, 255, 1, 0)      # a full window; one sample into a new frame; exactly one hop; one less; one sample; empty
 MW = [(8, 96), (2, 5)]
 MW_IDS = ["M8-W96", "M2-W5"]
-FIRST = [(1, 7, 479, 2400), ()]
-FIRST_IDS = ["ragged-blocks", "480-hops"]
+# the last: 3, 4, 5 and 2 frames in one push, so that the power kernel's last round of four waves holds 3, 4, 1 and 2 frames
+FIRST = [(1, 7, 479, 2400), (), (768, 1024, 1280, 512)]
+FIRST_IDS = ["ragged-blocks", "480-hops", "whole-frame-blocks"]
 
 
 def bits(a):
