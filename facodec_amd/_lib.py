@@ -165,6 +165,21 @@ class AecDesc(C.Structure):
     ]
 
 
+EDELAY_MAX_DELAY, EDELAY_MAX_LAGS, EDELAY_MIC_RING, EDELAY_POL = 16384, 65, 511, 4     # FAC_EDELAY_*
+
+
+class EdelayDesc(C.Structure):
+    _fields_ = [
+        ("mic", _p), ("far", _p), ("lens", _p), ("starts", _p), ("mic_ring", _p), ("far_ring", _p), ("C", _p), ("X", _p), ("act", _p),
+        ("pol", _p), ("conf_last", _p), ("y", _p), ("raw", _p), ("locked", _p), ("used", _p), ("conf", _p), ("ok", _p), ("score", _p),
+        ("mic_bs", _i64), ("far_bs", _i64), ("y_bs", _i64), ("c_bs", _i64), ("xr_bs", _i64), ("f_bs", _i64), ("n0", _i64), ("frm0", _i64),
+        ("a", C.c_double), ("eps", C.c_double), ("gate", C.c_double), ("thr", C.c_double),
+        ("B", C.c_int32), ("k", C.c_int32), ("n_frm", C.c_int32), ("f_ring", C.c_int32), ("max_delay", C.c_int32), ("far_rn", C.c_int32),
+        ("k_lo", C.c_int32), ("k_hi", C.c_int32), ("hold", C.c_int32), ("tol", C.c_int32), ("move", C.c_int32), ("margin", C.c_int32),
+        ("delay0", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class SidApplyDesc(C.Structure):
     _fields_ = [
         ("dst", _p * 3), ("dst_bs", _i64 * 3), ("dst_qs", _i64 * 3), ("n_q", C.c_int32 * 3), ("B", C.c_int32),
@@ -357,6 +372,8 @@ SIGNATURES = {
     "fac_ns_synth": (_i, [C.POINTER(NsSynthDesc), _p]),
     "fac_aec_run": (_i, [C.POINTER(AecDesc), _p]),
     "fac_aec_state_sizes": (_i, [_i, _i, C.POINTER(_i64)]),
+    "fac_edelay_run": (_i, [C.POINTER(EdelayDesc), _p]),
+    "fac_edelay_state_sizes": (_i, [_i, C.POINTER(_i64)]),
     "fac_true_peak_ws_bytes": (_i64, [_i, _i]),
     "fac_true_peak": (_i, [C.POINTER(ResampleDesc), _p, _p, _p]),
     "fac_codes_pack": (_i, [C.POINTER(CodesPackDesc), _p]),

@@ -847,9 +847,14 @@ def echo_cancel_clips(mics, fars, max_batch_samples=MAX_BATCH_SAMPLES, **paramet
     fars[i], (T_i,) or (1, T_i), float32 on the GPU, are one call's microphone and far-end signals, of one length.  They go
     through plan_groups' zero-padded groups with their lengths: one ops.echo_cancel call (one C call) per group, nothing is
     read back; a clip comes out as the single-clip call gives it, bit for bit, whatever it is grouped with.  **parameters:
-    ops.echo_cancel's P, mu, beta, delta, delay -- whose defaults were not tuned by listening."""
+    ops.echo_cancel's P, mu, beta, delta, delay -- whose defaults were not tuned by listening; with delay="auto" also
+    ops.echo_delay_params', and each group is two C calls."""
     from . import ops
-    ops.aec_params(**parameters)                                    # ValueError: the parameters
+    if parameters.get("delay") == "auto":                           # ValueError: the parameters
+        ops.aec_params(**{k: v for k, v in parameters.items() if k != "delay" and k not in ops.ECHO_DELAY_NAMES})
+        ops.echo_delay_params(**{k: v for k, v in parameters.items() if k in ops.ECHO_DELAY_NAMES})
+    else:
+        ops.aec_params(**parameters)
     mics, fars = list(mics), list(fars)
     if len(mics) != len(fars):
         raise ValueError(f"{len(mics)} microphone clips and {len(fars)} far-end clips")
@@ -871,6 +876,40 @@ def echo_cancel_clips(mics, fars, max_batch_samples=MAX_BATCH_SAMPLES, **paramet
         r = ops.echo_cancel(mic, far, lens=lens, **parameters)
         for j, i in enumerate(group):
             out[i] = ops.EchoCancelled(r.e[j, :lengths[i]], r.W[j], r.stats[j, :ops.aec_blocks(lengths[i])])
+    return out
+
+
+def echo_delay_clips(mics, fars, max_batch_samples=MAX_BATCH_SAMPLES, **parameters):
+    """The playout-to-capture delay (ops.echo_delay) of clips of different lengths -> per clip, in the caller's
+    order, (locked, conf): the latched delay in samples after the clip's last frame (-1: never latched) and that frame's
+    confidence, on the host; (-1, 0.0) for a clip under 512 samples, which has no frame.  mics[i] and fars[i] as
+    echo_cancel_clips takes them.  They go through plan_groups' zero-padded groups with their lengths: one ops.echo_delay call
+    (one C call) and one device-to-host copy per group.  **parameters: ops.echo_delay_params', not tuned by listening."""
+    from . import ops
+    p = ops.echo_delay_params(**parameters)                         # ValueError: the parameters
+    mics, fars = list(mics), list(fars)
+    if len(mics) != len(fars):
+        raise ValueError(f"{len(mics)} microphone clips and {len(fars)} far-end clips")
+    if not mics:
+        return []
+    _need_gpu(mics, "clips")
+    _need_gpu(fars, "clips")
+    for m, f in zip(mics, fars):
+        if not (m.dim() == 1 or (m.dim() == 2 and m.shape[0] == 1)) or not (f.dim() == 1 or (f.dim() == 2 and f.shape[0] == 1)):
+            raise ValueError(f"every clip must be (T,) or (1, T), got {tuple(m.shape)} and {tuple(f.shape)}")
+        if m.shape[-1] != f.shape[-1]:
+            raise ValueError(f"a microphone clip of {m.shape[-1]} samples with a far-end clip of {f.shape[-1]}")
+    lengths = [int(m.shape[-1]) for m in mics]
+    out = [None] * len(mics)
+    for group in plan_groups(lengths, max_batch_samples):
+        mic = torch.nn.utils.rnn.pad_sequence([mics[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        far = torch.nn.utils.rnn.pad_sequence([fars[i].reshape(-1).to(torch.float32) for i in group], batch_first=True)
+        lens = ops.h2d(torch.tensor([lengths[i] for i in group], dtype=torch.int32), mic.device)
+        state = ops.edelay_state(len(group), p, mic.device)
+        ops.echo_delay(mic, far, lens=lens, state=state, **parameters)
+        last = torch.cat([state["pol"][:, 2].to(torch.float64)[:, None], state["conf_last"][:, None]], dim=1).cpu()     # the one copy
+        for j, i in enumerate(group):
+            out[i] = (int(last[j, 0]), float(last[j, 1]))
     return out
 
 

@@ -2262,7 +2262,7 @@ def _aec_adapt(adapt, B, device):
     return h2d(torch.tensor(flags, dtype=torch.int32), device)
 
 
-def echo_cancel(mic, far, lens=None, starts=None, P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0, adapt=None):
+def echo_cancel(mic, far, lens=None, starts=None, P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0, adapt=None, **delay_params):
     """Acoustic echo cancellation of mic against the far-end reference far, both (B, T) or (B, 1, T) float32 on the GPU
      -> EchoCancelled(e, W, stats): e of mic's shape, float32, aligned with it: the microphone less the estimate
     of the echo; W (B, P, 257, 2) float64, the filter after the row's last block (partition p holds taps 256 p .. 256 p + 255
@@ -2274,9 +2274,17 @@ def echo_cancel(mic, far, lens=None, starts=None, P=8, mu=0.5, beta=1.0, delta=1
     lens[b] samples, nothing behind them is read and e comes out 0 there.  starts (B,) int: row b's stream begins at sample
     starts[b]; earlier samples of both signals count as zero, the filter starts from zero at block starts[b] // 256, outputs
     before starts[b] are 0.  One C call (fac_aec_run), one workgroup per row that walks the blocks in order, no host read;
-    what streaming.EchoCanceller gives for the same signals, 256 samples earlier.  There is no delay estimator, no
-    residual-echo suppressor and no double-talk detector beyond the error term of the step.  The arithmetic is pinned in
-    include/facodec_hip.h; the defaults were not tuned by listening."""
+    what streaming.EchoCanceller gives for the same signals, 256 samples earlier.  delay="auto" (with **delay_params,
+    echo_delay_params') finds the delay on the device: it is echo_cancel(mic, echo_delay(mic, far, ...).far, delay=0, ...)
+    (DESIGN.md 36).  There is no residual-echo suppressor and no double-talk detector beyond the error term of the step.  The
+    arithmetic is pinned in include/facodec_hip.h; the defaults were not tuned by listening."""
+    if isinstance(delay, str):
+        if delay != "auto":
+            raise ValueError(f"echo_cancel: delay = {delay!r} (an integer or \"auto\")")
+        aec_params(P, mu, beta, delta, 0), echo_delay_params(**delay_params)       # every refusal before the first launch
+        far, delay = echo_delay(mic, far, lens=lens, starts=starts, **delay_params).far, 0
+    elif delay_params:
+        raise TypeError(f"echo_cancel: {sorted(delay_params)} go with delay=\"auto\" only")
     p = aec_params(P, mu, beta, delta, delay)
     m2, f2 = _rows(mic, "echo_cancel"), _rows(far, "echo_cancel")
     if m2.shape != f2.shape:
@@ -2297,6 +2305,153 @@ def echo_cancel(mic, far, lens=None, starts=None, P=8, mu=0.5, beta=1.0, delta=1
     X = torch.zeros(B, p.P, AEC_BINS, 2, device=dev, dtype=torch.float64)
     e = aec_run(m2, f2, p, W, X, lens=lens, starts=starts, adapt=_aec_adapt(adapt, B, dev), stats=stats)
     return EchoCancelled(e.view(mic.shape), W, stats)
+
+
+# --------------------------------------------------------------------------------- echo delay
+EchoDelayParams = namedtuple("EchoDelayParams", "max_delay k_lo k_hi a eps gate thr hold tol move margin delay0 L")
+EchoDelay = namedtuple("EchoDelay", "far raw locked used conf ok score")
+ECHO_DELAY_NAMES = EchoDelayParams._fields[:-1]
+
+
+def echo_delay_params(max_delay=16384, k_lo=6, k_hi=134, a=0.05, eps=1e-20, gate=1e-8, thr=0.1, hold=8, tol=128, move=256, margin=128, delay0=0):
+    """-> EchoDelayParams(max_delay, k_lo, k_hi, a, eps, gate, thr, hold, tol, move, margin, delay0, L) of fac_edelay_run: lags 0 ..
+    L = ceil(max_delay / 256) of 256 samples; the bins k_lo .. k_hi - 1 of a 512-point transform (about 0.28 to 6.2 kHz at
+    24 kHz); a the smoothing of the cross-spectra, eps what keeps their normalisation finite; gate the mean square above which a
+    frame is active; a raw delay counts when the best lag's score reaches thr; hold agreeing frames (within tol samples) latch
+    it, a later run re-latches only move samples or more away; the far end is moved by the latched delay less margin samples,
+    by delay0 before the first latch.  None of the defaults was tuned by listening."""
+    for name, v in (("max_delay", max_delay), ("k_lo", k_lo), ("k_hi", k_hi), ("hold", hold), ("tol", tol), ("move", move), ("margin", margin),
+                    ("delay0", delay0)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"echo_delay: {name} = {v} is not an integer")
+    max_delay, k_lo, k_hi, hold, tol, move, margin, delay0 = (int(v) for v in (max_delay, k_lo, k_hi, hold, tol, move, margin, delay0))
+    a, eps, gate, thr = float(a), float(eps), float(gate), float(thr)
+    if not 1 <= max_delay <= _lib.EDELAY_MAX_DELAY:
+        raise ValueError(f"echo_delay: max_delay = {max_delay} outside 1 .. {_lib.EDELAY_MAX_DELAY} samples")
+    if not (0 <= k_lo < k_hi <= AEC_BINS and k_hi - k_lo <= AEC_H):
+        raise ValueError(f"echo_delay: band k_lo = {k_lo}, k_hi = {k_hi} (0 <= k_lo < k_hi <= 257, at most 256 bins)")
+    if not 0.0 < a <= 1.0:
+        raise ValueError(f"echo_delay: a = {a} outside (0, 1]")
+    if not 0.0 < eps < math.inf:
+        raise ValueError(f"echo_delay: eps = {eps} (finite, positive)")
+    if not 0.0 <= gate < math.inf:
+        raise ValueError(f"echo_delay: gate = {gate} (finite, not negative)")
+    if not 0.0 <= thr < math.inf:
+        raise ValueError(f"echo_delay: thr = {thr} (finite, not negative)")
+    if hold < 1:
+        raise ValueError(f"echo_delay: hold = {hold} below 1 frame")
+    if tol < 0 or move < 0 or margin < 0:
+        raise ValueError(f"echo_delay: tol = {tol}, move = {move}, margin = {margin} (not negative)")
+    if not 0 <= delay0 <= max_delay:
+        raise ValueError(f"echo_delay: delay0 = {delay0} outside 0 .. max_delay = {max_delay}")
+    return EchoDelayParams(max_delay, k_lo, k_hi, a, eps, gate, thr, hold, tol, move, margin, delay0, -(-max_delay // AEC_H))
+
+
+def echo_delay_frames(n):
+    """Frames of a signal of n samples: frame m >= 1 covers the blocks m - 1 and m, so max(n // 256 - 1, 0)."""
+    return max(int(n) // AEC_H - 1, 0)
+
+
+def edelay_state_sizes(max_delay=16384):
+    """fac_edelay_state_sizes: per-row (doubles of C, doubles of the X ring, ints of the activity ring, ints of the policy, floats
+    of the mic ring, floats of the far ring)."""
+    sizes = (C.c_int64 * 6)()
+    _lib.check(_lib.load().fac_edelay_state_sizes(int(max_delay), sizes), "fac_edelay_state_sizes")
+    return tuple(int(v) for v in sizes)
+
+
+def edelay_state(B, p, device, rings=False):
+    """A fresh state of fac_edelay_run for B rows: dict(C, X, act, pol, conf_last[, mic_ring, far_ring]) on `device`."""
+    n_c, n_x, n_act, n_pol, n_mic, n_far = edelay_state_sizes(p.max_delay)
+    L1 = p.L + 1
+    assert n_c == n_x == L1 * AEC_BINS * 2 and n_act == L1
+    st = dict(C=torch.zeros(B, L1, AEC_BINS, 2, device=device, dtype=torch.float64), X=torch.zeros(B, L1, AEC_BINS, 2, device=device, dtype=torch.float64),
+              act=torch.zeros(B, n_act, device=device, dtype=torch.int32),
+              pol=torch.tensor([-1, 0, -1, p.delay0], dtype=torch.int32).repeat(B, 1).to(device),
+              conf_last=torch.zeros(B, device=device, dtype=torch.float64))
+    if rings:
+        st["mic_ring"] = torch.zeros(B, n_mic, device=device, dtype=torch.float32)
+        st["far_ring"] = torch.zeros(B, n_far, device=device, dtype=torch.float32)
+    return st
+
+
+def edelay_run(mic, far, p, state, n0=0, frm0=1, n_frm=None, lens=None, starts=None, frames=None, f_ring=0):
+    """fac_edelay_run with p = echo_delay_params(...): the frames frm0 .. frm0 + n_frm - 1 of [ring | mic], [ring | far] (both
+    (B, k) float32, sample i at the absolute index n0 + i) on `state` (edelay_state: updated in place) -> the aligned far end
+    (B, k) float32.  frames: None, or a dict of per-frame output buffers raw, locked, used (int32), conf (float64), ok (uint8),
+    all (B, f_n), and score (B, f_n, L + 1) float64, any of them missing; f_n = n_frm, or f_ring > 0 columns used as a ring.
+    lens (B,) int32 only without rings; starts (B,) int64."""
+    mic, far = _rows(mic, "edelay_run"), _rows(far, "edelay_run")
+    if mic.shape != far.shape:
+        raise ValueError(f"edelay_run: mic {tuple(mic.shape)} and far {tuple(far.shape)} differ")
+    B, k = mic.shape
+    L1 = p.L + 1
+    n_frm = echo_delay_frames(k) if n_frm is None else int(n_frm)
+    y = torch.empty(B, k, device=mic.device, dtype=torch.float32)
+    if B == 0 or k == 0:
+        return y
+    f_n = int(f_ring) if f_ring else n_frm
+    frames = frames or {}
+    d = _lib.EdelayDesc()
+    d.mic, d.far, d.y = mic.data_ptr(), far.data_ptr(), y.data_ptr()
+    d.lens = _lens(lens, B).data_ptr() if lens is not None else None
+    d.starts = _ptr(_arg(starts, "edelay_run: starts", torch.int64, (B,), optional=True))
+    d.C = _arg(state["C"], "edelay_run: C", torch.float64, (B, L1, AEC_BINS, 2)).data_ptr()
+    d.X = _arg(state["X"], "edelay_run: X", torch.float64, (B, L1, AEC_BINS, 2)).data_ptr()
+    d.act = _arg(state["act"], "edelay_run: act", torch.int32, (B, L1)).data_ptr()
+    d.pol = _arg(state["pol"], "edelay_run: pol", torch.int32, (B, _lib.EDELAY_POL)).data_ptr()
+    d.conf_last = _arg(state["conf_last"], "edelay_run: conf_last", torch.float64, (B,)).data_ptr()
+    far_rn = L1 * AEC_H + AEC_H - 1
+    d.mic_ring = _ptr(_arg(state.get("mic_ring"), "edelay_run: mic_ring", torch.float32, (B, _lib.EDELAY_MIC_RING), optional=True))
+    d.far_ring = _ptr(_arg(state.get("far_ring"), "edelay_run: far_ring", torch.float32, (B, far_rn), optional=True))
+    for name, dtype in (("raw", torch.int32), ("locked", torch.int32), ("used", torch.int32), ("conf", torch.float64), ("ok", torch.uint8)):
+        setattr(d, name, _ptr(_arg(frames.get(name), f"edelay_run: {name}", dtype, (B, f_n), optional=True)))
+    d.score = _ptr(_arg(frames.get("score"), "edelay_run: score", torch.float64, (B, f_n, L1), optional=True))
+    d.mic_bs, d.far_bs, d.y_bs = _row_pitch(mic, B, k), _row_pitch(far, B, k), k
+    d.c_bs = d.xr_bs = L1 * AEC_BINS * 2
+    d.f_bs, d.n0, d.frm0 = f_n, int(n0), int(frm0)
+    d.a, d.eps, d.gate, d.thr = p.a, p.eps, p.gate, p.thr
+    d.B, d.k, d.n_frm, d.f_ring, d.max_delay, d.far_rn = B, k, n_frm, int(f_ring), p.max_delay, far_rn
+    d.k_lo, d.k_hi, d.hold, d.tol, d.move, d.margin, d.delay0 = p.k_lo, p.k_hi, p.hold, p.tol, p.move, p.margin, p.delay0
+    _lib.check(_lib.load().fac_edelay_run(C.byref(d), _stream()), "fac_edelay_run")
+    return y
+
+
+def _starts(starts, B, dev, what):
+    if starts is None:
+        return None
+    if not isinstance(starts, torch.Tensor) or tuple(starts.shape) != (B,) or starts.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: starts must be an int32 or int64 tensor ({B},)")
+    if not starts.is_cuda and bool((starts < 0).any()):
+        raise ValueError(f"{what}: starts must not be negative")
+    return h2d(starts, dev).to(torch.int64).contiguous()
+
+
+def echo_delay(mic, far, lens=None, starts=None, state=None, **params):
+    """The playout-to-capture delay of every row, frame by frame, and the far end moved by it: mic and far (B, T)
+    or (B, 1, T) float32 on the GPU -> EchoDelay(far, raw, locked, used, conf, ok, score).  far, of far's shape: the aligned far
+    end, far[n - used] with the `used` of the frame that ended before the sample's block of 256 -- no latency; what
+    ops.echo_cancel(mic, ., delay=0) wants.  Per frame m = 1 .. M = max(T // 256 - 1, 0), at column m - 1: raw (B, M) int32, the
+    delay the frame saw; locked int32, the latched delay, -1 before the first latch; used int32, what the aligner takes from the
+    next block on; conf float64, the best lag's score; ok uint8, whether raw counted; score (B, M, L + 1) float64.  A column
+    that is no frame of its row (behind lens[b] // 256 - 1 frames, before the frame starts[b] // 256 + 1) holds raw = locked =
+    used = -1 and conf = ok = score = 0.  lens, starts: as ops.echo_cancel's.  state: an ops.edelay_state to use and leave
+    updated (tests read C from it).  One C call, one workgroup per row, no host read.  **params: echo_delay_params'."""
+    p = echo_delay_params(**params)
+    m2, f2 = _rows(mic, "echo_delay"), _rows(far, "echo_delay")
+    if m2.shape != f2.shape:
+        raise ValueError(f"echo_delay: mic {tuple(m2.shape)} and far {tuple(f2.shape)} differ")
+    B, T = m2.shape
+    dev, M, L1 = m2.device, echo_delay_frames(T), p.L + 1
+    fr = dict(raw=torch.full((B, M), -1, device=dev, dtype=torch.int32), locked=torch.full((B, M), -1, device=dev, dtype=torch.int32),
+              used=torch.full((B, M), -1, device=dev, dtype=torch.int32), conf=torch.zeros(B, M, device=dev, dtype=torch.float64),
+              ok=torch.zeros(B, M, device=dev, dtype=torch.uint8), score=torch.zeros(B, M, L1, device=dev, dtype=torch.float64))
+    if B == 0 or T == 0:
+        return EchoDelay(torch.zeros_like(far), *fr.values())
+    starts = _starts(starts, B, dev, "echo_delay")
+    state = edelay_state(B, p, dev) if state is None else state
+    y = edelay_run(m2, f2, p, state, lens=lens, starts=starts, frames=fr if M else None)
+    return EchoDelay(y.view(far.shape), fr["raw"], fr["locked"], fr["used"], fr["conf"], fr["ok"], fr["score"])
 
 
 # --------------------------------------------------------------------------------- objective scores (DESIGN.md 27)

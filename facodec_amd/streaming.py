@@ -1524,8 +1524,8 @@ class EchoCanceller(_Stage):
     reset(rows) restarts the given rows on the device: their stream begins at `samples`, the filter starts from zero at the
     block that holds that sample, the 256 samples of the old stream that were not played yet come out as zeros, and the rows
     then give row b of ops.echo_cancel(concat(old, new), concat(old, new), starts=samples), 256 samples late, bit for bit.
-    The other rows are not touched.  There is no delay estimator, no clock-drift compensation and no residual-echo
-    suppressor; the defaults were not tuned by listening."""
+    The other rows are not touched.  A delay nobody knows is found by AlignedEchoCanceller.  There is no
+    clock-drift compensation and no residual-echo suppressor; the defaults were not tuned by listening."""
 
     def __init__(self, B, rate=MODEL_RATE, P=8, mu=0.5, beta=1.0, delta=1e-6, delay=0, adapt=True, device="cuda"):
         self.p = ops.aec_params(P, mu, beta, delta, delay)
@@ -1605,10 +1605,152 @@ class EchoCancelledSession(_FrontEndSession):
     argument.  The canceller runs at the rate the session takes its audio at, eagerly, around the session's captured graphs:
     one C call per push.  The session sees 256 zeros and then the cancelled input, cut off where the pushed audio ends;
     `latency_in` is that delay, 256 / rate seconds, on top of the wrapped session's own.  **parameters: EchoCanceller's (P, mu,
-    beta, delta, delay, adapt), whose defaults were not tuned by listening."""
+    beta, delta, delay, adapt), whose defaults were not tuned by listening.  delay="auto" puts an AlignedEchoCanceller there
+    instead (two C calls per push, the same latency), which also takes ops.echo_delay_params' names."""
 
     def __init__(self, session, **parameters):
-        super().__init__(session, EchoCanceller, "aec", **parameters)
+        auto = isinstance(parameters.get("delay"), str)
+        if auto:
+            if parameters["delay"] != "auto":
+                raise ValueError(f"EchoCancelledSession: delay = {parameters['delay']!r} (an integer or \"auto\")")
+            parameters = {k: v for k, v in parameters.items() if k != "delay"}
+        super().__init__(session, AlignedEchoCanceller if auto else EchoCanceller, "aec", **parameters)
+
+
+class EchoDelayTracker(_Stage):
+    """The playout-to-capture delay of B parallel streams, found and followed on the device, and the far end moved by it
+    (DESIGN.md 36):
+
+        trk = EchoDelayTracker(B)                            # max_delay = 16384, thr = 0.1, hold = 8, .. (ops.echo_delay_params)
+        aligned = trk.push(mic, far)                         # two (B, 1, k) or (B, k) float32 on the GPU, any k >= 1 -> far's shape
+        trk.delay(), trk.confidence()                        # (B,) int32, -1 while not latched; (B,) float64
+
+    aligned is far[n - used], `used` being the latched delay less a margin as of the last frame that ended before the sample's
+    block of 256: every sample comes out in the push that brings it (`latency` is 0), and the pushes, concatenated, are
+    ops.echo_delay(whole mic, whole far).far, bit for bit, for any chunking -- frames lie on the canceller's absolute grid and a
+    frame is computed once, when a push completes it, by the kernel of the offline call.  push is one C call (fac_edelay_run;
+    a push that completes more than `ring` frames is run as several), reads nothing back and allocates nothing but its output.
+    The state is all on the device: the cross-spectra of the L + 1 lags, the far-end spectra and activities of the last L + 1
+    frames, the policy's integers, the last 511 microphone samples and the last max_delay + 511 far-end samples in rings indexed
+    by the absolute sample, the rows' starts, and rings of the last `ring` frames' decisions (frames(n)).
+
+    reset(rows) restarts the given rows on the device: their stream begins at `samples`, and they then give row b of
+    ops.echo_delay(concat(old, new), concat(old, new), starts=samples), bit for bit.  The other rows are not touched.  There is
+    no finish(): nothing is held back.  The defaults were not tuned by listening."""
+
+    latency = 0.0
+
+    def __init__(self, B, rate=MODEL_RATE, ring=64, device="cuda", **params):
+        self.p = ops.echo_delay_params(**params)
+        self.B, self.rate, self.R, self.device = int(B), int(rate), int(ring), torch.device(device)
+        if self.B < 1:
+            raise ValueError(f"EchoDelayTracker: B = {B}")
+        if self.R < 1:
+            raise ValueError(f"EchoDelayTracker: ring = {ring} below 1 frame")
+        self.samples = 0
+        self._st = ops.edelay_state(self.B, self.p, self.device, rings=True)
+        self._start = torch.zeros(self.B, device=self.device, dtype=torch.int64)
+        i32 = dict(device=self.device, dtype=torch.int32)
+        self._fr = dict(raw=torch.full((self.B, self.R), -1, **i32), locked=torch.full((self.B, self.R), -1, **i32),
+                        used=torch.full((self.B, self.R), -1, **i32), conf=torch.zeros(self.B, self.R, device=self.device, dtype=torch.float64),
+                        ok=torch.zeros(self.B, self.R, device=self.device, dtype=torch.uint8))
+
+    @property
+    def n_frames(self):
+        """Frames that are complete (on the host): frame m = 1 .. n_frames."""
+        return ops.echo_delay_frames(self.samples)
+
+    def _run(self, m, f):
+        k = m.shape[1]
+        frm0 = max(self.samples // ops.AEC_H, 1)
+        y = ops.edelay_run(m, f, self.p, self._st, n0=self.samples, frm0=frm0, n_frm=max((self.samples + k) // ops.AEC_H - frm0, 0),
+                           starts=self._start, frames=self._fr, f_ring=self.R)
+        self.samples += k
+        return y
+
+    def push(self, mic, far):
+        m, f = self._block(mic), ops._rows(far, self._what)
+        if m.shape != f.shape:
+            raise ValueError(f"push() takes two (B = {self.B}, 1, k) or (B, k) of one length k >= 1, got {tuple(mic.shape)} and {tuple(far.shape)}")
+        parts, t, k = [], 0, m.shape[1]
+        while t < k:
+            n = min(k - t, self.R * ops.AEC_H - self.samples % ops.AEC_H)     # completes at most `ring` frames
+            parts.append(self._run(m[:, t:t + n], f[:, t:t + n]))
+            t += n
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)).view(far.shape)
+
+    def delay(self):
+        """-> (B,) int32 on the device: the latched delay in samples, -1 while a row has not latched (a copy)."""
+        return self._st["pol"][:, 2].clone()
+
+    def confidence(self):
+        """-> (B,) float64 on the device: the best lag's score at the last frame (a copy)."""
+        return self._st["conf_last"].clone()
+
+    def frames(self, n):
+        """-> (raw, locked, used, conf, ok), each (B, n): the last n frames' decisions (copies out of the rings; for tests and meters)."""
+        have = self.n_frames + 1                                     # frame m lies at slot m % ring; there is no frame 0
+        if not 1 <= n <= min(have - 1, self.R):
+            raise ValueError(f"frames({n}): {min(have - 1, self.R)} frames are in the ring")
+        return tuple(self._ring_tail(self._fr[name], have, n) for name in ("raw", "locked", "used", "conf", "ok"))
+
+    def reset(self, rows):
+        """Restarts the given rows (indices on the host) as a stream that begins at `samples`, on the device."""
+        idx = self._rows_idx(rows, "reset")
+        if idx is None:
+            return
+        self._start.index_fill_(0, idx, self.samples)
+        pol = self._st["pol"]
+        pol[:, 0].index_fill_(0, idx, -1), pol[:, 1].index_fill_(0, idx, 0), pol[:, 2].index_fill_(0, idx, -1)
+        pol[:, 3].index_fill_(0, idx, self.p.delay0)
+        self._st["conf_last"].index_fill_(0, idx, 0.0)
+
+
+class AlignedEchoCanceller(_Stage):
+    """An EchoDelayTracker and, behind it, an EchoCanceller with delay = 0: echo cancellation for streams whose
+    playout-to-capture delay nobody knows:
+
+        aec = AlignedEchoCanceller(B, P=8, max_delay=16384)
+        e = aec.push(mic, far); tail = aec.finish(); aec.tracker.delay()
+
+    EchoCanceller's surface (push, finish, weights, set_adapt, reset, `latency`, `delay`, `samples`); the output is, bit for bit,
+    EchoCanceller(delay=0).push(mic, EchoDelayTracker.push(mic, far)): two C calls per push, nothing read back.  **params go to
+    the two stages by name: ops.echo_delay_params' names and `ring` to the tracker (`tracker`), P, mu, beta, delta and adapt to
+    the canceller (`canceller`); a name of neither, and `delay`, is refused.  reset(rows) resets both.  When the tracker
+    re-latches, the canceller's filter is not restarted: it re-converges on the moved far end by itself."""
+
+    def __init__(self, B, rate=MODEL_RATE, device="cuda", **params):
+        mine = {k: v for k, v in params.items() if k in ops.ECHO_DELAY_NAMES or k == "ring"}
+        rest = {k: v for k, v in params.items() if k not in mine}
+        unknown = sorted(k for k in rest if k not in ("P", "mu", "beta", "delta", "adapt"))
+        if unknown:
+            raise ValueError(f"AlignedEchoCanceller: {unknown} are parameters of neither the tracker nor the canceller (the delay is tracked)")
+        self.tracker = EchoDelayTracker(B, rate, device=device, **mine)
+        self.canceller = EchoCanceller(B, rate, delay=0, device=device, **rest)
+        self.B, self.rate, self.device, self.p = self.canceller.B, self.canceller.rate, self.canceller.device, self.canceller.p
+        self.delay, self.latency, self.far_delay = self.canceller.delay, self.canceller.latency, "auto"
+
+    @property
+    def samples(self):
+        return self.canceller.samples
+
+    def push(self, mic, far):
+        self._block(mic)
+        return self.canceller.push(mic, self.tracker.push(mic, far))
+
+    def finish(self):
+        self._close()
+        return self.canceller.finish()
+
+    def weights(self):
+        return self.canceller.weights()
+
+    def set_adapt(self, rows, on):
+        self.canceller.set_adapt(rows, on)
+
+    def reset(self, rows):
+        self.tracker.reset(rows)
+        self.canceller.reset(rows)
 
 
 class ResampledSession:

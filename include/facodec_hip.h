@@ -1517,6 +1517,98 @@ typedef struct fac_aec_desc {
 int fac_aec_run(const fac_aec_desc* d, fac_stream_t stream);
 int fac_aec_state_sizes(int P, int delay, int64_t* sizes);
 
+/* ------------------------------------------------------------------------------------------
+ * Echo delay (csrc/echo_delay.hip): a per-row estimator and tracker of the playout-to-capture delay -- a
+ * PHAT-weighted, recursively smoothed cross-spectrum per lag of 256 samples, a latch policy on its peak -- and the aligner that
+ * hands the canceller above a far end already moved by that delay, so that the canceller runs with delay = 0.  This comment is
+ * the normative definition.  The state is recursive in time; any chunking of a stream gives the bits of the offline call,
+ * because the frame grid is absolute, a frame is computed once, when its last sample is there, the frames of a row are computed
+ * in ascending order by one workgroup, and a sample of block j is aligned by what the frames up to j - 1 decided, which are
+ * complete before the block's first sample: the stage adds no latency.  Every operation below is one IEEE fp64 operation with
+ * one round-to-nearest; nothing is fused.  No parameter was tuned by listening.
+ *
+ * Geometry.  N = 512, H = 256: the canceller's block grid.  Row b has a microphone signal d and a far-end signal x, both fp32;
+ * the call's sample i has the absolute index n0 + i and exists for i < k_b = lens ? clamp(lens[b], 0, k) : k.  mic_ring (B,
+ * FAC_EDELAY_MIC_RING) and far_ring (B, far_rn), far_rn = (L + 1) H + 255, hold the samples in front of n0, sample n at slot
+ * n % 511 and n % far_rn (NULL: zeros).  A sample of either signal before start_b = starts ? max(starts[b], 0) : 0, at or behind
+ * end_b = n0 + k_b, or further back than its ring is 0 and is not read.  Frame m >= 1 covers the samples (m - 1) H .. (m + 1) H -
+ * 1 of both signals and is complete when sample (m + 1) H - 1 is there.  ms_b = start_b / H; the row's first frame is ms_b + 1,
+ * its last floor(end_b / H) - 1.  Window w[n] = sinpi((n + 0.5) / 512).  Lags l = 0 .. L, L = ceil(max_delay / H), 1 <=
+ * max_delay <= FAC_EDELAY_MAX_DELAY.  Bins k_lo .. k_hi - 1, 0 <= k_lo < k_hi <= 257, n_bins = k_hi - k_lo <= 256.  At frame
+ * ms_b + 1 every C_l = 0, (cand, run, locked) = (-1, 0, -1), and no earlier frame is active.  DFT512 and IDFT512 are the transform
+ * of the noise suppressor above, butterfly for butterfly.
+ *
+ * Per frame m, in this order:
+ *   1. X_m = DFT512(w f), f[n] = (double)x[(m - 1) H + n], and D_m = DFT512(w g), g the same of d; each product w[n] f[n] once
+ *      rounded, the imaginary input 0.  X_m is kept in the ring X (B, L + 1, 257, 2) at slot m % (L + 1), bins k_lo .. k_hi - 1.
+ *   2. actx_m = (sum f^2) / 512 > gate, actd_m the same of g; each sum by the tree v[j] += v[j + s], j < s, for s = 256, 128, .. 1,
+ *      over the 512 fp64 squares.  actx_m is kept in the ring act (B, L + 1) at slot m % (L + 1).
+ *   3. If actd_m: for every lag l with m - l >= ms_b + 1 and actx_{m-l}, and every bin k of the band, with x = X_{m-l}[k], d =
+ *      D_m[k]:  p = (x.x d.x + x.y d.y,  x.x d.y - x.y d.x), i.e. conj(x) d: four products, a sum, a difference;
+ *      den = sqrt(x.x x.x + x.y x.y) * sqrt(d.x d.x + d.y d.y) + eps;  q = (p.x / den, p.y / den);
+ *      C_l[k] = ((1 - a) C_l[k].x + a q.x,  (1 - a) C_l[k].y + a q.y), 1 - a computed once in fp64.  Any other C_l stays.
+ *   4. score_l = (sum over the band of C_l[k].x^2 + C_l[k].y^2) / n_bins for every l: the squares at j = k - k_lo, zeros up to
+ *      256 entries, summed by the tree v[j] += v[j + s], j < s, s = 128, 64, .. 1 (the canceller's step 8).
+ *   5. l* = the l of the largest score, compared with > in ascending l (the lowest l wins a tie); conf_m = score_{l*}.
+ *   6. G[k] = C_{l*}[k] in the band, 0 outside it, the imaginary parts of bins 0 and 256 set to 0, G[512 - k] = conj(G[k]) for k =
+ *      1 .. 255;  g = Re(IDFT512(G)) (its factor 1 / 512 does not matter);  n* = the n of the largest |g[n]|, n = 0 .. 511,
+ *      compared with > in ascending n;  r = n* < H ? n* : n* - N;  raw_m = max(0, l* H + r).
+ *   7. ok_m = conf_m >= thr and actd_m and m - l* >= ms_b + 1 and actx_{m-l*}.
+ *   8. The latch.  If ok_m: if cand >= 0 and |raw_m - cand| <= tol then run += 1, else cand = raw_m and run = 1.  Then, ok_m or
+ *      not: if run >= hold and (locked < 0 or |cand - locked| >= move) then locked = cand.  locked_m is locked after this step;
+ *      used_m = locked_m < 0 ? delay0 : max(0, locked_m - margin).  used_m = delay0 for m < ms_b + 1.
+ * The aligner: y[n] = x[n - used_{n / H - 1}] for start_b <= n < end_b, where the source index is not before start_b; 0 otherwise.
+ *
+ * fac_edelay_run computes, per row, the frames max(frm0, ms_b + 1) .. min(frm0 + n_frm, floor(end_b / H)) - 1 and writes the k
+ * aligned samples y[b * y_bs + i], sample n0 + i.  Per-frame outputs, each NULL or (B, f_n) of row pitch f_bs entries (score:
+ * (B, f_n, L + 1), row pitch f_bs (L + 1)): raw, locked, used int32, conf fp64, ok uint8, score fp64.  With f_ring = 0, f_n =
+ * n_frm and frame m is at column m - frm0; a column that is not a frame of the row holds raw = locked = used = -1, conf = 0, ok =
+ * 0, score = 0.  With f_ring > 0 (a stream's rings), f_n = f_ring >= n_frm, frame m is at column m % f_ring and no other column is
+ * written.  The state -- C (B, L + 1, 257, 2) fp64 of row pitch c_bs doubles, X of row pitch xr_bs doubles, act (B, L + 1) int32,
+ * pol (B, 4) int32 = (cand, run, locked, used) after the row's last computed frame, conf_last (B) fp64, the two rings -- is read
+ * (unless the call holds frame ms_b + 1) and written in place; only row b's workgroup touches row b's state, and the rings take
+ * the call's last samples behind the workgroup's last read.  Offline: n0 = 0, frm0 = 1, n_frm = max(k / H - 1, 0), no rings,
+ * zeroed state.  A stream: after n samples the frames below n / H are complete, so a push of k samples at n0 is frm0 = max(n0 /
+ * H, 1), n_frm = max((n0 + k) / H - frm0, 0).  One 512-thread workgroup per row walks the call's blocks: it aligns block j's
+ * samples, then computes frame j if the call completes it.  Steps 1 and 2 are one wave's per signal, 3 and 4 one wave per lag in
+ * ceil((L + 1) / 8) rounds, 5 to 8 wave 0's.  C and X stay in global memory (L2); 25472 bytes of LDS.
+ * Refused before any launch: a NULL descriptor, mic, far, C, X, act, pol, conf_last or y; B outside 1 .. 65535; k outside 1 ..
+ * 2^30; max_delay outside 1 .. FAC_EDELAY_MAX_DELAY; a band outside 0 <= k_lo < k_hi <= 257 or wider than 256 bins; a outside
+ * (0, 1]; eps not positive and finite; gate or thr negative or not finite; hold < 1; tol, move or margin negative; delay0 outside
+ * 0 .. max_delay; n0 negative; frm0 < max(n0 / H, 1); n_frm negative or frames that end behind n0 + k; one ring without the other;
+ * far_rn other than (L + 1) H + 255 with the rings; lens with the rings; f_ring negative or below n_frm; C and X the same buffer;
+ * mic_bs, far_bs or y_bs below k, c_bs or xr_bs below 514 (L + 1), f_bs below the columns, with B > 1.
+ *
+ * fac_edelay_state_sizes: the per-row sizes of a stream's state for max_delay into sizes[0 .. 5]: doubles of C, doubles of X,
+ * ints of act, ints of pol, floats of the mic ring, floats of the far ring.
+ * ---------------------------------------------------------------------------------------- */
+enum { FAC_EDELAY_MAX_DELAY = 16384, FAC_EDELAY_MAX_LAGS = 65, FAC_EDELAY_MIC_RING = 511, FAC_EDELAY_POL = 4 };
+typedef struct fac_edelay_desc {
+  const float* mic;           /* (B, k), pitch mic_bs */
+  const float* far;           /* (B, k), pitch far_bs */
+  const int32_t* lens;        /* (B) or NULL */
+  const int64_t* starts;      /* (B) or NULL */
+  float* mic_ring;            /* read and written: (B, 511), or NULL */
+  float* far_ring;            /* read and written: (B, far_rn), or NULL */
+  double* C;                  /* read and written: (B, L + 1, 257, 2), row pitch c_bs doubles */
+  double* X;                  /* read and written: (B, L + 1, 257, 2), row pitch xr_bs doubles, frame j at slot j % (L + 1) */
+  int32_t* act;               /* read and written: (B, L + 1), frame j at slot j % (L + 1) */
+  int32_t* pol;               /* read and written: (B, 4): cand, run, locked, used */
+  double* conf_last;          /* read and written: (B) */
+  float* y;                   /* written: (B, k), pitch y_bs: the aligned far end */
+  int32_t* raw;               /* written: (B, f_n), pitch f_bs, or NULL */
+  int32_t* locked;            /* the same */
+  int32_t* used;              /* the same */
+  double* conf;               /* the same */
+  uint8_t* ok;                /* the same */
+  double* score;              /* written: (B, f_n, L + 1), pitch f_bs (L + 1), or NULL */
+  int64_t mic_bs, far_bs, y_bs, c_bs, xr_bs, f_bs, n0, frm0;
+  double a, eps, gate, thr;
+  int32_t B, k, n_frm, f_ring, max_delay, far_rn, k_lo, k_hi, hold, tol, move, margin, delay0, reserved;
+} fac_edelay_desc;
+int fac_edelay_run(const fac_edelay_desc* d, fac_stream_t stream);
+int fac_edelay_state_sizes(int max_delay, int64_t* sizes);
+
 static inline int fac_pad32(int n) { return (n + 31) & ~31; }
 /* packed weights carry zero rows up to a multiple of 48 input channels (lcm of the kernel's
  * channels-per-stage choices), so a partially filled last stage multiplies zeros */
